@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: 25-member ensemble DYffusion sampling on the 180x360 grid (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--scaling strong|weak]
+    python bench.py --gpus N --steps K --warmup W [--scaling strong|weak] [--dump-outputs DIR]
 
 works by itself for any N (the parent starts one child process per GPU BEFORE anything touches HIP and relays rank 0's
 JSON line), and also under an external launcher:
@@ -107,16 +107,49 @@ def build_models(device):
     return exp
 
 
-def one_pass(exp, x0, forcings):
+def one_pass(exp, x0, forcings, outputs=None):
     """The stepper's per-window call pattern (stepper_multistep.py:365-427): horizon 1 runs the sampler, 2..6 read the cache;
-    returns the new autoregressive state (t6)."""
+    returns the new autoregressive state (t6).  `outputs`: a dict that receives every array the six calls returned."""
     out = None
     for h in range(1, HORIZON + 1):
         batch = {"dynamics": x0, "static_condition": forcings}
         with exp.ema_scope(), exp.inference_dropout_scope():
             out = exp.get_preds_at_t_for_batch(batch, horizon=h, split="predict", is_autoregressive=False,
                                                prepare_inputs=False, ensemble=False, num_predictions=1)
+        if outputs is not None:
+            outputs.update(out)
     return out[f"t{HORIZON}_preds_normed"]
+
+
+DUMP_BUDGET = 64 * 10 ** 6     # bytes of all files --dump-outputs writes, headers included
+DUMP_SEED = 20240601           # the fixed sample of an output too large for its share of the budget
+
+
+def dump_outputs(outputs, directory):
+    """`outputs` ({name: tensor}, what the timed path returned in its last step) -> directory/<name>.npy, float32 (float64
+    stays float64).  An array larger than its even share of DUMP_BUDGET is replaced by a seeded sample of its flattened
+    elements: the same positions for the same shape, so two builds run with the same arguments can be compared element by
+    element.  Returns {name: {"shape", "dtype", "elements"}} for the JSON line."""
+    import numpy as np
+    import torch
+
+    os.makedirs(directory, exist_ok=True)
+    names = sorted(outputs)
+    info = {}
+    for name in names:
+        t = outputs[name].detach()
+        t = t if t.dtype == torch.float64 else t.float()
+        shape, n = list(t.shape), t.numel()
+        per = (DUMP_BUDGET // len(names) - 4096) // t.element_size()      # 4096: room for the .npy header
+        if n > per:
+            g = torch.Generator(device="cpu").manual_seed(DUMP_SEED)
+            idx = torch.randint(n, (per,), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        arr = t.cpu().numpy()
+        np.save(os.path.join(directory, name + ".npy"), arr)
+        info[name] = {"shape": shape, "dtype": str(arr.dtype),
+                      "elements": "all" if arr.size == n else "seeded sample of %d" % arr.size}
+    return info
 
 
 def synthetic_state(ic_index, B, device):
@@ -374,10 +407,16 @@ def main():
     ap.add_argument("--no-relay", action="store_true",
                     help="strong scaling with the static split only (25 over 8 = 4,3,3,...), no relayed remainder members")
     ap.add_argument("--digests", action="store_true", help="add (sum, norm) of every trajectory's final state to the JSON line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what rank 0's timed path returned in its last step (t1..t6 "
+                         "predictions of its resident members) as DIR/<name>.npy, %d MB at most in all (a seeded sample "
+                         "of each larger array)" % (DUMP_BUDGET // 10 ** 6))
     ap.add_argument("--share-gpu", action="store_true",
                     help="TEST ONLY: all ranks on GPU 0 with the gloo backend (exercises the N>1 path on a 1-GPU box; "
                          "the numbers mean nothing)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # Stand-alone multi-GPU run: become the launcher.  Nothing in this process has touched HIP (torch is not even
@@ -420,6 +459,7 @@ def main():
 
     digests = {}
     relay_info = {}
+    last_outputs = {}       # --dump-outputs: what the headline leg's last timed step returned on this rank
 
     def digest(first_unit, x):
         """(sum, L2 norm) in float64 of every trajectory's final state: what `--digests` prints, so that runs with different
@@ -428,8 +468,9 @@ def main():
             v = x[r].double()
             digests[first_unit + r] = [float(v.sum()), float(v.norm())]
 
-    def timed_leg(ic_index, first_unit, B):
-        """W warm-up + K timed sampling passes of this rank's B trajectories; returns the max-over-ranks seconds."""
+    def timed_leg(ic_index, first_unit, B, capture=None):
+        """W warm-up + K timed sampling passes of this rank's B trajectories; returns the max-over-ranks seconds.  `capture`
+        (a dict) receives the outputs of the last timed pass."""
         exp.set_batch_offset(first_unit)
         if B > 0:
             x, forc = synthetic_state(ic_index, B, device)
@@ -438,9 +479,9 @@ def main():
                 x = one_pass(exp, x, forc)
         barrier()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
+        for s in range(args.steps):
             if B > 0:
-                x = one_pass(exp, x, forc)
+                x = one_pass(exp, x, forc, capture if s == args.steps - 1 else None)
         barrier()
         dt = time.perf_counter() - t0
         if world > 1:
@@ -453,12 +494,12 @@ def main():
                 digest(first_unit, x)
         return dt
 
-    def relay_leg(M):
+    def relay_leg(M, capture=None):
         """Strong scaling with the remainder members RELAYED (ensemble.relay_plan): every rank keeps M // world resident
         members; the M % world others advance as batches of one, each rank hosting a slice of the timed windows and handing
         the state to the next (torch.distributed send / recv: the only data-path message, 16 MB per hand-over).  Every pass
         sets the trajectory offset and the dropout call counters of its (trajectory, window), so the samples are those of
-        the one-GPU job."""
+        the one-GPU job.  `capture` (a dict) receives the outputs of the resident members' last timed pass."""
         plan = ensemble.relay_plan(M, world, args.steps, rank)
         q = plan.count
         x1, forc1 = synthetic_state(0, 1, device)
@@ -467,10 +508,10 @@ def main():
         one_pass(exp, x1, forc1)                       # B = 1 warm-up (workspace, kernels); also: calls per pass
         per_pass = tuple(b - a for a, b in zip(c0, exp.dropout_calls()))
 
-        def run(x, forc, first_unit, w_abs):
+        def run(x, forc, first_unit, w_abs, outputs=None):
             exp.set_batch_offset(first_unit)
             exp.set_dropout_calls((per_pass[0] * w_abs, per_pass[1] * w_abs))
-            return one_pass(exp, x, forc)
+            return one_pass(exp, x, forc, outputs)
 
         for w in range(args.warmup):
             if q:
@@ -483,7 +524,7 @@ def main():
         state = {"res": xr}
 
         def resident_step(w):
-            state["res"] = run(state["res"], forc_r, plan.start, args.warmup + w)
+            state["res"] = run(state["res"], forc_r, plan.start, args.warmup + w, capture if w == args.steps - 1 else None)
 
         def relay_step(task, w, x):
             return run(x, forc1, task.unit, args.warmup + w)
@@ -519,13 +560,14 @@ def main():
     parts = ensemble.partition(M, world)                   # strong: members of ONE initial condition over the ranks
     relay = world > 1 and M % world != 0 and M >= world and not args.no_relay
     legs = {}
+    capture = last_outputs if args.dump_outputs and rank == 0 else None
     if args.scaling == "strong":
         start, cnt = parts[rank]
-        legs["strong"] = (relay_leg(M) if relay else timed_leg(0, start, cnt), M)
+        legs["strong"] = (relay_leg(M, capture) if relay else timed_leg(0, start, cnt, capture), M)
         if world > 1 and not args.no_extras:
             legs["weak"] = (timed_leg(rank, rank * M, M), world * M)
     else:
-        legs["weak"] = (timed_leg(rank, rank * M, M), world * M)
+        legs["weak"] = (timed_leg(rank, rank * M, M, capture), world * M)
     dt, n_traj = legs[args.scaling]
     value = n_traj * HORIZON * args.steps / dt
     all_digests = None
@@ -584,6 +626,9 @@ def main():
         res["c5_extrapolation"] = {"trajectories": 100, "steps": 14600, "measured_steps": HORIZON * args.steps,
                                    "hours_at_this_rate": round(100 * 14600 / value / 3600.0, 2), "n_gpus": world,
                                    "note": "extrapolated from the measured rate; run --steps >= 100 for a 600-step sample"}
+        if args.dump_outputs:
+            res["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dump_outputs(last_outputs, args.dump_outputs)}
+            last_outputs.clear()
         if all_digests is not None:
             res["trajectory_digests"] = dict(sorted(all_digests.items(), key=lambda kv: int(kv[0])))
 

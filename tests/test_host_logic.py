@@ -383,19 +383,20 @@ def test_packaged_statistics_hold_the_reference_scalars(sdy, tmp_path):
     st = sdy.MultiStepStepper.from_statistics(None, _FV3GFS_STATE + _FV3GFS_FORCING, _FV3GFS_STATE)
     assert sorted(st.forcing_names) == sorted(_FV3GFS_FORCING) and st.in_names == _FV3GFS_STATE
     assert st.means["HGTsfc"] == known_mean["HGTsfc"] and st.stds["HGTsfc"] == known_std["HGTsfc"]
-    # where the reference's files and a libhdf5 are at hand (the build container), the converter reproduces the shipped JSON
-    src = "/root/reference/data_statistics"
-    if os.path.exists(src):
-        import importlib.util
-        spec = importlib.util.spec_from_file_location(
-            "convert_statistics", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools", "convert_statistics.py"))
-        conv = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(conv)
+    # where a libhdf5 is at hand, the converter reproduces the shipped JSON from the reference's own files (stored unchanged
+    # under tests/golden/data_statistics)
+    import importlib.util
+    spec = importlib.util.spec_from_file_location(
+        "convert_statistics", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools", "convert_statistics.py"))
+    conv = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(conv)
+    src = os.path.join(gu.GOLDEN, "data_statistics")
+    for stem, shipped in (("scaling", stds), ("centering", means)):
         try:
-            fresh = conv.read_scalars(os.path.join(src, "scaling.nc"))
+            fresh = conv.read_scalars(os.path.join(src, stem + ".nc"))
         except SystemExit:
             return
-        assert {k: v for k, v in fresh.items() if v == v} == {k: v for k, v in stds.items() if v == v}
+        assert {k: v for k, v in fresh.items() if v == v} == {k: v for k, v in shipped.items() if v == v}, stem
 
 
 def test_inference_log_plumbing_follows_the_reference(sdy):
@@ -454,3 +455,34 @@ def test_bench_reads_the_counter_traffic_of_the_newest_profile():
     # the per-launch work of a stage scales with the rows its launches covered (drop-path skip)
     w25, w20 = bench.stage_work(25)["mlp fused (dropout)"], bench.stage_work(20)["mlp fused (dropout)"]
     assert abs(w20[0] / w25[0] - 0.8) < 1e-12 and abs(w20[1] / w25[1] - 0.8) < 1e-12
+
+
+def test_bench_dump_outputs_fit_the_budget_and_repeat(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs`: float32 (float64 kept) .npy files within DUMP_BUDGET; an array over its share becomes a
+    seeded sample of its elements -- the same positions on every run, so dumps of two builds compare element by element."""
+    import os
+    import sys
+
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 1 << 20)
+    g = torch.Generator().manual_seed(5)
+    outs = {"t1_preds_normed": torch.randn(3, 7, 90, 180, generator=g), "t2_preds_normed": torch.randn(3, 7, 90, 180, generator=g),
+            "small": torch.randn(2, 3, generator=g, dtype=torch.float64), "half": torch.randn(4, 5, generator=g).half()}
+    info = bench.dump_outputs(outs, str(tmp_path / "a"))
+    bench.dump_outputs({k: v.clone() for k, v in outs.items()}, str(tmp_path / "b"))
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(k + ".npy" for k in outs) and set(info) == set(outs)
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= bench.DUMP_BUDGET
+    for k, v in outs.items():
+        a, b = np.load(tmp_path / "a" / (k + ".npy")), np.load(tmp_path / "b" / (k + ".npy"))
+        assert a.dtype == (np.float64 if v.dtype == torch.float64 else np.float32) and np.array_equal(a, b)
+        assert info[k]["shape"] == list(v.shape)
+        if info[k]["elements"] == "all":
+            assert a.shape == tuple(v.shape) and np.array_equal(a, v.numpy().astype(a.dtype))
+        else:                                   # every sampled value is one of the array's, in flattened order
+            flat = v.reshape(-1).numpy()
+            assert a.ndim == 1 and 0 < a.size < flat.size and np.isin(a, flat).all()
+    assert info["small"]["elements"] == info["half"]["elements"] == "all"
+    assert info["t1_preds_normed"]["elements"] != "all"
