@@ -32,6 +32,15 @@
  *     drop path       : c0 = b_global, c1 = 0xFFFFFFFF, stream = 0x1000 + layer, word 0;
  *                       keep <=> word >= floor(p * 2^32)
  *   kept values are scaled by 1/(1-p).
+ *
+ * Forward-conditioning noise stream (the eps of DYffusion's "data+noise-v1/v2", src/diffusion/dyffusion.py:321-330, where the
+ * reference draws torch.randn_like): same generator and key, one call per 4 consecutive pixels of one (trajectory, channel):
+ *     counter = (q, b_global*C + c, 0x2000, call)   q = pixel / 4 (pixel = h*nlon + w), C = channels of the group,
+ *                                                   c < C its channel, call = the network's call number of the row
+ *     u(word) = ((word >> 8) + 1) * 2^-24 in (0, 1];  Box-Muller on the call's words (w0, w1) and (w2, w3):
+ *     eps[4q + 0], eps[4q + 1] = r0 cos(2 pi u(w1)), r0 sin(2 pi u(w1))    r0 = sqrt(-2 ln u(w0))
+ *     eps[4q + 2], eps[4q + 3] = r1 cos(2 pi u(w3)), r1 sin(2 pi u(w3))    r1 = sqrt(-2 ln u(w2))
+ *   stream word 0x2000 is outside every stream word of the dropout stream (< 64 and 0x1000 + layer, layer < 32).
  */
 #ifndef SDY_AMD_H
 #define SDY_AMD_H
@@ -336,6 +345,18 @@ typedef struct sdy_sfno_fwd_args {
                               rows, and row b of the forward reads input row b % n (the two interpolations of a cold-sampling
                               step as ONE forward of 2n rows: same (x_0, forecast) and static condition, other time and dropout
                               call).  The encoder then runs on n rows; results are bit-identical to stacking copies. */
+  /* One GENERATED channel group (DYffusion forward conditioning, src/diffusion/dyffusion.py:310-353): it holds
+   *   a_b * gen_src[b, c, p] + s_b * eps(seed, call(b), batch_offset + b % n, c, p)     (n = rows_per_call or B,
+   *   call(b) = call + b / n; eps: the forward-conditioning noise stream above), both products rounded before the sum.
+   * The group sits in front of the gen_pos-th PRESENT `in` group (0 = first, number of present groups = last); the channel
+   * total including gen_chans must be in_chans.  s_b == 0 copies a_b * x and draws nothing ("data" with a_b = 1).
+   * Zeroed fields (gen_src NULL): no generated group, the concat of earlier revisions.  Its values change with every call, so
+   * reuse_encoder / shared_inputs with a generated group are SDY_ERR_ARG. */
+  const float* gen_src;    /* dev (B, gen_chans, nlat, nlon) or NULL */
+  int gen_chans;
+  int gen_pos;
+  const float* gen_coef;   /* dev [B][2]: (a_b, s_b) */
+  const float* gen_noise;  /* optional injected eps (tests), dev (B, gen_chans, nlat, nlon), or NULL: the Philox draw */
 } sdy_sfno_fwd_args;
 int sdy_sfno_forward(sdy_sfno* net, const sdy_sfno_fwd_args* args, void* stream);
 
@@ -464,6 +485,11 @@ int sdy_range_headroom(float* max_staged5, int reset, void* stream);
 int sdy_dropout_stream_rounds(void);
 int sdy_dropout_stream_words(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t key_lo, uint32_t key_hi,
                              uint32_t* out4);
+/* The forward-conditioning noise stream (above) written out: out dev (B, C, HW) receives eps of row b = trajectory
+ * batch_offset + b % n, call + b / n (n = rows_per_call, 0 means B), channel c, pixel p -- what sdy_sfno_forward draws for a
+ * generated group of C channels.  HW % 4 == 0. */
+int sdy_cond_noise_fill(uint64_t seed, uint32_t call, uint32_t batch_offset, int rows_per_call, int B, int C, int HW, float* out,
+                        void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * Measurement.  While enabled, every kernel launch of sdy_sfno_forward is bracketed by a pair of

@@ -134,6 +134,8 @@ class SdySfnoFwdArgs(C.Structure):
         ("ws", C.c_void_p), ("ws_floats", C.c_size_t),
         ("reuse_encoder", C.c_int),
         ("shared_inputs", C.c_int),
+        ("gen_src", C.c_void_p), ("gen_chans", C.c_int), ("gen_pos", C.c_int),
+        ("gen_coef", C.c_void_p), ("gen_noise", C.c_void_p),
     ]
 
 
@@ -215,6 +217,8 @@ SIGNATURES = {
     "sdy_dropout_stream_rounds": (C.c_int, []),
     "sdy_dropout_stream_words": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                            C.POINTER(C.c_uint32)]),
+    "sdy_cond_noise_fill": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                      C.c_void_p]),
     "sdy_ensemble_series": (C.c_int, [C.c_void_p, C.c_int, C.c_long, C.c_long, C.c_void_p, C.c_long, C.c_void_p, C.c_int,
                                      C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "sdy_profile_enable": (C.c_int, [C.c_int]),

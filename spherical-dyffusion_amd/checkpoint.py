@@ -126,6 +126,16 @@ def resolve_interpolator_state(state: Mapping[str, Any], interpolator_state: Opt
                      f"(interpolator_run_id={dc.get('interpolator_run_id')!r} needs wandb access, which this path does not have)")
 
 
+def forward_conditioning_channels(diffusion_config: Mapping[str, Any], window: int, n_in: int) -> int:
+    """Input channels DYffusion's forward conditioning adds to the forecaster (`_base_experiment.num_conditional_channels`,
+    src/experiment_types/_base_experiment.py:207-225): none for a missing key or "none", window * n_in otherwise."""
+    mode = diffusion_config.get("forward_conditioning", "")
+    mode = "none" if mode is None else str(mode).lower()
+    if mode in ("", "none"):
+        return 0
+    return (2 if mode == "data|noise" else 1) * int(window) * int(n_in)
+
+
 def module_from_state(state: Mapping[str, Any], interpolator_state: Optional[Mapping[str, Any]], spatial_shape: Tuple[int, int],
                       use_ema: Optional[bool] = None, interpolator_use_ema: Optional[bool] = None,
                       device="cuda", **net_kwargs) -> MultiHorizonForecastingDYffusion:
@@ -138,9 +148,11 @@ def module_from_state(state: Mapping[str, Any], interpolator_state: Optional[Map
     n_in, n_out, n_cond = len(in_names), len(out_names), len(forcing)
     horizon = int(dm.get("horizon", dc.get("timesteps", 6)))
     fw, iw = module_weights(state, interpolator_state, use_ema, interpolator_use_ema)
+    # the forecaster's conditional channels grow by the forward-conditioning group (x_0 of the window, dyffusion.py:310-353)
+    n_cond_f = n_cond + forward_conditioning_channels(dc, int(dm.get("window", 1) or 1), n_in)
     # the interpolator sees (x_0, x_h) stacked on the channel axis (interpolation.py: window + 1 snapshot)
     with torch.cuda.device(device):
-        fnet = _build_net(_plain(hp["model_config"]), n_in, n_out, n_cond, spatial_shape, fw, **net_kwargs)
+        fnet = _build_net(_plain(hp["model_config"]), n_in, n_out, n_cond_f, spatial_shape, fw, **net_kwargs)
         inet = _build_net(_plain(ihp["model_config"]), 2 * n_in, n_out, n_cond, spatial_shape, iw, **net_kwargs)
     ipol = InterpolationExperiment(inet, horizon=horizon,
                                    enable_inference_dropout=bool(ihp.get("enable_inference_dropout", True)))

@@ -573,6 +573,11 @@ extern "C" int sdy_concat_channels(const float* const* src, const int* chans, in
   return sdy_concat_launch(src, chans, nsrc, out, total * HW, B, HW, (hipStream_t)stream);
 }
 
+extern "C" int sdy_cond_noise_fill(uint64_t seed, uint32_t call, uint32_t batch_offset, int rows_per_call, int B, int C, int HW,
+                                   float* out, void* stream) {
+  return sdy_cond_noise_launch(seed, call, batch_offset, rows_per_call, B, C, HW, out, (hipStream_t)stream);
+}
+
 // =========================================================================================================
 // SFNO network object
 // =========================================================================================================
@@ -1184,11 +1189,19 @@ extern "C" int sdy_sfno_forward(sdy_sfno* n, const sdy_sfno_fwd_args* a, void* s
 
   // ---- input concat (BaseModel.concat_condition_if_needed, _base_model.py:166-192) into the tail of the big-skip
   //      buffer: cat = [ block output (E) | inputs (Cin) ]  (sfnonet.py:804-805,831-832)
-  const float* srcs[3];
-  int chans[3];
+  const float* srcs[4];
+  int chans[4];
   int ns = 0, ctot = 0;
   for (int i = 0; i < 3; ++i)
     if (a->in[i] && a->in_chans[i] > 0) { srcs[ns] = a->in[i]; chans[ns] = a->in_chans[i]; ctot += a->in_chans[i]; ++ns; }
+  // the generated group (forward conditioning) joins the list at its position
+  const bool gen = a->gen_src != nullptr;
+  if (gen) {
+    if (a->gen_chans <= 0 || !a->gen_coef || a->gen_pos < 0 || a->gen_pos > ns) return SDY_ERR_ARG;
+    if (a->reuse_encoder || a->shared_inputs) return SDY_ERR_ARG;     // its values change with every call
+    for (int i = ns; i > a->gen_pos; --i) { srcs[i] = srcs[i - 1]; chans[i] = chans[i - 1]; }
+    srcs[a->gen_pos] = a->gen_src; chans[a->gen_pos] = a->gen_chans; ctot += a->gen_chans; ++ns;
+  }
   if (ns == 0 || ctot != Cin) return SDY_ERR_SHAPE;
   const long cat_bs = (long)n->catC * HW;
   float* cat_in = cat + (size_t)(n->catC - Cin) * HW;
@@ -1202,7 +1215,14 @@ extern "C" int sdy_sfno_forward(sdy_sfno* n, const sdy_sfno_fwd_args* a, void* s
   const bool shared = a->shared_inputs != 0;
   if (shared && (reuse || rpc >= B)) return SDY_ERR_ARG;
   // (reuse_encoder: the inputs already sit in the tail of `cat` -- no block writes there -- and the encoder output in xe)
-  if (!reuse) SDY_STAGE(ST_CONCAT, sdy_concat_launch(srcs, chans, ns, cat_in, cat_bs, B, HW, stream, shared ? rpc : 0));
+  if (gen) {
+    SdyConcatGen g;
+    g.gen = a->gen_pos; g.coef = a->gen_coef; g.noise = a->gen_noise;
+    g.seed = a->seed; g.call = a->call; g.batch_offset = a->batch_offset; g.rows_per_call = rpc;
+    SDY_STAGE(ST_CONCAT, sdy_concat_gen_launch(srcs, chans, ns, g, cat_in, cat_bs, B, HW, stream));
+  } else if (!reuse) {
+    SDY_STAGE(ST_CONCAT, sdy_concat_launch(srcs, chans, ns, cat_in, cat_bs, B, HW, stream, shared ? rpc : 0));
+  }
   const bool enc_once = shared && n->enc.w && n->plan_data != n->plan_lg && plan_tiled_ok(n->plan_data, E, spec_ilv(c));
   const int Be = enc_once ? rpc : B;                               // rows the encoder computes
 

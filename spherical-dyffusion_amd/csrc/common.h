@@ -338,6 +338,26 @@ static inline uint32_t sdy_drop_threshold(float p) {
   return (uint32_t)t;
 }
 
+// ---- forward-conditioning noise (DYffusion "data+noise-v1/v2", include/sdy_amd.h) ------------------------------------------
+// One Philox call per 4 consecutive pixels 4q .. 4q+3 of one (trajectory, channel) plane: counter (q, traj * C + c,
+// SDY_NOISE_STREAM, call), the words (x, y) and (z, w) become two Box-Muller pairs.  The stream word is outside every range
+// the dropout stream uses (2 * layer + kind < 64, drop path 0x1000 + layer with layer < 32).
+#define SDY_NOISE_STREAM 0x2000u
+// 24 random bits -> (0, 1], exact in fp32: the log never sees 0
+__device__ __forceinline__ float sdy_u01_open0(uint32_t w) { return (float)((w >> 8) + 1u) * 5.9604644775390625e-08f; }
+__device__ __forceinline__ f32x4 sdy_cond_noise4(uint32_t q, uint32_t traj, uint32_t C, uint32_t c, uint32_t call,
+                                                 uint32_t seed_lo, uint32_t seed_hi) {
+  const philox4 w = philox4x32(q, traj * C + c, SDY_NOISE_STREAM, call, seed_lo, seed_hi);
+  const float r0 = sqrtf(-2.0f * logf(sdy_u01_open0(w.x)));
+  const float r1 = sqrtf(-2.0f * logf(sdy_u01_open0(w.z)));
+  float s0, c0, s1, c1;
+  sincospif(2.0f * sdy_u01_open0(w.y), &s0, &c0);   // (2u: exact; sincospi keeps the angle's reduction exact too)
+  sincospif(2.0f * sdy_u01_open0(w.w), &s1, &c1);
+  f32x4 e;
+  e.x = r0 * c0; e.y = r0 * s0; e.z = r1 * c1; e.w = r1 * s1;
+  return e;
+}
+
 // ---- GEMM launcher (gemm.hip) --------------------------------------------------------------------------
 enum { SDY_TRI_NONE = 0, SDY_TRI_LEG_FWD = 1, SDY_TRI_LEG_INV = 2, SDY_TRI_DHCONV = 3 };
 enum { SDY_TILE_128x128 = 0, SDY_TILE_64x128 = 1 };

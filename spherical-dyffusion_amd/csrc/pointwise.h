@@ -22,6 +22,22 @@ int sdy_instnorm_coeffs_launch(const float* x, int B, int C, int HW, const float
                                const float* ss, long ss_stride, float eps, float* a, float* d, hipStream_t stream);
 int sdy_concat_launch(const float* const* src, const int* chans, int nsrc, float* out, long out_bstride, int B, int HW,
                       hipStream_t stream, int src_rows = 0);   // src_rows > 0: output row b reads source row b % src_rows
+// The concat with one GENERATED group (DYffusion forward conditioning, sdy_sfno_fwd_args.gen_*): group `gen` of src/chans holds
+// a_b * src[b, c, p] + s_b * eps(seed, call + b / rows_per_call, batch_offset + b % rows_per_call, c, p), coef = dev [B][2] (a, s);
+// s_b == 0 draws nothing; `noise` (dev (B, chans[gen], HW) or null) replaces the draw (tests).  Copied groups read row b.
+struct SdyConcatGen {
+  int gen;
+  const float* coef;
+  const float* noise;
+  uint64_t seed;
+  uint32_t call, batch_offset;
+  int rows_per_call;
+};
+int sdy_concat_gen_launch(const float* const* src, const int* chans, int nsrc, const SdyConcatGen& g, float* out,
+                          long out_bstride, int B, int HW, hipStream_t stream);
+// raw eps of the same stream, out dev (B, C, HW)
+int sdy_cond_noise_launch(uint64_t seed, uint32_t call, uint32_t batch_offset, int rows_per_call, int B, int C, int HW, float* out,
+                          hipStream_t stream);
 int sdy_cold_update_launch(const float* xs, const float* xn, const float* xi, float* out, size_t n, hipStream_t stream);
 // scratch: dev, B * T floats (2 B T when trep is NULL) -- the hidden layer between the launches
 int sdy_time_mlp_launch(const SdyTimeMlp& t, const float* time, int B, float* trep, float* ss, float* dp,

@@ -257,6 +257,70 @@ __global__ __launch_bounds__(256) void concat_kernel(const ConcatArgs a, float* 
   dst[i] = src[i];
 }
 
+// The same concat with group `g.gen` generated (pointwise.h SdyConcatGen).  A separate kernel: the plain concat stays as it was.
+// One float4 per thread = the 4 pixels of one Philox call.  a * x + s * eps rounds both products before the sum, as the
+// reference's torch expression `f * x0 + (1 - f) * randn` does.
+struct ConcatGenArgs {
+  ConcatArgs cat;
+  int gen;
+  const float* coef;
+  const float* noise;
+  uint32_t seed_lo, seed_hi, call, batch_offset;
+  int rows_per_call;
+};
+__global__ __launch_bounds__(256) void concat_gen_kernel(const ConcatGenArgs g, float* __restrict__ out, long out_bstride,
+                                                          int HW4) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= HW4) return;
+  int c = blockIdx.y;
+  const int b = blockIdx.z;
+  int s = 0, coff = 0;
+  while (s < g.cat.nsrc - 1 && c >= g.cat.chans[s]) {
+    c -= g.cat.chans[s];
+    coff += g.cat.chans[s];
+    ++s;
+  }
+  const int C = g.cat.chans[s];
+  const long plane = ((long)b * C + c) * HW4 * 4;
+  const f32x4 x = reinterpret_cast<const f32x4*>(g.cat.src[s] + plane)[i];
+  f32x4* dst = reinterpret_cast<f32x4*>(out + (long)b * out_bstride + (long)(coff + c) * HW4 * 4);
+  if (s != g.gen) {
+    dst[i] = x;
+    return;
+  }
+  const float a = g.coef[2 * b], sc = g.coef[2 * b + 1];
+  f32x4 v;
+  if (sc == 0.0f) {   // "data": a plain (scaled) copy, no Philox work
+    v.x = __fmul_rn(a, x.x); v.y = __fmul_rn(a, x.y); v.z = __fmul_rn(a, x.z); v.w = __fmul_rn(a, x.w);
+  } else {
+    f32x4 e;
+    if (g.noise) {
+      e = reinterpret_cast<const f32x4*>(g.noise + plane)[i];
+    } else {
+      const int bq = b / g.rows_per_call;
+      e = sdy_cond_noise4((uint32_t)i, (uint32_t)(b - bq * g.rows_per_call) + g.batch_offset, (uint32_t)C, (uint32_t)c,
+                          g.call + (uint32_t)bq, g.seed_lo, g.seed_hi);
+    }
+    v.x = __fadd_rn(__fmul_rn(a, x.x), __fmul_rn(sc, e.x));
+    v.y = __fadd_rn(__fmul_rn(a, x.y), __fmul_rn(sc, e.y));
+    v.z = __fadd_rn(__fmul_rn(a, x.z), __fmul_rn(sc, e.z));
+    v.w = __fadd_rn(__fmul_rn(a, x.w), __fmul_rn(sc, e.w));
+  }
+  dst[i] = v;
+}
+
+// raw eps (sdy_cond_noise_fill): out (B, C, HW)
+__global__ __launch_bounds__(256) void cond_noise_kernel(float* __restrict__ out, int HW4, uint32_t seed_lo, uint32_t seed_hi,
+                                                          uint32_t call, uint32_t batch_offset, int rows_per_call) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= HW4) return;
+  const int c = blockIdx.y, C = gridDim.y, b = blockIdx.z;
+  const int bq = b / rows_per_call;
+  reinterpret_cast<f32x4*>(out + ((long)b * C + c) * HW4 * 4)[i] =
+      sdy_cond_noise4((uint32_t)i, (uint32_t)(b - bq * rows_per_call) + batch_offset, (uint32_t)C, (uint32_t)c,
+                      call + (uint32_t)bq, seed_lo, seed_hi);
+}
+
 // ---- cold-sampling update: out = x_s + (x_ip_next - x_ip_s)   (src/diffusion/dyffusion.py:517-519) -------
 __global__ __launch_bounds__(256) void cold_update_kernel(const float* __restrict__ xs, const float* __restrict__ xn,
                                                            const float* __restrict__ xi, float* __restrict__ out,
@@ -958,6 +1022,45 @@ int sdy_concat_launch(const float* const* src, const int* chans, int nsrc, float
   a.nsrc = nsrc;
   const int HW4 = HW / 4;
   hipLaunchKernelGGL(concat_kernel, dim3((HW4 + 255) / 256, total, B), dim3(256), 0, stream, a, out, out_bstride, HW4, src_rows);
+  return sdy_launch_status();
+}
+
+int sdy_concat_gen_launch(const float* const* src, const int* chans, int nsrc, const SdyConcatGen& gen, float* out,
+                          long out_bstride, int B, int HW, hipStream_t stream) {
+  if (!src || !chans || !out || nsrc < 1 || nsrc > 4 || B <= 0 || HW <= 0) return SDY_ERR_ARG;
+  if (gen.gen < 0 || gen.gen >= nsrc || !gen.coef || gen.rows_per_call <= 0 || B % gen.rows_per_call) return SDY_ERR_ARG;
+  if (HW & 3) return SDY_ERR_ALIGN;
+  ConcatGenArgs g;
+  int total = 0;
+  for (int i = 0; i < 4; ++i) {
+    g.cat.src[i] = i < nsrc ? src[i] : nullptr;
+    g.cat.chans[i] = i < nsrc ? chans[i] : 0;
+    if (i < nsrc) {
+      if (!src[i] || chans[i] <= 0) return SDY_ERR_ARG;
+      total += chans[i];
+    }
+  }
+  if ((long)gen.batch_offset + gen.rows_per_call > 0xFFFFFFFFL / chans[gen.gen])
+    return SDY_ERR_ARG;   // counter word c1 = trajectory * C + c must not wrap
+  g.cat.nsrc = nsrc;
+  g.gen = gen.gen; g.coef = gen.coef; g.noise = gen.noise;
+  g.seed_lo = (uint32_t)(gen.seed & 0xFFFFFFFFu); g.seed_hi = (uint32_t)(gen.seed >> 32);
+  g.call = gen.call; g.batch_offset = gen.batch_offset; g.rows_per_call = gen.rows_per_call;
+  const int HW4 = HW / 4;
+  hipLaunchKernelGGL(concat_gen_kernel, dim3((HW4 + 255) / 256, total, B), dim3(256), 0, stream, g, out, out_bstride, HW4);
+  return sdy_launch_status();
+}
+
+int sdy_cond_noise_launch(uint64_t seed, uint32_t call, uint32_t batch_offset, int rows_per_call, int B, int C, int HW, float* out,
+                          hipStream_t stream) {
+  if (!out || B <= 0 || C <= 0 || HW <= 0 || rows_per_call < 0 || (rows_per_call > 0 && B % rows_per_call)) return SDY_ERR_ARG;
+  if (HW & 3) return SDY_ERR_ALIGN;
+  const int rpc = rows_per_call > 0 ? rows_per_call : B;
+  if ((long)batch_offset + rpc > 0xFFFFFFFFL / C) return SDY_ERR_ARG;
+  if (C > 65535 || B > 65535) return SDY_ERR_ARG;   // grid y / z extents
+  const int HW4 = HW / 4;
+  hipLaunchKernelGGL(cond_noise_kernel, dim3((HW4 + 255) / 256, C, B), dim3(256), 0, stream, out, HW4,
+                     (uint32_t)(seed & 0xFFFFFFFFu), (uint32_t)(seed >> 32), call, batch_offset, rpc);
   return sdy_launch_status();
 }
 

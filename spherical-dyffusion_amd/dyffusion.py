@@ -16,10 +16,14 @@ from __future__ import annotations
 from types import SimpleNamespace
 from typing import Any, Dict, List, Optional, Sequence, Union
 
+import numpy as np
 import torch
 from torch import Tensor
 
 from . import ops
+
+# forward conditioning of the forecaster (reference dyffusion.py:59-60, :310-330)
+FORWARD_CONDITIONING = ("data", "none", "data+noise-v1", "data+noise-v2")
 
 
 class DYffusion(torch.nn.Module):
@@ -53,8 +57,9 @@ class DYffusion(torch.nn.Module):
         super().__init__()
         if schedule != "before_t1_only":
             raise NotImplementedError(f"schedule={schedule!r}: only 'before_t1_only' (the shipped config) is in scope")
-        if forward_conditioning != "none":
-            raise NotImplementedError(f"forward_conditioning={forward_conditioning!r}: only 'none' is in scope")
+        if forward_conditioning not in FORWARD_CONDITIONING:
+            raise ValueError(f"Invalid value for forward_conditioning: {forward_conditioning!r}, "
+                             f"must be one of {list(FORWARD_CONDITIONING)}")
         if time_encoding not in ("dynamics", "discrete"):
             raise ValueError(f"Invalid time_encoding: {time_encoding}")
         if enable_interpolator_dropout not in [True, False, "always", "except_dynamical_steps"]:
@@ -295,9 +300,27 @@ class DYffusion(torch.nn.Module):
             out = ops.concat_channels([two(x_end[:, :1]), out])
         return out[:B], out[B:]
 
+    def forward_condition_coefs(self, t):
+        """(a, s) of the forecaster's generated input group a * x_0 + s * eps at diffusion step `t` (dyffusion.py:310-330), or
+        None for "none".  f = t / (num_timesteps - 1) with the artificial steps counted, in fp32 like the reference's tensor
+        arithmetic; "data" is (1, 0), which copies x_0 and draws nothing."""
+        mode = self.hparams.forward_conditioning
+        if mode == "none":
+            return None
+        if mode == "data":
+            return 1.0, 0.0
+        f = np.float32(t) / np.float32(self.num_timesteps - 1)
+        g = np.float32(1.0) - f
+        return (float(f), float(g)) if mode == "data+noise-v1" else (float(g), float(f))
+
     def predict_x_last(self, initial_condition: Tensor, x_t: Tensor, t, **kwargs) -> Tensor:
-        """Forecaster call (dyffusion.py:286-355); `t` is a host scalar diffusion step."""
+        """Forecaster call (dyffusion.py:286-355); `t` is a host scalar diffusion step.  With forward conditioning the
+        network sees [x_t | a x_0 + s eps | dynamical condition | static condition]: the middle group is generated inside the
+        network's input concat (eps: the library's noise stream of this call and trajectory, no torch RNG)."""
         assert 0 <= t <= self.num_timesteps - 1, f"Invalid timestep: {t}. {self.num_timesteps=}"
+        coefs = self.forward_condition_coefs(t)
+        if coefs is not None:
+            kwargs["forward_condition"] = (initial_condition,) + coefs
         dyn = kwargs.pop("dynamical_condition", None)
         cond = None
         if dyn is not None:

@@ -117,6 +117,7 @@ class SphericalFourierNeuralOperatorNet(nn.Module):
         self.batch_offset = 0           # global index of the first trajectory this rank owns
         self._call = 0                  # advances the dropout stream on every forward
         self.mask_injector = None       # tests: callable(call_index) -> (keep_masks, drop_path_keep) replacing Philox
+        self.noise_injector = None      # tests: callable(call_index) -> eps of the forward condition's noise, replacing Philox
         self.supports_shared_inputs = True     # forward(shared_inputs=True): stacked calls that share their input rows
 
         E, T, H, Cin, L = embed_dim, self.time_dim, self.mlp_hidden, self.in_chans, self.modes_lat
@@ -330,7 +331,7 @@ class SphericalFourierNeuralOperatorNet(nn.Module):
     # ---- forward ------------------------------------------------------------------------------------------------
     def forward(self, inputs, time=None, condition=None, static_condition=None, return_time_emb: bool = False,
                 keep_masks=None, drop_path_keep=None, rows_per_call: Optional[int] = None, reuse_encoder: bool = False,
-                shared_inputs: bool = False, **kwargs):
+                shared_inputs: bool = False, forward_condition=None, **kwargs):
         """`reuse_encoder=True`: the caller guarantees that `inputs` / `condition` / `static_condition` hold the same values
         as in the previous forward of this network (same batch): the input concat and the encoder are skipped and the
         forward restarts from the stored encoder output -- bit-identical results; `time` and the dropout call number may
@@ -341,19 +342,28 @@ class SphericalFourierNeuralOperatorNet(nn.Module):
         sampling step share their inputs, reference dyffusion.py:497,515.)
         `shared_inputs=True` (with `rows_per_call=n`): the stacked calls share their inputs -- `inputs` / `condition` /
         `static_condition` hold n rows, `time` one value per row of the stacked batch (B = len(time)), and row b reads input
-        row b % n: no stacked copy of the inputs is made and the encoder runs once (bit-identical to stacking copies)."""
+        row b % n: no stacked copy of the inputs is made and the encoder runs once (bit-identical to stacking copies).
+        `forward_condition=(x0, a, s)`: DYffusion's forward conditioning (reference dyffusion.py:310-353), a channel group
+        GENERATED inside the input concat in front of `condition`: row b holds a_b * x0[b] + s_b * eps with eps the library's
+        standard-normal stream of (seed, call, trajectory) (include/sdy_amd.h); `a`, `s` are floats or one value per row,
+        s = 0 draws nothing.  The inputs become [inputs | generated | condition | static_condition]."""
         if return_time_emb:
             raise NotImplementedError("return_time_emb is a training-path feature")
         if not inputs.is_cuda:
             raise RuntimeError("sdy_amd SFNO runs on the GPU only (no CPU fallback); move inputs to cuda")
         dev = inputs.device
         # concat_condition_if_needed (_base_model.py:166-192): same checks, concat happens inside the native call
+        gen = None
+        if forward_condition is not None:
+            if reuse_encoder or shared_inputs:
+                raise ValueError("forward_condition changes with every call: no reuse_encoder / shared_inputs")
+            gen = self._forward_condition(forward_condition, inputs.shape[0], dev)
         if self.num_conditional_channels > 0:
-            if condition is None and static_condition is None:
+            if condition is None and static_condition is None and gen is None:
                 raise ValueError(f"condition and static_condition are both None but num_conditional_channels is "
                                  f"{self.num_conditional_channels}")
         else:
-            assert condition is None, "condition is not None but num_conditional_channels is 0"
+            assert condition is None and gen is None, "condition is not None but num_conditional_channels is 0"
             assert static_condition is None, "static_condition is not None but num_conditional_channels is 0"
         pieces = [t.to(torch.float32).contiguous() for t in (inputs, condition, static_condition) if t is not None]
         B = B_in = inputs.shape[0]
@@ -364,9 +374,10 @@ class SphericalFourierNeuralOperatorNet(nn.Module):
         nlat, nlon = self.img_shape
         for t in pieces:
             assert t.shape[0] == B_in and tuple(t.shape[-2:]) == (nlat, nlon), f"bad input shape {tuple(t.shape)}"
-        if sum(t.shape[1] for t in pieces) != self.in_chans:
+        n_gen = 0 if gen is None else gen[0].shape[1]
+        if sum(t.shape[1] for t in pieces) + n_gen != self.in_chans:
             raise RuntimeError(f"inputs.shape: {tuple(inputs.shape)}, expected {self.in_chans} channels in total, got "
-                               f"{[t.shape[1] for t in pieces]}")
+                               f"{[t.shape[1] for t in pieces[:1]] + ([n_gen] if gen else []) + [t.shape[1] for t in pieces[1:]]}")
         tt = None
         if self.with_time_emb:
             assert self.min_time is not None and self.max_time is not None, \
@@ -390,7 +401,8 @@ class SphericalFourierNeuralOperatorNet(nn.Module):
             # A larger batch runs as consecutive calls on near-equal row ranges; every row keeps its dropout stream (same call
             # number, batch_offset + first row of the range), so the result equals the single call's row for row.
             if rows_per_call not in (None, B) or shared_inputs or keep_masks is not None or drop_path_keep is not None or \
-                    (self.mask_injector is not None and self.inference_dropout):
+                    (self.mask_injector is not None and self.inference_dropout) or \
+                    (gen is not None and self.noise_injector is not None):
                 raise _lib.SdyError(f"batch {B} > {max_b} rows per native call cannot be split with stacked calls / injected masks")
             n_chunks = -(-B // max_b)
             step = -(-B // n_chunks)
@@ -398,7 +410,8 @@ class SphericalFourierNeuralOperatorNet(nn.Module):
             for r0 in range(0, B, step):       # the prepared pieces are sliced: no second pass through the checks above
                 r1 = min(B, r0 + step)
                 self._native_call(h, dev, [t[r0:r1] for t in pieces], None if tt is None else tt[r0:r1], out[r0:r1],
-                                  self._call, self.batch_offset + r0)
+                                  self._call, self.batch_offset + r0,
+                                  gen=None if gen is None else (gen[0][r0:r1], gen[1][r0:r1], None))
             self._call += 1                    # only once every chunk has been enqueued: a failed chunk leaves the counter alone
             return out
         out = torch.empty(B, self.out_chans, nlat, nlon, dtype=torch.float32, device=dev)
@@ -410,14 +423,35 @@ class SphericalFourierNeuralOperatorNet(nn.Module):
             n_calls = B // int(rows_per_call)
         if keep_masks is None and drop_path_keep is None and self.mask_injector is not None and self.inference_dropout:
             keep_masks, drop_path_keep = self.mask_injector(self._call)
+        if gen is not None and self.noise_injector is not None:
+            assert n_calls == 1, "injected noise addresses one call per forward"
+            eps = self.noise_injector(self._call)
+            if eps is not None:
+                eps = eps.to(dev, torch.float32).contiguous()
+                assert eps.shape == gen[0].shape, f"injected noise {tuple(eps.shape)} != {tuple(gen[0].shape)}"
+            gen = (gen[0], gen[1], eps)
         self._native_call(h, dev, pieces, tt, out, self._call, self.batch_offset, rows_per_call, keep_masks, drop_path_keep,
-                          reuse_encoder=bool(reuse_encoder), shared_inputs=bool(shared_inputs))
+                          reuse_encoder=bool(reuse_encoder), shared_inputs=bool(shared_inputs), gen=gen)
         self._call += n_calls
         return out
 
+    def _forward_condition(self, fc, B: int, dev):
+        """(x0, a, s) -> (x0 as fp32 contiguous, coef (B, 2) on the device, no injected noise)."""
+        x0, a, s = fc
+        x0 = x0.to(torch.float32).contiguous()
+        nlat, nlon = self.img_shape
+        assert x0.shape[0] == B and tuple(x0.shape[-2:]) == (nlat, nlon), f"bad forward_condition shape {tuple(x0.shape)}"
+
+        def col(v):
+            t = torch.as_tensor(v, dtype=torch.float32).reshape(-1).to(dev)
+            return t.expand(B) if t.numel() == 1 else t.reshape(B)
+        return x0, torch.stack([col(a), col(s)], dim=1).contiguous(), None
+
     def _native_call(self, h, dev, pieces, tt, out, call: int, batch_offset: int, rows_per_call: Optional[int] = None,
-                     keep_masks=None, drop_path_keep=None, reuse_encoder: bool = False, shared_inputs: bool = False) -> None:
-        """One sdy_sfno_forward on prepared (fp32, contiguous-per-row) inputs; `out` is a (B, out_chans, nlat, nlon) view."""
+                     keep_masks=None, drop_path_keep=None, reuse_encoder: bool = False, shared_inputs: bool = False,
+                     gen=None) -> None:
+        """One sdy_sfno_forward on prepared (fp32, contiguous-per-row) inputs; `out` is a (B, out_chans, nlat, nlon) view.
+        `gen`: (x0, coef, injected eps or None), the generated group in front of the condition."""
         B = out.shape[0]
         ws = self._workspace(h, dev, B)
         a = SdySfnoFwdArgs()
@@ -447,6 +481,10 @@ class SphericalFourierNeuralOperatorNet(nn.Module):
         a.ws, a.ws_floats = ptr(ws), ws.numel()
         a.reuse_encoder = int(reuse_encoder)
         a.shared_inputs = int(shared_inputs)
+        if gen is not None:
+            keep.append(gen)
+            a.gen_src, a.gen_chans, a.gen_pos = ptr(gen[0]), gen[0].shape[1], 1
+            a.gen_coef, a.gen_noise = ptr(gen[1]), ptr(gen[2])
         with torch.cuda.device(dev):
             check(lib.sdy_sfno_forward(h, C.byref(a), current_stream()), "sdy_sfno_forward")
 

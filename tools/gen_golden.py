@@ -226,11 +226,13 @@ def build_experiments(C, n_forc, H, W, E, L, hack, dropout, seed_f, seed_i, extr
     ipol.model.load_state_dict(isd, strict=False)
     dcfg = AttrDict(_target_="src.diffusion.dyffusion.DYffusion", timesteps=6, forward_conditioning="none",
                     interpolator=ipol, interpolator_local_checkpoint_path=None, time_encoding="dynamics",
-                    hack_for_imprecise_interpolation=hack,
-                    **{"enable_interpolator_dropout": bool(dropout), **(extra or {})})
+                    hack_for_imprecise_interpolation=hack, enable_interpolator_dropout=bool(dropout))
+    dcfg.update(extra or {})     # (`extra` may set forward_conditioning)
     fc = MultiHorizonForecastingDYffusion(model_config=mcfg(), datamodule_config=dm, diffusion_config=dcfg,
                                           verbose=False)
-    fcfg = SFNOConfig(in_chans=cs + n_forc, out_chans=C, nlat=H, nlon=W, embed_dim=E, num_layers=L,
+    # forward conditioning widens the forecaster by window * n_input channels (_base_experiment.py:207-225)
+    n_fwd = 0 if dcfg["forward_conditioning"] == "none" else cs
+    fcfg = SFNOConfig(in_chans=cs + n_fwd + n_forc, out_chans=C, nlat=H, nlon=W, embed_dim=E, num_layers=L,
                       with_time_emb=True, min_time=0.0, max_time=5.0)
     assert fc.model.model.in_chans == fcfg.in_chans
     fsd = make_state_dict(fcfg, seed=seed_f)
@@ -285,6 +287,113 @@ def gen_sample(tag, hack, dropout, extra=None, ipol_min_time=1.0):
     return trace
 
     # also exercise the stepper-facing surface once (get_preds_at_t_for_batch), results must equal sample()
+
+
+class RandnRecorder:
+    """Records every torch.randn_like draw while active (the reference's forward-conditioning noise)."""
+
+    def __enter__(self):
+        self.draws, self._orig = [], torch.randn_like
+
+        def rec(*a, **k):
+            e = self._orig(*a, **k)
+            self.draws.append(e.detach().clone())
+            return e
+        torch.randn_like = rec
+        return self.draws
+
+    def __exit__(self, *exc):
+        torch.randn_like = self._orig
+
+
+def _digest(*ts):
+    return np.array([float(t.double().abs().sum()) for t in ts] + [float((t.double() ** 2).sum()) for t in ts])
+
+
+def _seeded_sample_head(fcfg, icfg, fsd, isd, extra, hack, seeds, inputs):
+    """The part every seeded forward-conditioning fixture shares: configs, seeds and checksums instead of weights / inputs."""
+    return dict(hack=np.array(int(hack)), dropout=np.array(0), fcfg=json.dumps(fcfg.__dict__), icfg=json.dumps(icfg.__dict__),
+                diffusion_extra=json.dumps(extra), seed_f=np.array(seeds[0]), seed_i=np.array(seeds[1]),
+                seed_x=np.array(seeds[2]), f_digest=_weights_digest(fsd), i_digest=_weights_digest(isd),
+                inputs_digest=_digest(*inputs))
+
+
+def gen_sample_fcond_seeded(tag, hack, extra, ipol_min_time=1.0, B=1):
+    """One DYffusion.sample with forward conditioning, stored SEEDED (tests rebuild weights, inputs and noise from the seeds
+    and refuse to compare unless the checksums agree): the trace, the outputs, and for the noise modes the checksum of every
+    torch.randn_like draw of the pass.  The draws are the only use of torch's global generator in the pass (no dropout), so
+    after torch.manual_seed(seed_eps) they are torch.randn(x0.shape) one after the other -- asserted here."""
+    C, n_forc, H, W, E, L = 6, 2, 32, 64, 16, 2
+    seeds = (11, 22, 1234)
+    fc, ipol, fcfg, icfg, fsd, isd, cs = build_experiments(C, n_forc, H, W, E, L, hack, False, *seeds[:2], extra,
+                                                           ipol_min_time=ipol_min_time)
+    g = torch.Generator(device="cpu").manual_seed(seeds[2])
+    x0 = torch.randn(B, cs, H, W, generator=g)
+    if hack:
+        kw = {"static_condition": torch.randn(B, n_forc, H, W, generator=g)}
+    else:
+        kw = {"dynamical_condition": torch.randn(B, 7, n_forc, H, W, generator=g)}
+    trace = []
+    f_net, i_net = fc.model.model, ipol.model
+    hf = f_net.register_forward_pre_hook(lambda m, a, k: trace.append(["F", float(k["time"][0])]), with_kwargs=True)
+    hi = i_net.register_forward_pre_hook(lambda m, a, k: trace.append(["I", float(k["time"][0])]), with_kwargs=True)
+    seed_eps = 4242
+    torch.manual_seed(seed_eps)
+    with RandnRecorder() as eps:       # the forward-conditioning noise (dyffusion.py:321-330), in call order
+        res = fc.model.sample(x0, **kw)     # DYffusion.sample (dyffusion.py:569-572)
+    hf.remove()
+    hi.remove()
+    ge = torch.Generator(device="cpu").manual_seed(seed_eps)
+    for e in eps:
+        assert torch.equal(e, torch.randn(x0.shape, generator=ge)), "the noise draws are not the seeded sequence"
+    out = _seeded_sample_head(fcfg, icfg, fsd, isd, extra, hack, seeds, [x0] + list(kw.values()))
+    out.update(trace=json.dumps(trace), input_keys=json.dumps(list(kw)), batch=np.array(B), seed_eps=np.array(seed_eps),
+               n_eps=np.array(len(eps)), eps_digest=_digest(*eps) if eps else np.zeros(0))
+    for k, v in res.items():
+        out["out::" + k] = v.numpy()
+    np.savez_compressed(os.path.join(OUT, f"{tag}.npz"), **out)
+    print(f"{tag}: keys {sorted(res.keys())}, {len(trace)} network calls, {len(eps)} noise draws, saved")
+
+
+def gen_sample_fcond():
+    """DYffusion forward conditioning (src/diffusion/dyffusion.py:299-355; the forecaster sees [x_t | forward inputs |
+    dynamical condition | static condition], _base_model.py:166-192): "data" with a dynamical condition, "data" with the carried
+    channel and a static condition (four groups), both noise variants, v1 with two artificial steps (f = t / 7), and two
+    autoregressive windows through get_preds_at_t_for_batch (x_0 changes between them).  Seeded (small files)."""
+    gen_sample_fcond_seeded("fx_sample_fcond_data", False, dict(forward_conditioning="data"))
+    gen_sample_fcond_seeded("fx_sample_fcond_data_hack", True, dict(forward_conditioning="data"))
+    gen_sample_fcond_seeded("fx_sample_fcond_v1", False, dict(forward_conditioning="data+noise-v1"))
+    gen_sample_fcond_seeded("fx_sample_fcond_v2", False, dict(forward_conditioning="data+noise-v2"))
+    gen_sample_fcond_seeded("fx_sample_fcond_v1_k2", True, dict(forward_conditioning="data+noise-v1",
+                                                                additional_interpolation_steps=2), ipol_min_time=0.0)
+    gen_fcond_windows()
+
+
+def gen_fcond_windows(tag="fx_sample_fcond_windows", B=1):
+    """Two autoregressive windows of get_preds_at_t_for_batch (forecasting_multi_horizon.py:331-381, the stepper's
+    prepare_inputs=False form) with forward_conditioning="data": window 2 starts from window 1's last prediction.  Seeded;
+    stored: window 1's last prediction (window 2's x_0) and every prediction of window 2."""
+    C, n_forc, H, W, E, L = 6, 2, 32, 64, 16, 2
+    extra = dict(forward_conditioning="data")
+    seeds = (11, 22, 4321)
+    fc, ipol, fcfg, icfg, fsd, isd, cs = build_experiments(C, n_forc, H, W, E, L, False, False, *seeds[:2], extra)
+    g = torch.Generator(device="cpu").manual_seed(seeds[2])
+    x0 = torch.randn(B, cs, H, W, generator=g)
+    dyns = [torch.randn(B, 7, n_forc, H, W, generator=g) for _ in range(2)]
+    out = _seeded_sample_head(fcfg, icfg, fsd, isd, extra, False, seeds, [x0] + dyns)
+    out["batch"] = np.array(B)
+    x = x0
+    for w, dyn in enumerate(dyns):
+        res = {}
+        for h in range(1, 7):
+            batch = {"dynamics": x, "dynamical_condition": dyn}     # (read at h = 1 only; the reference pops from it)
+            res.update(fc.get_preds_at_t_for_batch(batch, horizon=h, split="predict", prepare_inputs=False))
+        x = res["t6_preds_normed"]
+        for k, v in res.items():
+            if w == 1 or k == "t6_preds_normed":
+                out[f"out{w}::" + k] = v.numpy()
+    np.savez_compressed(os.path.join(OUT, f"{tag}.npz"), **out)
+    print(f"{tag}: keys {sorted(res.keys())}, saved")
 
 
 def gen_sample_refine():
@@ -602,6 +711,7 @@ if __name__ == "__main__":
     gen_sample("fx_sample_tiny_masks", hack=True, dropout=True)
     gen_sample_refine()
     gen_sample_artificial()
+    gen_sample_fcond()
     with open(os.path.join(OUT, "fx_trace.json"), "w") as f:
         json.dump(t1, f)
     gen_stepper()
