@@ -344,7 +344,8 @@ typedef struct sdy_sfno_fwd_args {
   int shared_inputs;       /* 1 (needs rows_per_call = n < B): the stacked calls share their inputs -- every `in` tensor holds n
                               rows, and row b of the forward reads input row b % n (the two interpolations of a cold-sampling
                               step as ONE forward of 2n rows: same (x_0, forecast) and static condition, other time and dropout
-                              call).  The encoder then runs on n rows; results are bit-identical to stacking copies. */
+                              call).  The encoder then runs on n rows (when block 0 changes grids, on the default path;
+                              otherwise on all B rows); results are bit-identical to stacking copies. */
   /* One GENERATED channel group (DYffusion forward conditioning, src/diffusion/dyffusion.py:310-353): it holds
    *   a_b * gen_src[b, c, p] + s_b * eps(seed, call(b), batch_offset + b % n, c, p)     (n = rows_per_call or B,
    *   call(b) = call + b / n; eps: the forward-conditioning noise stream above), both products rounded before the sum.

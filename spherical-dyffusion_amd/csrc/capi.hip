@@ -102,6 +102,10 @@ struct sdy_sht_plan {
   // mcut[k] = number of orders that are live on ring k (kdead is non-decreasing in m).
   int* d_kdead = nullptr;   // [mtr]
   int* d_mcut = nullptr;    // [nlat]
+  // Resolved at creation from the tables above and the switches: the Legendre kernel of both directions, and whether the
+  // plan can take the contracts of the fft360 + leg_par pair (polar cut-off, tile-major Xf; plan_polar_ok / plan_tiled_ok)
+  enum Leg { LEG_PAR, LEG_H3, LEG_GEMM_H3, LEG_GEMM_F32 } leg = LEG_GEMM_F32;
+  bool fused360 = false;
 };
 
 // Every environment switch of the library, read once per process.  Each routes a stage to its fallback kernel (the only
@@ -123,6 +127,23 @@ const SdySwitches& sw() {
 }
 }  // namespace
 static int env_gemm_mode() { return sw().gemm_f32 ? 0 : 1; }
+
+template <class D, class T>
+static hipError_t upload(D** dst, const std::vector<T>& v) {
+  hipError_t e = hipMalloc((void**)dst, v.size() * sizeof(T));
+  return e == hipSuccess ? hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice) : e;
+}
+// value(m, row, k) of the analysis table wqT (rows l, k = latitude) / the synthesis table pf (rows = latitude, k = l): what the
+// fragment-stream packers read
+struct LegTables { const float *wqT, *pf; int nlat, lmax, Lpad4, Kpad4; };
+static float leg_wq_at(void* c, int m, int l, int k) {
+  const LegTables* x = static_cast<const LegTables*>(c);
+  return x->wqT[((size_t)m * x->nlat + k) * x->Lpad4 + l];
+}
+static float leg_pct_at(void* c, int m, int k, int l) {
+  const LegTables* x = static_cast<const LegTables*>(c);
+  return x->pf[((size_t)m * x->lmax + l) * x->Kpad4 + k];
+}
 
 extern "C" int sdy_sht_plan_create(int nlat, int nlon, int lmax, int mmax, int grid, sdy_sht_plan** out) {
   return sdy_sht_plan_create_ex(nlat, nlon, lmax, mmax, grid, env_gemm_mode(), out);
@@ -173,16 +194,11 @@ extern "C" int sdy_sht_plan_create_ex(int nlat, int nlon, int lmax, int mmax, in
     pw[2 * m] = (float)std::cos(a);
     pw[2 * m + 1] = (float)std::sin(a);
   }
-  hipError_t e;
-#define PLAN_UP(dst, vec)                                                                         \
-  e = hipMalloc((void**)&(dst), (vec).size() * sizeof(float));                                    \
-  if (e == hipSuccess) e = hipMemcpy((dst), (vec).data(), (vec).size() * sizeof(float), hipMemcpyHostToDevice); \
+  hipError_t e = upload(&p->d_wqT, wqT);
+  if (e == hipSuccess) e = upload(&p->d_pct, pf);
+  if (e == hipSuccess) e = upload(&p->d_tw, tw);
+  if (e == hipSuccess) e = upload(&p->d_pw, pw);
   if (e != hipSuccess) { sdy_sht_plan_destroy(p); return (int)e; }
-  PLAN_UP(p->d_wqT, wqT)
-  PLAN_UP(p->d_pct, pf)
-  PLAN_UP(p->d_tw, tw)
-  PLAN_UP(p->d_pw, pw)
-#undef PLAN_UP
   p->gemm_mode = gemm_mode;
   if (gemm_mode == 1) {
     // the fp32 tables (exactly what the reference's `.float()` buffers hold) split into fp16 hi + lo
@@ -191,47 +207,27 @@ extern "C" int sdy_sht_plan_create_ex(int nlat, int nlon, int lmax, int mmax, in
     p->s_wq = h3_pack_host(buf, mtr, lmax, nlat, p->h3_rows_fwd, p->h3_k_fwd, [&](int m, int l, int k) {
       return wqT[((size_t)m * nlat + k) * p->Lpad4 + l];
     });
-    e = hipMalloc(&p->d_wq_h3, buf.size() * sizeof(_Float16));
-    if (e == hipSuccess) e = hipMemcpy(p->d_wq_h3, buf.data(), buf.size() * sizeof(_Float16), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { sdy_sht_plan_destroy(p); return (int)e; }
+    if ((e = upload(&p->d_wq_h3, buf)) != hipSuccess) { sdy_sht_plan_destroy(p); return (int)e; }
     p->h3_rows_inv = nlat > 128 ? round_up(nlat, 256) : 128; p->h3_k_inv = round_up(lmax, 64);
     p->s_pct = h3_pack_host(buf, mtr, nlat, lmax, p->h3_rows_inv, p->h3_k_inv, [&](int m, int k, int l) {
       return pf[((size_t)m * lmax + l) * p->Kpad4 + k];
     });
-    e = hipMalloc(&p->d_pct_h3, buf.size() * sizeof(_Float16));
-    if (e == hipSuccess) e = hipMemcpy(p->d_pct_h3, buf.data(), buf.size() * sizeof(_Float16), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { sdy_sht_plan_destroy(p); return (int)e; }
+    if ((e = upload(&p->d_pct_h3, buf)) != hipSuccess) { sdy_sht_plan_destroy(p); return (int)e; }
   }
   if (gemm_mode == 1 && sdy_leg_h3_supported(lmax, nlat) && sdy_leg_h3_supported(nlat, lmax)) {
-    struct Ctx { const float* t; int nlat, lmax, Lpad4, Kpad4; } cx{nullptr, nlat, lmax, p->Lpad4, p->Kpad4};
+    LegTables cx{wqT.data(), pf.data(), nlat, lmax, p->Lpad4, p->Kpad4};
     e = hipMalloc(&p->d_wq_frag, sdy_leg_h3_table_bytes(mtr));
     if (e == hipSuccess) e = hipMalloc(&p->d_pct_frag, sdy_leg_h3_table_bytes(mtr));
     if (e != hipSuccess) { sdy_sht_plan_destroy(p); return (int)e; }
-    cx.t = wqT.data();
-    r = sdy_leg_h3_pack(mtr, lmax, nlat, [](void* c, int m, int l, int k) {
-      const Ctx* x = static_cast<const Ctx*>(c);
-      return x->t[((size_t)m * x->nlat + k) * x->Lpad4 + l];
-    }, &cx, p->d_wq_frag, &p->s_wq_frag);
-    cx.t = pf.data();
-    if (r == SDY_OK) r = sdy_leg_h3_pack(mtr, nlat, lmax, [](void* c, int m, int k, int l) {
-      const Ctx* x = static_cast<const Ctx*>(c);
-      return x->t[((size_t)m * x->lmax + l) * x->Kpad4 + k];
-    }, &cx, p->d_pct_frag, &p->s_pct_frag);
+    r = sdy_leg_h3_pack(mtr, lmax, nlat, leg_wq_at, &cx, p->d_wq_frag, &p->s_wq_frag);
+    if (r == SDY_OK) r = sdy_leg_h3_pack(mtr, nlat, lmax, leg_pct_at, &cx, p->d_pct_frag, &p->s_pct_frag);
     if (r != SDY_OK) { sdy_sht_plan_destroy(p); return r; }
     if (sdy_leg_par_supported(nlat, lmax)) {
       e = hipMalloc(&p->d_wq_par, sdy_leg_par_table_bytes(mtr));
       if (e == hipSuccess) e = hipMalloc(&p->d_pct_par, sdy_leg_par_table_bytes(mtr));
       if (e != hipSuccess) { sdy_sht_plan_destroy(p); return (int)e; }
-      cx.t = wqT.data();
-      r = sdy_leg_par_pack(mtr, nlat, lmax, 1, [](void* c, int m, int l, int k) {
-        const Ctx* x = static_cast<const Ctx*>(c);
-        return x->t[((size_t)m * x->nlat + k) * x->Lpad4 + l];
-      }, &cx, p->d_wq_par, &p->s_wq_par);
-      cx.t = pf.data();
-      if (r == SDY_OK) r = sdy_leg_par_pack(mtr, nlat, lmax, 0, [](void* c, int m, int k, int l) {
-        const Ctx* x = static_cast<const Ctx*>(c);
-        return x->t[((size_t)m * x->lmax + l) * x->Kpad4 + k];
-      }, &cx, p->d_pct_par, &p->s_pct_par);
+      r = sdy_leg_par_pack(mtr, nlat, lmax, 1, leg_wq_at, &cx, p->d_wq_par, &p->s_wq_par);
+      if (r == SDY_OK) r = sdy_leg_par_pack(mtr, nlat, lmax, 0, leg_pct_at, &cx, p->d_pct_par, &p->s_pct_par);
       if (r != SDY_OK) { sdy_sht_plan_destroy(p); return r; }
       // polar cut-off tables
       std::vector<int> kdead(mtr, 0), mcut(nlat, mtr);
@@ -262,33 +258,29 @@ extern "C" int sdy_sht_plan_create_ex(int nlat, int nlon, int lmax, int mmax, in
         while (c < mtr && kdead[c] <= kp) ++c;
         mcut[k] = c;
       }
-      e = hipMalloc((void**)&p->d_kdead, mtr * sizeof(int));
-      if (e == hipSuccess) e = hipMalloc((void**)&p->d_mcut, nlat * sizeof(int));
-      if (e == hipSuccess) e = hipMemcpy(p->d_kdead, kdead.data(), mtr * sizeof(int), hipMemcpyHostToDevice);
-      if (e == hipSuccess) e = hipMemcpy(p->d_mcut, mcut.data(), nlat * sizeof(int), hipMemcpyHostToDevice);
+      e = upload(&p->d_kdead, kdead);
+      if (e == hipSuccess) e = upload(&p->d_mcut, mcut);
       if (e != hipSuccess) { sdy_sht_plan_destroy(p); return (int)e; }
     }
   }
   p->fft.tw = p->d_tw;
   p->fft.pw = p->d_pw;
+  p->fft.fft360 = !sw().no_fft360;
+  const bool no_frag = sw().no_leg_frag, no_par = sw().no_leg_par;
+  p->leg = (p->d_wq_par && !no_frag && !no_par) ? sdy_sht_plan::LEG_PAR
+         : (p->d_wq_frag && !no_frag)          ? sdy_sht_plan::LEG_H3
+         : gemm_mode == 1                      ? sdy_sht_plan::LEG_GEMM_H3
+                                               : sdy_sht_plan::LEG_GEMM_F32;
+  p->fused360 = p->leg == sdy_sht_plan::LEG_PAR && p->fft.fft360 && p->fft.n == 180;
   *out = p;
   return SDY_OK;
 }
 
 extern "C" void sdy_sht_plan_destroy(sdy_sht_plan* p) {
   if (!p) return;
-  if (p->d_wqT) (void)hipFree(p->d_wqT);
-  if (p->d_pct) (void)hipFree(p->d_pct);
-  if (p->d_tw) (void)hipFree(p->d_tw);
-  if (p->d_pw) (void)hipFree(p->d_pw);
-  if (p->d_wq_h3) (void)hipFree(p->d_wq_h3);
-  if (p->d_pct_h3) (void)hipFree(p->d_pct_h3);
-  if (p->d_kdead) (void)hipFree(p->d_kdead);
-  if (p->d_mcut) (void)hipFree(p->d_mcut);
-  if (p->d_wq_par) (void)hipFree(p->d_wq_par);
-  if (p->d_pct_par) (void)hipFree(p->d_pct_par);
-  if (p->d_wq_frag) (void)hipFree(p->d_wq_frag);
-  if (p->d_pct_frag) (void)hipFree(p->d_pct_frag);
+  for (void* b : {(void*)p->d_wqT, (void*)p->d_pct, (void*)p->d_tw, (void*)p->d_pw, p->d_wq_h3, p->d_pct_h3, (void*)p->d_kdead,
+                  (void*)p->d_mcut, p->d_wq_par, p->d_pct_par, p->d_wq_frag, p->d_pct_frag})
+    if (b) (void)hipFree(b);
   delete p;
 }
 
@@ -319,24 +311,13 @@ extern "C" int sdy_irfft_lon(const sdy_sht_plan* p, const float* Yf, const float
   return sdy_fft_launch_inv(p->fft, Yf, bias, y, B, C, p->nlat, p->mtr, 0, nullptr, (hipStream_t)stream);
 }
 
-static int legendre_fwd_impl(const sdy_sht_plan* p, const float* Xf, float* Cs, int B, int C, bool polar, void* stream,
-                             bool tiled = false, bool cs_tiled = false);
-extern "C" int sdy_legendre_fwd(const sdy_sht_plan* p, const float* Xf, float* Cs, int B, int C, void* stream) {
-  return legendre_fwd_impl(p, Xf, Cs, B, C, false, stream);
-}
 // polar: skip the rows / orders of the polar cut-off (only valid when the producer / consumer of Xf is fft360 with the same
 // cut-off: plan_polar_ok)
-static bool plan_polar_ok(const sdy_sht_plan* p, int C) {
-  const bool off = sw().no_fft360 || sw().no_leg_par || sw().no_leg_frag;
-  return !off && p->d_kdead && p->d_wq_par && p->fft.n == 180 && C % 16 == 0;
-}
+static bool plan_polar_ok(const sdy_sht_plan* p, int C) { return p->fused360 && C % 16 == 0; }
 // Tile-major grid-frequency tensor (fft.h, ilv == 2): like the polar cut-off a contract between fft360 and leg_par only --
 // the plane of one order is stored as whole 64-column tiles, so a Legendre workgroup's activation tile is one contiguous
 // block.
-static bool plan_tiled_ok(const sdy_sht_plan* p, int C, int ilv) {
-  const bool off = sw().no_fft360 || sw().no_leg_par || sw().no_leg_frag;
-  return !off && ilv == 1 && p->d_wq_par && p->d_pct_par && p->fft.n == 180 && C % 32 == 0;
-}
+static bool plan_tiled_ok(const sdy_sht_plan* p, int C, int ilv) { return p->fused360 && ilv == 1 && C % 32 == 0; }
 static int legendre_fwd_impl(const sdy_sht_plan* p, const float* Xf, float* Cs, int B, int C, bool polar, void* stream,
                              bool tiled, bool cs_tiled) {
   if (!p || !Xf || !Cs || B <= 0 || C <= 0) return SDY_ERR_ARG;
@@ -348,28 +329,25 @@ static int legendre_fwd_impl(const sdy_sht_plan* p, const float* Xf, float* Cs, 
   g.C = Cs; g.ldc = p->mtr * N; g.sC = N;
   g.M = p->Lpad4; g.M_store = p->lmax; g.N = N; g.K = p->nlat; g.nbatch = p->mtr;
   g.tri_mode = SDY_TRI_LEG_FWD; g.tile = SDY_TILE_64x128;
-  const bool no_frag = sw().no_leg_frag, no_par = sw().no_leg_par;
-  if (p->d_wq_par && !no_frag && !no_par)
+  if (p->leg == sdy_sht_plan::LEG_PAR)
     // cs_tiled: the coefficients TILE-MAJOR by order, [m][column tile][l][64] (dh_h3.hip, DhParams::tiled)
     return sdy_leg_par_launch(p->d_wq_par, p->s_wq_par, p->mtr, Xf, tiled ? 64 : N, (long)p->nlat * N, Cs,
                               cs_tiled ? 64L : (long)p->mtr * N, cs_tiled ? (long)(N / 64) * p->lmax * 64 : (long)N,
                               p->lmax, p->nlat, N, 1, polar ? p->d_kdead : nullptr, (hipStream_t)stream,
                               tiled ? 64L * p->nlat : 0L, cs_tiled ? 64L * p->lmax : 0L);
   if (tiled || cs_tiled) return SDY_ERR_UNSUPPORTED;
-  if (p->d_wq_frag && !no_frag)
+  if (p->leg == sdy_sht_plan::LEG_H3)
     return sdy_leg_h3_launch(p->d_wq_frag, p->s_wq_frag, p->mtr, Xf, N, (long)p->nlat * N, Cs, (long)p->mtr * N, N, p->lmax,
                              p->nlat, N, SDY_TRI_LEG_FWD, (hipStream_t)stream);
-  if (p->gemm_mode == 1)
+  if (p->leg == sdy_sht_plan::LEG_GEMM_H3)
     return sdy_gemm_h3_launch(g, p->d_wq_h3, p->h3_rows_fwd, p->h3_k_fwd, (long)p->h3_rows_fwd * p->h3_k_fwd,
                               (long)p->mtr * p->h3_rows_fwd * p->h3_k_fwd, p->s_wq, 0, (hipStream_t)stream);
   return sdy_gemm_launch(g, (hipStream_t)stream);
 }
-
-static int legendre_inv_impl(const sdy_sht_plan* p, const float* Cs, float* Yf, int B, int C, bool polar, void* stream,
-                             bool tiled = false, bool cs_tiled = false);
-extern "C" int sdy_legendre_inv(const sdy_sht_plan* p, const float* Cs, float* Yf, int B, int C, void* stream) {
-  return legendre_inv_impl(p, Cs, Yf, B, C, false, stream);
+extern "C" int sdy_legendre_fwd(const sdy_sht_plan* p, const float* Xf, float* Cs, int B, int C, void* stream) {
+  return legendre_fwd_impl(p, Xf, Cs, B, C, false, stream, false, false);
 }
+
 static int legendre_inv_impl(const sdy_sht_plan* p, const float* Cs, float* Yf, int B, int C, bool polar, void* stream,
                              bool tiled, bool cs_tiled) {
   if (!p || !Cs || !Yf || B <= 0 || C <= 0) return SDY_ERR_ARG;
@@ -381,20 +359,22 @@ static int legendre_inv_impl(const sdy_sht_plan* p, const float* Cs, float* Yf, 
   g.C = Yf; g.ldc = N; g.sC = (long)p->nlat * N;
   g.M = p->Kpad4; g.M_store = p->nlat; g.N = N; g.K = p->lmax; g.nbatch = p->mtr;
   g.tri_mode = SDY_TRI_LEG_INV; g.tile = SDY_TILE_64x128;
-  const bool no_frag = sw().no_leg_frag, no_par = sw().no_leg_par;
-  if (p->d_pct_par && !no_frag && !no_par)
+  if (p->leg == sdy_sht_plan::LEG_PAR)
     return sdy_leg_par_launch(p->d_pct_par, p->s_pct_par, p->mtr, Cs, cs_tiled ? 64L : (long)p->mtr * N,
                               cs_tiled ? (long)(N / 64) * p->lmax * 64 : (long)N, Yf, tiled ? 64 : N,
                               (long)p->nlat * N, p->nlat, p->lmax, N, 0, polar ? p->d_kdead : nullptr, (hipStream_t)stream,
                               cs_tiled ? 64L * p->lmax : 0L, tiled ? 64L * p->nlat : 0L);
   if (tiled || cs_tiled) return SDY_ERR_UNSUPPORTED;
-  if (p->d_pct_frag && !no_frag)
+  if (p->leg == sdy_sht_plan::LEG_H3)
     return sdy_leg_h3_launch(p->d_pct_frag, p->s_pct_frag, p->mtr, Cs, (long)p->mtr * N, N, Yf, N, (long)p->nlat * N, p->nlat,
                              p->lmax, N, SDY_TRI_LEG_INV, (hipStream_t)stream);
-  if (p->gemm_mode == 1)
+  if (p->leg == sdy_sht_plan::LEG_GEMM_H3)
     return sdy_gemm_h3_launch(g, p->d_pct_h3, p->h3_rows_inv, p->h3_k_inv, (long)p->h3_rows_inv * p->h3_k_inv,
                               (long)p->mtr * p->h3_rows_inv * p->h3_k_inv, p->s_pct, 0, (hipStream_t)stream);
   return sdy_gemm_launch(g, (hipStream_t)stream);
+}
+extern "C" int sdy_legendre_inv(const sdy_sht_plan* p, const float* Cs, float* Yf, int B, int C, void* stream) {
+  return legendre_inv_impl(p, Cs, Yf, B, C, false, stream, false, false);
 }
 
 extern "C" int sdy_sht_forward(const sdy_sht_plan* p, const float* x, float* out_c64, int B, int C, float* ws,
@@ -606,10 +586,9 @@ struct BlockW {
   std::vector<float> w1_host, w2_host;
   void* mlp = nullptr;
   float mlp_s1 = 1.0f, mlp_s2 = 1.0f;
-  // Inner skip FOLDED into the dhconv (grid-changing blocks only, see skip_foldable): host copies of the filter weight, the
-  // skip weight and the two biases until all are known; then `fw.frag` holds W_dh[l] + W_skip and `fbs` = filter bias + skip bias
+  // Inner skip FOLDED into the dhconv (DH_FOLDED, see skip_foldable): host copies of the filter weight, the skip weight and the
+  // two biases until all are known; then `fw.frag` holds W_dh[l] + W_skip and `fbs` = filter bias + skip bias
   std::vector<float> fw_host, skw_host, fb_host, skb_host;
-  bool skip_folded = false;
   DevBuf fbs;
 };
 
@@ -629,8 +608,49 @@ static int spec_ilv(const sdy_sfno_config& c) { return (c.gemm_mode == 1 && c.em
 // on the dh_h3 path (split-fp16 mode, 256 channels); every other configuration runs the convolution as the reference does.
 static bool skip_foldable(const sdy_sfno_config& c, int i) {
   const bool first = i == 0, last = i == c.num_layers - 1;
-  return c.gemm_mode == 1 && c.data_grid != SDY_GRID_LEGENDRE_GAUSS && first != last && !sw().no_skip_fold;
+  return c.gemm_mode == 1 && c.data_grid != SDY_GRID_LEGENDRE_GAUSS && first != last;
 }
+
+// The kernel of block i's dhconv, and so how sdy_sfno_set_param packs its filter.filter.weight: the persistent fragment-stream
+// kernel (dh_h3.hip) with the inner skip folded in or not, the split-fp16 tile GEMM, or the fp32 GEMM.
+enum DhKind { DH_FOLDED, DH_FRAG, DH_GEMM_H3, DH_GEMM_F32 };
+static DhKind dhconv_kind(const sdy_sfno_config& c, int i) {
+  if (c.gemm_mode != 1) return DH_GEMM_F32;
+  if (!sdy_dhconv_frag_supported(c.embed_dim, c.embed_dim) || sw().no_dh_frag) return DH_GEMM_H3;
+  return skip_foldable(c, i) && !sw().no_skip_fold ? DH_FOLDED : DH_FRAG;
+}
+
+namespace {
+// One side of a block's spectral transform: its grid and the contracts its FFT and Legendre kernels agree on.
+struct XfSide {
+  const sdy_sht_plan* plan;
+  bool polar;          // polar cut-off (plan_polar_ok)
+  bool tiled;          // Xf / Yf tile-major (plan_tiled_ok)
+  int ilv;             // channel order of Xf / Yf (fft.h): 2 when tiled, else spec_ilv
+  const int* mcut;     // the FFT's polar cut-off: plan->d_mcut when polar, else nullptr
+};
+
+// How block i runs.  Depends on the config, the packed weights and the switches only: resolved by sdy_sfno_ready.
+struct BlockPath {
+  XfSide in, out;          // data grid at the first block's input / the last block's output, else the Gauss grid
+  bool scale_residual;     // in.plan != out.plan: the residual is the SHT round trip of norm0(x) (s2convolutions.py:79-83)
+  bool fused_mlp;          // one mlp_h3 launch (injected masks too: sdy_mlp_args.keep_hidden / keep_out)
+  // The block's residual is norm0(x) (or its SHT round trip when the grids differ).  With the fused MLP kernel the normalised
+  // tensor is never materialised: its two consumers (inner skip, final residual add) apply a*x + d to the block input.
+  bool lazy_norm;
+  // Cs / Cs2 tile-major by order too (analysis stores and synthesis loads become contiguous tiles; dh_h3 reads and writes
+  // 256-byte pieces instead of 2 KB rows, which it does not notice: it is matrix / issue bound).
+  bool cs_tiled;
+  DhKind dh;
+  // x = GELU(y + inner_skip(residual)): a convolution, or with the skip folded into the dhconv a GELU pass over y, or nothing
+  enum Skip { SKIP_CONV, SKIP_GELU, SKIP_IN_FFT } skip;
+  bool stats1;             // norm1 statistics from the inner-skip convolution's epilogue (conv_h3)
+  // The tensor between the inner skip and the fused MLP has exactly one producer and one consumer, both walking 64-pixel
+  // tiles: it is stored TILE-MAJOR (a tile = one contiguous 64 KB block for the stores of one and the loads of the other).
+  bool z_tiled;
+  bool drop_skip;          // the drop-path skip can apply (the kernels of the default path take the row map)
+};
+}  // namespace
 
 struct sdy_sfno {
   sdy_sfno_config cfg;
@@ -642,6 +662,7 @@ struct sdy_sfno {
   struct Pair { std::vector<float> w1_host, w2_host; void* w = nullptr; float s1 = 1.0f, s2 = 1.0f; } enc, dec;
   DevBuf t1w, t1b, t3w, t3b, freq, wbt, bb;
   std::vector<BlockW> blk;
+  std::vector<BlockPath> path;   // one per block once sdy_sfno_ready has resolved them; emptied by every set_param
   SdyTimeMlp tm;
   std::string missing;
   // sdy_sfno_fwd_args.reuse_encoder: where (and for which batch) the last forward left its encoder output
@@ -774,6 +795,7 @@ extern "C" int sdy_sfno_set_param(sdy_sfno* n, const char* name_c, const float* 
   const std::string name(name_c);
   const bool h3 = c.gemm_mode == 1;
   n->enc_ws = nullptr;   // new weights: a stored encoder output (sdy_sfno_fwd_args.reuse_encoder) is no longer this network's
+  n->path.clear();       // ... and the kernel paths are resolved again by sdy_sfno_ready
   // non-persistent SHT buffers of older torch-harmonics releases: accepted, ignored
   if (name.find("trans") != std::string::npos && (name.find(".weights") != std::string::npos ||
                                                    name.find(".pct") != std::string::npos))
@@ -864,21 +886,19 @@ extern "C" int sdy_sfno_set_param(sdy_sfno* n, const char* name_c, const float* 
           for (int l = 0; l < c.lmax; ++l) d[2 * l] += ws;
         }
       if (!w.fw.frag) SDY_HIP_TRY(hipMalloc(&w.fw.frag, sdy_dhconv_frag_pack_bytes(c.lmax)));
-      SDY_TRY(sdy_dh_h3_pack(sum.data(), c.lmax, w.fw.frag, &w.fw.frag_scale, spec_ilv(c)));
-      w.skip_folded = true;
-      return SDY_OK;
+      return sdy_dh_h3_pack(sum.data(), c.lmax, w.fw.frag, &w.fw.frag_scale, spec_ilv(c));
     };
-    const bool fold = skip_foldable(c, i) && sdy_dhconv_frag_supported(E, E) && !sw().no_dh_frag;
+    const DhKind dh = dhconv_kind(c, i);
+    const bool fold = dh == DH_FOLDED;
     if (rest == "filter.filter.weight") {
       EXPECT_NUMEL((size_t)E * E * c.lmax * 2);
-      const bool no_dh_frag = sw().no_dh_frag;
       if (fold) {   // packed when the skip weight is here too
         w.fw_host.assign(host, host + numel);
         SDY_TRY(pack_folded());
-      } else if (h3 && sdy_dhconv_frag_supported(E, E) && !no_dh_frag) {   // persistent fragment-stream kernel (dh_h3.hip)
+      } else if (dh == DH_FRAG) {   // persistent fragment-stream kernel (dh_h3.hip)
         if (!w.fw.frag) SDY_HIP_TRY(hipMalloc(&w.fw.frag, sdy_dhconv_frag_pack_bytes(c.lmax)));
         SDY_TRY(sdy_dh_h3_pack(host, c.lmax, w.fw.frag, &w.fw.frag_scale, spec_ilv(c)));
-      } else if (h3) {
+      } else if (dh == DH_GEMM_H3) {
         if (w.fw.h3) (void)hipFree(w.fw.h3);
         w.fw.h3 = nullptr;
         SDY_HIP_TRY(hipMalloc(&w.fw.h3, sdy_dhconv_h3_pack_bytes(E, E, c.lmax)));
@@ -941,9 +961,35 @@ extern "C" int sdy_sfno_set_param(sdy_sfno* n, const char* name_c, const float* 
   return SDY_ERR_NAME;
 }
 
+static BlockPath resolve_path(const sdy_sfno* n, int i) {
+  const sdy_sfno_config& c = n->cfg;
+  const BlockW& w = n->blk[i];
+  const int E = c.embed_dim, ilv = spec_ilv(c);
+  auto side = [&](const sdy_sht_plan* p) {
+    const bool polar = plan_polar_ok(p, E), tiled = plan_tiled_ok(p, E, ilv);
+    return XfSide{p, polar, tiled, tiled ? 2 : ilv, polar ? p->d_mcut : nullptr};
+  };
+  BlockPath b;
+  b.in = side(i == 0 ? n->plan_data : n->plan_lg);
+  b.out = side(i == c.num_layers - 1 ? n->plan_data : n->plan_lg);
+  b.scale_residual = b.in.plan != b.out.plan;
+  b.fused_mlp = w.mlp && !sw().no_fused_mlp;
+  b.lazy_norm = b.fused_mlp && !b.scale_residual;
+  b.dh = dhconv_kind(c, i);
+  const bool dh_frag = b.dh == DH_FOLDED || b.dh == DH_FRAG;
+  b.cs_tiled = b.in.tiled && b.out.tiled && dh_frag && b.in.plan->lmax == b.out.plan->lmax && b.in.plan->mtr == b.out.plan->mtr;
+  b.stats1 = c.gemm_mode == 1 && w.skw.frag && sdy_conv256_h3_supported(E, E);
+  b.z_tiled = b.stats1 && b.fused_mlp;
+  b.skip = b.dh != DH_FOLDED ? BlockPath::SKIP_CONV : (b.out.tiled && b.z_tiled) ? BlockPath::SKIP_IN_FFT : BlockPath::SKIP_GELU;
+  // the drop-path skip needs the row map of fft360, dh_h3, conv_h3 and mlp_h3; SDY_NO_DROP_SKIP=1 computes every row
+  b.drop_skip = b.fused_mlp && b.z_tiled && b.cs_tiled && !sw().no_drop_skip;
+  return b;
+}
+
 extern "C" int sdy_sfno_ready(const sdy_sfno* n_c) {
   sdy_sfno* n = const_cast<sdy_sfno*>(n_c);
   if (!n) return SDY_ERR_ARG;
+  if (!n->path.empty()) return SDY_OK;   // resolved, and no parameter has been set since
   const sdy_sfno_config& c = n->cfg;
   n->missing.clear();
   auto need = [&](const DevBuf& b, const std::string& nm) {
@@ -975,6 +1021,17 @@ extern "C" int sdy_sfno_ready(const sdy_sfno* n_c) {
   } else {
     n->tm.E = 0;
   }
+  std::vector<BlockPath> path;
+  for (int i = 0; i < c.num_layers; ++i) {
+    const BlockW& w = n->blk[i];
+    const BlockPath b = resolve_path(n, i);
+    const void* packed = b.dh == DH_GEMM_F32 ? (const void*)w.fw.p : b.dh == DH_GEMM_H3 ? w.fw.h3 : w.fw.frag;
+    if (!packed) return SDY_ERR_STATE;
+    // the packed dhconv stream of a folded block HOLDS the inner skip: it runs in a grid-changing block with the summed biases
+    if (b.dh == DH_FOLDED && !(b.scale_residual && w.fbs.set)) return SDY_ERR_STATE;
+    path.push_back(b);
+  }
+  n->path = std::move(path);
   return SDY_OK;
 }
 
@@ -991,20 +1048,15 @@ WsLayout ws_layout(const sdy_sfno* n, int B) {
   size_t off = 0;
   auto take = [&](size_t floats) { size_t o = off; off += round_up_sz(floats, 64); return o; };
   w.cat = take((size_t)B * n->catC * HW);
-  w.xa = take((size_t)B * E * HW);
-  w.xb = take((size_t)B * E * HW);
-  w.xe = take((size_t)B * E * HW);    // encoder output: block 0 reads it, nothing overwrites it (sdy_sfno_fwd_args.reuse_encoder)
-  w.xn = take((size_t)B * E * HW);
-  w.y = take((size_t)B * E * HW);
+  const size_t img = (size_t)B * E * HW;
+  w.xa = take(img); w.xb = take(img);
+  w.xe = take(img);    // encoder output: block 0 reads it, nothing overwrites it (sdy_sfno_fwd_args.reuse_encoder)
+  w.xn = take(img); w.y = take(img);
   w.zt = take((size_t)B * ((HW + 63) / 64) * E * 64);   // inner-skip output, tile-major (conv_h3 -> mlp_h3), tiles padded
   w.hid = take((size_t)B * c.mlp_hidden * HW);
   w.xf = take(xf_floats(n->plan_data, B, (int)E));
-  w.cs = take(cs_floats(n->plan_data, B, (int)E));
-  w.cs2 = take(cs_floats(n->plan_data, B, (int)E));
-  w.ca = take((size_t)B * E);
-  w.cd = take((size_t)B * E);
-  w.ca1 = take((size_t)B * E);
-  w.cd1 = take((size_t)B * E);
+  w.cs = take(cs_floats(n->plan_data, B, (int)E)); w.cs2 = take(cs_floats(n->plan_data, B, (int)E));
+  w.ca = take((size_t)B * E); w.cd = take((size_t)B * E); w.ca1 = take((size_t)B * E); w.cd1 = take((size_t)B * E);
   w.st1 = take((size_t)B * E * 4);   // same for norm1, filled by the inner-skip convolution's epilogue
   w.st0 = take((size_t)B * E * 4);   // (sum, sumsq) doubles of the next block's norm0, filled by the fused MLP epilogue
   w.ste = take((size_t)B * E * 4);   // the encoder output's statistics (block 0's norm0), kept for reuse_encoder
@@ -1031,13 +1083,8 @@ extern "C" int sdy_sfno_max_batch(const sdy_sfno* n) {
   if (!n) return 0;
   const sdy_sfno_config& c = n->cfg;
   const int mtr = c.mmax < c.lmax ? c.mmax : c.lmax;
-  bool all_tiled = c.gemm_mode == 1 && n->plan_data && n->plan_lg;
-  if (all_tiled) {
-    const int ilv = spec_ilv(c);
-    all_tiled = plan_tiled_ok(n->plan_data, c.embed_dim, ilv) && plan_tiled_ok(n->plan_lg, c.embed_dim, ilv) &&
-                n->plan_data->lmax == n->plan_lg->lmax && n->plan_data->mtr == n->plan_lg->mtr;
-    for (const BlockW& w : n->blk) all_tiled = all_tiled && w.fw.frag != nullptr;
-  }
+  bool all_tiled = sdy_sfno_ready(n) == SDY_OK;
+  for (const BlockPath& p : n->path) all_tiled = all_tiled && p.cs_tiled;
   long b;
   if (all_tiled) {
     b = ((1L << 32) - 1) / ((long)mtr * 8 * c.lmax * 64);
@@ -1160,338 +1207,367 @@ extern "C" int sdy_profile_read_rows(double* total_ms, long* launches, long* row
   return rc;
 }
 
-extern "C" int sdy_sfno_forward(sdy_sfno* n, const sdy_sfno_fwd_args* a, void* stream_v) {
-  if (!n || !a || !a->out || !a->ws || a->B <= 0) return SDY_ERR_ARG;
-  SDY_TRY(sdy_sfno_ready(n));
-  const sdy_sfno_config& c = n->cfg;
-  hipStream_t stream = (hipStream_t)stream_v;
-  const int B = a->B, E = c.embed_dim, L = c.num_layers, HW = n->HW, Cin = c.in_chans, Hd = c.mlp_hidden;
-  if (c.with_time_emb && !a->time) return SDY_ERR_ARG;
-  const WsLayout w = ws_layout(n, B);
-  if (a->ws_floats < w.total) return SDY_ERR_WORKSPACE;
-  float* ws = a->ws;
-  float *cat = ws + w.cat, *xa = ws + w.xa, *xb = ws + w.xb, *xn = ws + w.xn, *y = ws + w.y, *hid = ws + w.hid;
-  float *Xf = ws + w.xf, *Cs = ws + w.cs, *Cs2 = ws + w.cs2, *ca = ws + w.ca, *cd = ws + w.cd;
-  float *ca1 = ws + w.ca1, *cd1 = ws + w.cd1;
-  double* st0 = reinterpret_cast<double*>(ws + w.st0);   // take() rounds offsets to 64 floats: 8-byte aligned
-  double* st1 = reinterpret_cast<double*>(ws + w.st1);
-  SDY_HIP_TRY(hipMemsetAsync(st1, 0, (size_t)B * E * 2 * sizeof(double), stream));
-  bool have_st0 = false;                                  // statistics of `cur` are waiting in st0
-  SDY_HIP_TRY(hipMemsetAsync(st0, 0, (size_t)B * E * 2 * sizeof(double), stream));
-  float *ss = ws + w.ss, *dp = ws + w.dp, *trep = ws + w.trep;
-  float* xe = ws + w.xe;
-  double* ste = reinterpret_cast<double*>(ws + w.ste);
-  const bool reuse = a->reuse_encoder != 0;
-  if (reuse && (n->enc_ws != ws || n->enc_B != B)) return SDY_ERR_STATE;   // no previous forward on this workspace / batch
-  // (a forward that overwrites the inputs invalidates the stored encoder output until its own encoder launch has been
-  //  enqueued: an early error return must not leave a handle that claims a valid one)
-  if (!reuse) n->enc_ws = nullptr;
-
-  // ---- input concat (BaseModel.concat_condition_if_needed, _base_model.py:166-192) into the tail of the big-skip
-  //      buffer: cat = [ block output (E) | inputs (Cin) ]  (sfnonet.py:804-805,831-832)
-  const float* srcs[4];
-  int chans[4];
-  int ns = 0, ctot = 0;
-  for (int i = 0; i < 3; ++i)
-    if (a->in[i] && a->in_chans[i] > 0) { srcs[ns] = a->in[i]; chans[ns] = a->in_chans[i]; ctot += a->in_chans[i]; ++ns; }
-  // the generated group (forward conditioning) joins the list at its position
-  const bool gen = a->gen_src != nullptr;
-  if (gen) {
-    if (a->gen_chans <= 0 || !a->gen_coef || a->gen_pos < 0 || a->gen_pos > ns) return SDY_ERR_ARG;
-    if (a->reuse_encoder || a->shared_inputs) return SDY_ERR_ARG;     // its values change with every call
-    for (int i = ns; i > a->gen_pos; --i) { srcs[i] = srcs[i - 1]; chans[i] = chans[i - 1]; }
-    srcs[a->gen_pos] = a->gen_src; chans[a->gen_pos] = a->gen_chans; ctot += a->gen_chans; ++ns;
-  }
-  if (ns == 0 || ctot != Cin) return SDY_ERR_SHAPE;
-  const long cat_bs = (long)n->catC * HW;
-  float* cat_in = cat + (size_t)(n->catC - Cin) * HW;
-  const bool drop = a->enable_dropout != 0;
-  if (a->rows_per_call < 0 || (a->rows_per_call > 0 && B % a->rows_per_call)) return SDY_ERR_ARG;
+namespace {
+// One sdy_sfno_forward call: its rows, workspace, dropout stream and stream.  The driver runs its stages in order.
+struct SfnoCall {
+  sdy_sfno* n;
+  const sdy_sfno_config& c;
+  const sdy_sfno_fwd_args* a;
+  hipStream_t stream;
+  const int B, E = c.embed_dim, HW = n->HW, ilv = spec_ilv(c);   // ilv: channel order of Xf / Cs / Cs2 inside the forward
   const int rpc = a->rows_per_call > 0 ? a->rows_per_call : B;   // stacked calls (sdy_sfno_fwd_args.rows_per_call)
+  const bool drop = a->enable_dropout != 0, reuse = a->reuse_encoder != 0, shared = a->shared_inputs != 0, gen = a->gen_src;
   // shared_inputs: the stacked calls read the same rpc input rows (row b: input row b % rpc).  The concat still writes all B
   // rows (the decoder reads them beside every row's own block output); the ENCODER runs on the rpc distinct rows when block 0
-  // can take its input through a row rule -- its only reader is then the forward FFT (x_mod): the grid-changing first block of
-  // an equiangular data grid on the fft360 + leg_par path, with the encoder's own statistics (the production shape).
-  const bool shared = a->shared_inputs != 0;
-  if (shared && (reuse || rpc >= B)) return SDY_ERR_ARG;
-  // (reuse_encoder: the inputs already sit in the tail of `cat` -- no block writes there -- and the encoder output in xe)
-  if (gen) {
-    SdyConcatGen g;
-    g.gen = a->gen_pos; g.coef = a->gen_coef; g.noise = a->gen_noise;
-    g.seed = a->seed; g.call = a->call; g.batch_offset = a->batch_offset; g.rows_per_call = rpc;
-    SDY_STAGE(ST_CONCAT, sdy_concat_gen_launch(srcs, chans, ns, g, cat_in, cat_bs, B, HW, stream));
-  } else if (!reuse) {
-    SDY_STAGE(ST_CONCAT, sdy_concat_launch(srcs, chans, ns, cat_in, cat_bs, B, HW, stream, shared ? rpc : 0));
-  }
-  const bool enc_once = shared && n->enc.w && n->plan_data != n->plan_lg && plan_tiled_ok(n->plan_data, E, spec_ilv(c));
-  const int Be = enc_once ? rpc : B;                               // rows the encoder computes
+  // can take its input through a row rule -- its only reader is then the forward FFT (x_mod): a grid-changing first block (its
+  // residual is the SHT round trip) on the fft360 + leg_par path, with the encoder's own statistics (the production shape).
+  const bool enc_once = shared && n->enc.w && n->path[0].scale_residual && n->path[0].in.tiled;
+  const int Be = enc_once ? rpc : B;                                 // rows the encoder computes
+  const float pm = (drop && c.dropout_mlp > 0.f) ? c.dropout_mlp : 0.f;   // the MLP's dropout probability
+  const WsLayout w = ws_layout(n, B);
+  float* const ws = a->ws;
+  const long xbs = (long)E * HW, cat_bs = (long)n->catC * HW;       // floats per batch row: E-channel image, big-skip buffer
+  const long zt_bs = (long)((HW + 63) / 64) * E * 64;                // ... and the tile-major MLP input
+  float *cat = ws + w.cat, *xa = ws + w.xa, *xb = ws + w.xb, *xe = ws + w.xe, *xn = ws + w.xn, *y = ws + w.y, *zt = ws + w.zt;
+  float *hid = ws + w.hid, *Xf = ws + w.xf, *Cs = ws + w.cs, *Cs2 = ws + w.cs2, *ss = ws + w.ss, *dp = ws + w.dp;
+  float *ca = ws + w.ca, *cd = ws + w.cd, *ca1 = ws + w.ca1, *cd1 = ws + w.cd1, *trep = ws + w.trep;
+  float* cat_in = cat + (size_t)(n->catC - c.in_chans) * HW;
+  // statistics doubles (ws_layout; take() rounds offsets to 64 floats: 8-byte aligned)
+  double *st0 = reinterpret_cast<double*>(ws + w.st0), *st1 = reinterpret_cast<double*>(ws + w.st1);
+  double *ste = reinterpret_cast<double*>(ws + w.ste), *sp = reinterpret_cast<double*>(ws + w.sp);
+  const float* srcs[4];              // the input groups in concat order
+  int chans[4], ns = 0;
+  float *cur = xe, *nxt = xa;        // the block input, and where the next block writes
+  double* cur_stats = nullptr;       // statistics of `cur` its producer accumulated (st0), or nullptr: norm0 takes a pass
 
-  // ---- time embedding + per-layer (scale|shift) + drop-path scales
-  SDY_STAGE(ST_TIME_MLP, sdy_time_mlp_launch(n->tm, a->time, B, trep, ss, dp, a->drop_path_keep, drop ? 1 : 0, a->seed,
-                                             a->call, a->batch_offset, rpc, stream,
-                                             trep + (size_t)B * (n->cfg.with_time_emb ? n->cfg.time_dim : 1)));
-
-  // ---- drop-path skip.  DropPath (src/models/modules/drop_path.py:15-22, applied at sfnonet.py:330) multiplies the whole
-  //      branch of a trajectory -- transforms, dhconv, inner skip, MLP -- by 0 with the layer's rate; the keep decision is a
-  //      Philox function of (seed, call, layer, trajectory) that the host evaluates here exactly as time_dense_kernel does on
-  //      the device.  A block with dropped trajectories runs its kernels on the kept ones only (per-block intermediates are
-  //      indexed compactly, SdyImgMap) and writes the dropped ones' output a x + d with sdy_affine_copy_stats_launch.
-  //      Only on the default kernel path (fft360 + leg_par + dh_h3 + conv_h3 + mlp_h3); injected decisions (tests) are
-  //      device data, so they run unskipped.  SDY_NO_DROP_SKIP=1 computes everything (A/B: bit-identical results).
-  const bool no_drop_skip = sw().no_drop_skip;
-  const bool skip_allowed = drop && !a->drop_path_keep && !no_drop_skip && B <= SDY_MAP_MAX;
-  auto drop_path_keeps = [&](int layer, int b) {
-    const int bq = b / rpc;
-    const philox4 wd = philox4x32((uint32_t)(b - bq * rpc) + a->batch_offset, 0xFFFFFFFFu, 0x1000u + (uint32_t)layer,
-                                     a->call + (uint32_t)bq, (uint32_t)(a->seed & 0xFFFFFFFFu), (uint32_t)(a->seed >> 32));
-    return wd.x >= n->tm.dp_thr[layer];
+  // one block in this call
+  struct Blk {
+    int i;
+    const BlockPath& P;
+    const BlockW& w;
+    float* dst; long dst_bs;           // the block output (the last block's goes to the head of `cat`)
+    float* z; long z_bs;               // the MLP's input (zt tile-major, or y)
+    double* st_out;                    // the next block's norm0 statistics from this block's MLP epilogue, or nullptr
+    unsigned char perm[SDY_MAP_MAX];   // drop-path skip: perm[0 .. Bp) the kept rows the kernels run on, perm[Bp .. B) the dropped
+    int Bp, nD, Bf;                    // kept rows, dropped rows, rows of the forward transform
+    const unsigned char* rows;         // perm, or nullptr: every row is active, identity map
   };
 
-  sdy_conv_args cv;
-  auto use_w = [&](const DevBuf& b) {
-    cv.wt = b.p;
-    if (c.gemm_mode == 1) {
-      cv.w_h3 = b.h3; cv.w_h3_scale = b.h3_scale;
-      cv.w_frag = b.frag; cv.w_frag_scale = b.frag_scale;
-    }
-  };
-  auto conv_reset = [&]() {
-    std::memset(&cv, 0, sizeof(cv));
-    cv.B = B; cv.HW = HW; cv.seed = a->seed; cv.call = a->call; cv.batch_offset = a->batch_offset; cv.rows_per_call = rpc;
-  };
+  SfnoCall(sdy_sfno* n_, const sdy_sfno_fwd_args* a_, hipStream_t s) : n(n_), c(n_->cfg), a(a_), stream(s), B(a_->B) {}
 
-  // ---- encoder (sfnonet.py:609-618,810,824): conv+bias -> GELU -> conv (no bias) -> + pos_embed
-  // The encoder writes to a buffer of its own (xe) and its statistics to `ste`; block 0 works on a copy of the statistics
-  // (sdy_instnorm_from_stats clears what it reads), so that a following forward on the same inputs can restart here.
-  bool have_ste = false;
-  if (reuse) {
-    have_ste = n->enc_has_stats;
-  } else if (n->enc.w) {   // one launch (pair_h3.hip), block 0's norm0 statistics from its epilogue
-    sdy_pair_args pa{};
-    pa.x = cat_in; pa.x_bstride = cat_bs; pa.w = n->enc.w; pa.w1_scale = n->enc.s1; pa.w2_scale = n->enc.s2;
-    pa.b1 = n->e0b.p; pa.out = xe; pa.out_bstride = (long)E * HW;
-    if (c.pos_embed) { pa.add = n->pos.p; pa.add_bstride = 0; }
-    pa.B = Be; pa.Cin = Cin; pa.hidden = E; pa.Cout = E; pa.HW = HW;
-    SDY_HIP_TRY(hipMemsetAsync(ste, 0, (size_t)Be * E * 2 * sizeof(double), stream));
-    pa.stats = ste; have_ste = true;
-    SDY_STAGE_N(ST_ENC_PAIR, Be, sdy_pair_h3(&pa, stream));
-  } else {
-  conv_reset();
-  cv.x = cat_in; cv.x_bstride = cat_bs; use_w(n->e0w); cv.ldw = E; cv.out = xa; cv.out_bstride = (long)E * HW;
-  cv.Cin = Cin; cv.Cout = E; cv.bias = n->e0b.p; cv.act = 1;
-  SDY_STAGE(ST_ENC0, sdy_conv1x1(&cv, stream));
-  conv_reset();
-  cv.x = xa; cv.x_bstride = (long)E * HW; use_w(n->e2w); cv.ldw = E; cv.out = xe; cv.out_bstride = (long)E * HW;
-  cv.Cin = E; cv.Cout = E;
-  if (c.pos_embed) { cv.add = n->pos.p; cv.add_bstride = 0; cv.add_mode = 2; }
-  // block 0's norm0 statistics from this convolution's epilogue (persistent kernel only): no pass over its output
-  if (cv.w_frag && sdy_conv256_h3_supported(E, E)) {
-    SDY_HIP_TRY(hipMemsetAsync(ste, 0, (size_t)B * E * 2 * sizeof(double), stream));
-    cv.stats = ste; have_ste = true;
-  }
-  SDY_STAGE(ST_ENC2, sdy_conv1x1(&cv, stream));
-  }
-  // (a forward that ran the encoder on the shared rows only leaves nothing a later reuse_encoder forward of B rows could take)
-  n->enc_ws = enc_once ? nullptr : ws; n->enc_B = B; n->enc_has_stats = have_ste;
-  if (have_ste) {   // every stacked call starts from the statistics of the rows it shares
-    for (int b0 = 0; b0 < B; b0 += Be)
-      SDY_HIP_TRY(hipMemcpyAsync(st0 + (size_t)b0 * E * 2, ste, (size_t)Be * E * 2 * sizeof(double), hipMemcpyDeviceToDevice, stream));
-    have_st0 = true;
-  }
-
-  float* cur = xe;
-  float* nxt = xa;
-  const int ilv = spec_ilv(c);   // channel order of Xf / Cs / Cs2 inside this forward
-  for (int i = 0; i < L; ++i) {
-    const BlockW& bw = n->blk[i];
-    const sdy_sht_plan* pin = (i == 0) ? n->plan_data : n->plan_lg;
-    const sdy_sht_plan* pout = (i == L - 1) ? n->plan_data : n->plan_lg;
-    const bool scale_residual = pin != pout;  // s2convolutions.py:79-83
-    const float pm = (drop && c.dropout_mlp > 0.f) ? c.dropout_mlp : 0.f;
-    const bool no_fused = sw().no_fused_mlp;
-    const bool fused_mlp = bw.mlp && !no_fused;   // (injected masks too: sdy_mlp_args.keep_hidden / keep_out)
-    // The block's residual is norm0(x) (or its SHT round trip when the grids differ).  With the fused MLP kernel the
-    // normalised tensor is never materialised: its two consumers (inner skip, final residual add) apply a*x + d to `cur`.
-    const bool lazy_norm = fused_mlp && !scale_residual;
-    // norm0 + time scale/shift folded into a*x+d (sfnonet.py:292,298-299)
-    if (have_st0)   // statistics were accumulated by the previous block's MLP epilogue: no pass over `cur`
-      SDY_STAGE(ST_NORM_COEFFS, sdy_instnorm_from_stats(st0, B, E, HW, bw.n0w.p, bw.n0b.p,
-                                                        c.with_time_emb ? ss + (size_t)i * 2 * E : nullptr, (long)L * 2 * E,
-                                                        1e-6f, ca, cd, stream));
-    else
-      SDY_STAGE(ST_NORM_COEFFS, sdy_instnorm_coeffs_launch(cur, B, E, HW, bw.n0w.p, bw.n0b.p,
-                                                           c.with_time_emb ? ss + (size_t)i * 2 * E : nullptr,
-                                                           (long)L * 2 * E, 1e-6f, ca, cd, stream));
-    have_st0 = false;
-    // SpectralConvS2.forward (s2convolutions.py:158-193)
-    const bool polar_in = plan_polar_ok(pin, E), polar_out = plan_polar_ok(pout, E);
-    const bool tiled_in = plan_tiled_ok(pin, E, ilv), tiled_out = plan_tiled_ok(pout, E, ilv);   // Xf / Yf tile-major (fft.h)
-    // Cs / Cs2 tile-major by order too (analysis stores and synthesis loads become contiguous tiles; dh_h3 reads and writes
-    // 256-byte pieces instead of 2 KB rows, which it does not notice: it is matrix / issue bound).
-    const bool cs_tiled = tiled_in && tiled_out && bw.fw.frag && pin->lmax == pout->lmax && pin->mtr == pout->mtr;
-    const bool frag_conv = c.gemm_mode == 1 && bw.skw.frag && sdy_conv256_h3_supported(E, E);
-    const bool stats1 = frag_conv;   // norm1 statistics from the inner-skip convolution's epilogue
-    // The tensor between the inner skip and the fused MLP has exactly one producer and one consumer, both walking 64-pixel
-    // tiles: it is stored TILE-MAJOR (a tile = one contiguous 64 KB block for the stores of one and the loads of the other).
-    const bool z_tiled = stats1 && fused_mlp;
-    const long zt_bs = (long)((HW + 63) / 64) * E * 64;
-    float* dst = (i == L - 1) ? cat : nxt;
-    const long dst_bs = (i == L - 1) ? cat_bs : (long)E * HW;
-    const long cur_bs = (cur == cat) ? cat_bs : (long)E * HW;
-
-    // drop-path skip: the rows this block's kernels run on (Bp of them: perm[0 .. Bp) are their batch rows) and the dropped
-    // ones (perm[Bp .. B)).  Two forms:
-    //  * the residual is a x + d of the block input (lazy_norm: every block between the first and the last, or all of them when
-    //    the data grid is the Gauss grid): NOTHING of the block runs for a dropped row, its output is the affine copy;
-    //  * the residual is the SHT round trip of a x + d (scale_residual, s2convolutions.py:79-83: the first / last block on an
-    //    equiangular data grid): forward transform and the residual's inverse transform run on all rows, in the ORDER perm
-    //    (kept rows first -- a row's transform does not depend on its place in the batch), so that the dhconv, the second
-    //    inverse transform, the inner skip and the MLP work on the leading Bp rows of tensors in that order; a dropped row's
-    //    output is the copy of its residual.
-    unsigned char perm[SDY_MAP_MAX];
-    int Bp = B, nD = 0;
-    if (skip_allowed && n->tm.dp_rate[i] > 0.f && fused_mlp && z_tiled && cs_tiled) {
-      unsigned char drp[SDY_MAP_MAX];
-      Bp = 0;
-      for (int b = 0; b < B; ++b) {
-        if (drop_path_keeps(i, b)) perm[Bp++] = (unsigned char)b;
-        else drp[nD++] = (unsigned char)b;
-      }
-      for (int k = 0; k < nD; ++k) perm[Bp + k] = drp[k];
+  // everything that refuses the call, before anything is enqueued
+  int check() {
+    if (c.with_time_emb && !a->time) return SDY_ERR_ARG;
+    if (a->ws_floats < w.total) return SDY_ERR_WORKSPACE;
+    if (reuse && (n->enc_ws != ws || n->enc_B != B)) return SDY_ERR_STATE;   // no previous forward on this workspace / batch
+    int ctot = 0;
+    for (int i = 0; i < 3; ++i)
+      if (a->in[i] && a->in_chans[i] > 0) { srcs[ns] = a->in[i]; chans[ns] = a->in_chans[i]; ctot += a->in_chans[i]; ++ns; }
+    // the generated group (forward conditioning) joins the list at its position
+    if (gen) {
+      if (a->gen_chans <= 0 || !a->gen_coef || a->gen_pos < 0 || a->gen_pos > ns) return SDY_ERR_ARG;
+      if (reuse || shared) return SDY_ERR_ARG;     // its values change with every call
+      for (int i = ns; i > a->gen_pos; --i) { srcs[i] = srcs[i - 1]; chans[i] = chans[i - 1]; }
+      srcs[a->gen_pos] = a->gen_src; chans[a->gen_pos] = a->gen_chans; ctot += a->gen_chans; ++ns;
     }
-    const unsigned char* rows = nD > 0 ? perm : nullptr;   // nullptr: every row is active, identity map
-    const int Bf = scale_residual ? B : Bp;                // rows of the forward transform
-
-    if (Bf > 0) {
-      SDY_STAGE_N(ST_FFT_FWD, Bf, sdy_fft_launch_fwd(pin->fft, cur, ca, cd, (scale_residual || lazy_norm) ? nullptr : xn, Xf, Bf, E,
-                                                     pin->nlat, pin->mtr, tiled_in ? 2 : ilv, polar_in ? pin->d_mcut : nullptr, stream, rows,
-                                                     (i == 0 && enc_once) ? Be : 0));
-      SDY_STAGE_N(ST_LEG_FWD, Bf, legendre_fwd_impl(pin, Xf, Cs, Bf, E, polar_in, stream, tiled_in, cs_tiled));
-      if (scale_residual) {  // residual = inverse_transform(forward_transform(x)); in the order `perm` when rows were dropped
-        SDY_STAGE(ST_LEG_INV, legendre_inv_impl(pout, Cs, Xf, B, E, polar_out, stream, tiled_out, cs_tiled));
-        SDY_STAGE(ST_FFT_INV, sdy_fft_launch_inv(pout->fft, Xf, nullptr, xn, B, E, pout->nlat, pout->mtr, tiled_out ? 2 : ilv,
-                                                 polar_out ? pout->d_mcut : nullptr, stream));
-      }
-    }
-    if (Bp > 0) {
-      if (bw.fw.frag)
-        SDY_STAGE_N(ST_DHCONV, Bp, sdy_dh_h3_launch(Cs, bw.fw.frag, bw.fw.frag_scale, Cs2, c.lmax, pin->mtr, Bp, ilv, (hipStream_t)stream,
-                                                    cs_tiled ? 1 : 0, Bf));
-      else if (c.gemm_mode == 1)
-        SDY_STAGE(ST_DHCONV, sdy_dhconv_h3(Cs, bw.fw.h3, bw.fw.h3_scale, Cs2, c.lmax, pin->mtr, B, E, E, stream));
-      else
-        SDY_STAGE(ST_DHCONV, sdy_dhconv(Cs, bw.fw.p, Cs2, c.lmax, pin->mtr, B, E, E, stream));
-      // grid-changing block with the inner skip folded into the dhconv weights (skip_foldable): y = filter + skip + both biases
-      // (the packed dhconv stream of such a block HOLDS the skip: running the convolution as well would count it twice)
-      if (bw.skip_folded && !(scale_residual && bw.fw.frag && bw.fbs.set)) return SDY_ERR_STATE;
-      const bool folded = bw.skip_folded;
-      SDY_STAGE_N(ST_LEG_INV, Bp, legendre_inv_impl(pout, Cs2, Xf, Bp, E, polar_out, stream, tiled_out, cs_tiled));
-      // ... and on the fft360 path with the tile-major conv -> MLP tensor the act itself rides on the inverse FFT's stores
-      // (GELU, tile-major layout, per-ring norm1 statistics): no pass over y at all
-      const bool act_in_fft = folded && tiled_out && z_tiled;
-      if (act_in_fft) {
-        double* part = reinterpret_cast<double*>(ws + w.sp);
-        SDY_STAGE_N(ST_FFT_INV, Bp, sdy_fft360_launch_inv(pout->fft, Xf, bw.fbs.p, nullptr, Bp, E, pout->nlat, pout->mtr, 2,
-                                                          polar_out ? pout->d_mcut : nullptr, stream, ws + w.zt, zt_bs, part));
-        SDY_STAGE_N(ST_NORM_COEFFS, Bp, sdy_instnorm_from_partials_launch(part, pout->nlat, Bp, E, HW, bw.n1w.p, bw.n1b.p, 1e-6f, ca1,
-                                                                          cd1, stream));
-      } else
-      SDY_STAGE_N(ST_FFT_INV, Bp, sdy_fft_launch_inv(pout->fft, Xf, folded ? bw.fbs.p : bw.fb.p, y, Bp, E, pout->nlat, pout->mtr,
-                                                     tiled_out ? 2 : ilv, polar_out ? pout->d_mcut : nullptr, stream));
-      if (act_in_fft) {
-      } else if (folded) {
-        // x = GELU(y): the 256 -> 256 convolution has become a matrix addition at load time; norm1 statistics from this pass
-        float* zo = z_tiled ? ws + w.zt : y;
-        SDY_STAGE_N(ST_SKIP_GELU, Bp, sdy_gelu_stats_launch(y, (long)E * HW, zo, z_tiled ? zt_bs : (long)E * HW, z_tiled ? 1 : 0, st1,
-                                                           Bp, E, HW, stream));
-        SDY_STAGE_N(ST_NORM_COEFFS, Bp, sdy_instnorm_from_stats(st1, Bp, E, HW, bw.n1w.p, bw.n1b.p, nullptr, 0, 1e-6f, ca1, cd1, stream));
-      } else {
-      // x = GELU(y + inner_skip(residual))  (sfnonet.py:303-311), in place over y
-      conv_reset();
-      cv.B = Bp; cv.x_rows = lazy_norm ? rows : nullptr;   // (xn is in the launch's own row order)
-      cv.x = lazy_norm ? cur : xn; cv.x_bstride = lazy_norm ? cur_bs : (long)E * HW;
-      if (lazy_norm) { cv.pa = ca; cv.pd = cd; }
-      use_w(bw.skw); cv.ldw = E; cv.out = y; cv.out_bstride = (long)E * HW;
-      cv.Cin = E; cv.Cout = E; cv.bias = bw.skb.p; cv.add = y; cv.add_bstride = (long)E * HW; cv.add_mode = 1; cv.act = 1; cv.kernel_tag = 3;
-      if (stats1) cv.stats = st1;
-      if (z_tiled) { cv.out = ws + w.zt; cv.out_bstride = zt_bs; cv.out_tiled = 1; }
-      SDY_STAGE_N(ST_SKIP_CONV, Bp, sdy_conv1x1(&cv, stream));
-      // norm1 (sfnonet.py:313-320) folded into the fc1 prologue; its statistics come from the convolution's epilogue
-      if (stats1)
-        SDY_STAGE_N(ST_NORM_COEFFS, Bp, sdy_instnorm_from_stats(st1, Bp, E, HW, bw.n1w.p, bw.n1b.p, nullptr, 0, 1e-6f, ca1, cd1, stream));
-      else
-        SDY_STAGE(ST_NORM_COEFFS, sdy_instnorm_coeffs_launch(y, B, E, HW, bw.n1w.p, bw.n1b.p, nullptr, 0, 1e-6f, ca1, cd1, stream));
-      }
-    }
-    // MLP (layers.py:73-80): fc1 + GELU + dropout
-    const bool stats_next = fused_mlp && i < L - 1;   // the next block's norm0 statistics from this block's epilogue
-    if (Bp == 0) {
-      // (every trajectory dropped: nothing of the branch runs)
-    } else if (fused_mlp) {
-      // fc1 + GELU + dropout + fc2 + dropout + DropPath + residual in one launch: the hidden activation stays on the CU
-      sdy_mlp_args ma;
-      std::memset(&ma, 0, sizeof(ma));
-      ma.x = y; ma.x_bstride = (long)E * HW; ma.pa = ca1; ma.pd = cd1;
-      if (z_tiled) { ma.x = ws + w.zt; ma.x_bstride = zt_bs; ma.x_tiled = 1; }
-      ma.w = bw.mlp; ma.w1_scale = bw.mlp_s1; ma.w2_scale = bw.mlp_s2; ma.b1 = bw.b1.p; ma.b2 = bw.b2.p;
-      ma.out = dst; ma.out_bstride = dst_bs;
-      if (lazy_norm) { ma.add = cur; ma.add_bstride = cur_bs; ma.add_a = ca; ma.add_d = cd; }
-      else { ma.add = xn; ma.add_bstride = (long)E * HW; ma.add_by_launch_row = rows ? 1 : 0; }
-      ma.B = Bp; ma.out_rows = rows; ma.E = E; ma.hidden = Hd; ma.HW = HW;
-      ma.drop_p = pm; ma.seed = a->seed; ma.call = a->call; ma.stream_fc1 = 2u * i; ma.stream_fc2 = 2u * i + 1u;
-      ma.batch_offset = a->batch_offset; ma.rows_per_call = rpc;
-      if (drop && n->tm.dp_rate[i] > 0.f) ma.batch_scale = dp + (size_t)i * B;  // dp is laid out [layer][b]
-      if (pm > 0.f && a->keep_masks) {   // tests: the reference's recorded masks drive the fused kernel's INJECT instantiation
-        ma.keep_hidden = static_cast<const float*>(a->keep_masks[2 * i]);
-        ma.keep_out = static_cast<const float*>(a->keep_masks[2 * i + 1]);
-      }
-      if (stats_next) ma.stats = st0;
-      SDY_STAGE_N(pm > 0.f ? ST_MLP_FUSED_DROP : ST_MLP_FUSED, Bp, sdy_mlp_h3(&ma, stream));
-    } else {
-      conv_reset();
-      cv.x = y; cv.x_bstride = (long)E * HW; use_w(bw.w1); cv.ldw = Hd; cv.out = hid; cv.out_bstride = (long)Hd * HW;
-      cv.Cin = E; cv.Cout = Hd; cv.pa = ca1; cv.pd = cd1; cv.bias = bw.b1.p; cv.act = 1; cv.kernel_tag = 1;
-      cv.drop_p = pm; cv.stream_id = 2u * i; cv.keep_mask = (pm > 0.f && a->keep_masks) ? a->keep_masks[2 * i] : nullptr;
-      SDY_STAGE(ST_FC1, sdy_conv1x1(&cv, stream));
-      // fc2 + dropout, DropPath, + residual (sfnonet.py:325-335)
-      conv_reset();
-      cv.x = hid; cv.x_bstride = (long)Hd * HW; use_w(bw.w2); cv.ldw = E; cv.out = dst; cv.out_bstride = dst_bs;
-      cv.Cin = Hd; cv.Cout = E; cv.bias = bw.b2.p; cv.kernel_tag = 2;
-      cv.drop_p = pm; cv.stream_id = 2u * i + 1u; cv.keep_mask = (pm > 0.f && a->keep_masks) ? a->keep_masks[2 * i + 1] : nullptr;
-      if (drop && n->tm.dp_rate[i] > 0.f) cv.batch_scale = dp + (size_t)i * B;  // dp is laid out [layer][b]
-      cv.add = xn; cv.add_bstride = (long)E * HW; cv.add_mode = 2;
-      SDY_STAGE(ST_FC2, sdy_conv1x1(&cv, stream));
-    }
-    if (nD > 0) {   // dropped trajectories: block output = the residual; their share of the next block's statistics
-      if (lazy_norm)
-        SDY_STAGE_N(ST_DROP_COPY, nD, sdy_affine_copy_stats_launch(cur, cur_bs, ca, cd, dst, dst_bs, stats_next ? st0 : nullptr, E, HW,
-                                                                   perm + Bp, nD, stream));
-      else
-        SDY_STAGE_N(ST_DROP_COPY, nD, sdy_affine_copy_stats_launch(xn, (long)E * HW, nullptr, nullptr, dst, dst_bs,
-                                                                   stats_next ? st0 : nullptr, E, HW, perm + Bp, nD, stream, Bp));
-    }
-    if (stats_next) have_st0 = true;
-    cur = dst;
-    nxt = (dst == xa) ? xb : xa;
-  }
-
-  // ---- decoder (sfnonet.py:734-744,831-837)
-  if (n->dec.w) {
-    sdy_pair_args pa{};
-    pa.x = cat; pa.x_bstride = cat_bs; pa.w = n->dec.w; pa.w1_scale = n->dec.s1; pa.w2_scale = n->dec.s2;
-    pa.b1 = n->d0b.p; pa.out = a->out; pa.out_bstride = (long)c.out_chans * HW;
-    pa.B = B; pa.Cin = n->decC; pa.hidden = E; pa.Cout = c.out_chans; pa.HW = HW;
-    SDY_STAGE(ST_DEC_PAIR, sdy_pair_h3(&pa, stream));
+    if (ns == 0 || ctot != c.in_chans) return SDY_ERR_SHAPE;
+    if (a->rows_per_call < 0 || (a->rows_per_call > 0 && B % a->rows_per_call)) return SDY_ERR_ARG;
+    if (shared && (reuse || rpc >= B)) return SDY_ERR_ARG;
     return SDY_OK;
   }
-  float* dh = xa;
-  conv_reset();
-  cv.x = cat; cv.x_bstride = cat_bs; use_w(n->d0w); cv.ldw = E;
-  cv.out = dh; cv.out_bstride = (long)E * HW; cv.Cin = n->decC; cv.Cout = E; cv.bias = n->d0b.p; cv.act = 1;
-  SDY_STAGE(ST_DEC0, sdy_conv1x1(&cv, stream));
-  conv_reset();
-  cv.x = dh; cv.x_bstride = (long)E * HW; use_w(n->d2w); cv.ldw = n->ldo; cv.out = a->out;
-  cv.out_bstride = (long)c.out_chans * HW; cv.Cin = E; cv.Cout = c.out_chans;
-  SDY_STAGE(ST_DEC2, sdy_conv1x1(&cv, stream));
-  return SDY_OK;
+
+  // input concat (BaseModel.concat_condition_if_needed, _base_model.py:166-192) into the tail of the big-skip buffer:
+  // cat = [ block output (E) | inputs (Cin) ]  (sfnonet.py:804-805,831-832)
+  int inputs() {
+    // (a forward that overwrites the inputs invalidates the stored encoder output until its own encoder launch has been
+    //  enqueued: an early error return must not leave a handle that claims a valid one)
+    if (!reuse) n->enc_ws = nullptr;
+    SDY_HIP_TRY(hipMemsetAsync(st1, 0, (size_t)B * E * 2 * sizeof(double), stream));
+    SDY_HIP_TRY(hipMemsetAsync(st0, 0, (size_t)B * E * 2 * sizeof(double), stream));
+    if (gen) {
+      SdyConcatGen g;
+      g.gen = a->gen_pos; g.coef = a->gen_coef; g.noise = a->gen_noise;
+      g.seed = a->seed; g.call = a->call; g.batch_offset = a->batch_offset; g.rows_per_call = rpc;
+      SDY_STAGE(ST_CONCAT, sdy_concat_gen_launch(srcs, chans, ns, g, cat_in, cat_bs, B, HW, stream));
+    } else if (!reuse) {   // (reuse_encoder: the inputs already sit in the tail of `cat` -- no block writes there)
+      SDY_STAGE(ST_CONCAT, sdy_concat_launch(srcs, chans, ns, cat_in, cat_bs, B, HW, stream, shared ? rpc : 0));
+    }
+    return SDY_OK;
+  }
+
+  // time embedding + per-layer (scale|shift) + drop-path scales
+  int time_mlp() {
+    SDY_STAGE(ST_TIME_MLP, sdy_time_mlp_launch(n->tm, a->time, B, trep, ss, dp, a->drop_path_keep, drop ? 1 : 0, a->seed, a->call,
+                                               a->batch_offset, rpc, stream, trep + (size_t)B * (c.with_time_emb ? c.time_dim : 1)));
+    return SDY_OK;
+  }
+
+  // a 1 x 1 convolution of this call over `rows` batch rows, on the kernel the weights `wb` were packed for
+  sdy_conv_args conv_args(const DevBuf& wb, int rows) const {
+    sdy_conv_args cv;
+    std::memset(&cv, 0, sizeof(cv));
+    cv.B = rows; cv.HW = HW; cv.seed = a->seed; cv.call = a->call; cv.batch_offset = a->batch_offset; cv.rows_per_call = rpc;
+    cv.wt = wb.p;
+    if (c.gemm_mode == 1) { cv.w_h3 = wb.h3; cv.w_h3_scale = wb.h3_scale; cv.w_frag = wb.frag; cv.w_frag_scale = wb.frag_scale; }
+    return cv;
+  }
+
+  // encoder (sfnonet.py:609-618,810,824): conv+bias -> GELU -> conv (no bias) -> + pos_embed
+  // The encoder writes to a buffer of its own (xe) and its statistics to `ste`; block 0 works on a copy of the statistics
+  // (sdy_instnorm_from_stats clears what it reads), so that a following forward on the same inputs can restart here.
+  int encoder() {
+    bool have_ste = false;
+    if (reuse) {
+      have_ste = n->enc_has_stats;
+    } else if (n->enc.w) {   // one launch (pair_h3.hip), block 0's norm0 statistics from its epilogue
+      sdy_pair_args pa{};
+      pa.x = cat_in; pa.x_bstride = cat_bs; pa.w = n->enc.w; pa.w1_scale = n->enc.s1; pa.w2_scale = n->enc.s2;
+      pa.b1 = n->e0b.p; pa.out = xe; pa.out_bstride = xbs;
+      if (c.pos_embed) { pa.add = n->pos.p; pa.add_bstride = 0; }
+      pa.B = Be; pa.Cin = c.in_chans; pa.hidden = E; pa.Cout = E; pa.HW = HW;
+      SDY_HIP_TRY(hipMemsetAsync(ste, 0, (size_t)Be * E * 2 * sizeof(double), stream));
+      pa.stats = ste; have_ste = true;
+      SDY_STAGE_N(ST_ENC_PAIR, Be, sdy_pair_h3(&pa, stream));
+    } else {
+      sdy_conv_args cv = conv_args(n->e0w, B);
+      cv.x = cat_in; cv.x_bstride = cat_bs; cv.ldw = E; cv.out = xa; cv.out_bstride = xbs;
+      cv.Cin = c.in_chans; cv.Cout = E; cv.bias = n->e0b.p; cv.act = 1;
+      SDY_STAGE(ST_ENC0, sdy_conv1x1(&cv, stream));
+      cv = conv_args(n->e2w, B);
+      cv.x = xa; cv.x_bstride = xbs; cv.ldw = E; cv.out = xe; cv.out_bstride = xbs; cv.Cin = E; cv.Cout = E;
+      if (c.pos_embed) { cv.add = n->pos.p; cv.add_bstride = 0; cv.add_mode = 2; }
+      // block 0's norm0 statistics from this convolution's epilogue (persistent kernel only): no pass over its output
+      if (cv.w_frag && sdy_conv256_h3_supported(E, E)) {
+        SDY_HIP_TRY(hipMemsetAsync(ste, 0, (size_t)B * E * 2 * sizeof(double), stream));
+        cv.stats = ste; have_ste = true;
+      }
+      SDY_STAGE(ST_ENC2, sdy_conv1x1(&cv, stream));
+    }
+    // (a forward that ran the encoder on the shared rows only leaves nothing a later reuse_encoder forward of B rows could take)
+    n->enc_ws = enc_once ? nullptr : ws; n->enc_B = B; n->enc_has_stats = have_ste;
+    if (have_ste) {   // every stacked call starts from the statistics of the rows it shares
+      for (int b0 = 0; b0 < B; b0 += Be)
+        SDY_HIP_TRY(hipMemcpyAsync(st0 + (size_t)b0 * E * 2, ste, (size_t)Be * E * 2 * sizeof(double), hipMemcpyDeviceToDevice,
+                                   stream));
+      cur_stats = st0;
+    }
+    return SDY_OK;
+  }
+
+  int block(int i) {
+    const bool last = i == c.num_layers - 1;
+    Blk k{i, n->path[i], n->blk[i], last ? cat : nxt, last ? cat_bs : xbs};
+    k.z = k.P.z_tiled ? zt : y;
+    k.z_bs = k.P.z_tiled ? zt_bs : xbs;
+    k.st_out = (k.P.fused_mlp && !last) ? st0 : nullptr;
+    SDY_TRY(norm0(k));
+    drop_rows(k);
+    SDY_TRY(spectral(k));
+    if (k.Bp > 0) {   // (every trajectory dropped: nothing of the branch runs)
+      SDY_TRY(inner_skip(k));
+      SDY_TRY(mlp(k));
+    }
+    if (k.nD > 0) SDY_TRY(drop_copy(k));
+    cur_stats = k.st_out;
+    cur = k.dst;
+    nxt = (k.dst == xa) ? xb : xa;
+    return SDY_OK;
+  }
+
+  // norm0 + time scale/shift folded into a*x+d (sfnonet.py:292,298-299)
+  int norm0(const Blk& k) {
+    const float* ssk = c.with_time_emb ? ss + (size_t)k.i * 2 * E : nullptr;
+    const long ss_bs = (long)c.num_layers * 2 * E;
+    if (cur_stats)   // statistics were accumulated by the previous block's MLP epilogue (or the encoder's): no pass over `cur`
+      SDY_STAGE(ST_NORM_COEFFS, sdy_instnorm_from_stats(cur_stats, B, E, HW, k.w.n0w.p, k.w.n0b.p, ssk, ss_bs, 1e-6f, ca, cd, stream));
+    else
+      SDY_STAGE(ST_NORM_COEFFS, sdy_instnorm_coeffs_launch(cur, B, E, HW, k.w.n0w.p, k.w.n0b.p, ssk, ss_bs, 1e-6f, ca, cd, stream));
+    return SDY_OK;
+  }
+
+  // Drop-path skip.  DropPath (src/models/modules/drop_path.py:15-22, applied at sfnonet.py:330) multiplies the whole branch of
+  // a trajectory -- transforms, dhconv, inner skip, MLP -- by 0 with the layer's rate; the keep decision is a Philox function of
+  // (seed, call, layer, trajectory) that the host evaluates here exactly as time_dense_kernel does on the device.  A block with
+  // dropped trajectories runs its kernels on the kept ones only (per-block intermediates are indexed compactly, SdyImgMap) and
+  // writes the dropped ones' output a x + d with sdy_affine_copy_stats_launch.  Only on the default kernel path (fft360 +
+  // leg_par + dh_h3 + conv_h3 + mlp_h3: BlockPath::drop_skip); injected decisions (tests) are device data, so they run
+  // unskipped.  SDY_NO_DROP_SKIP=1 computes everything (A/B: bit-identical results).
+  // The rows this block's kernels run on are perm[0 .. Bp), the dropped ones perm[Bp .. B).  Two forms:
+  //  * the residual is a x + d of the block input (lazy_norm: every block between the first and the last, or all of them when
+  //    the data grid is the Gauss grid): NOTHING of the block runs for a dropped row, its output is the affine copy;
+  //  * the residual is the SHT round trip of a x + d (scale_residual, s2convolutions.py:79-83: the first / last block on an
+  //    equiangular data grid): forward transform and the residual's inverse transform run on all rows, in the ORDER perm
+  //    (kept rows first -- a row's transform does not depend on its place in the batch), so that the dhconv, the second
+  //    inverse transform, the inner skip and the MLP work on the leading Bp rows of tensors in that order; a dropped row's
+  //    output is the copy of its residual.
+  void drop_rows(Blk& k) const {
+    k.Bp = B;
+    k.nD = 0;
+    if (drop && !a->drop_path_keep && B <= SDY_MAP_MAX && n->tm.dp_rate[k.i] > 0.f && k.P.drop_skip) {
+      unsigned char drp[SDY_MAP_MAX];
+      k.Bp = 0;
+      for (int b = 0; b < B; ++b) {
+        const int bq = b / rpc;
+        const philox4 wd = philox4x32((uint32_t)(b - bq * rpc) + a->batch_offset, 0xFFFFFFFFu, 0x1000u + (uint32_t)k.i,
+                                      a->call + (uint32_t)bq, (uint32_t)(a->seed & 0xFFFFFFFFu), (uint32_t)(a->seed >> 32));
+        if (wd.x >= n->tm.dp_thr[k.i]) k.perm[k.Bp++] = (unsigned char)b;
+        else drp[k.nD++] = (unsigned char)b;
+      }
+      for (int j = 0; j < k.nD; ++j) k.perm[k.Bp + j] = drp[j];
+    }
+    k.rows = k.nD > 0 ? k.perm : nullptr;
+    k.Bf = k.P.scale_residual ? B : k.Bp;
+  }
+
+  // SpectralConvS2.forward (s2convolutions.py:158-193): forward transform (+ the residual's round trip), dhconv, inverse
+  // transform + filter bias
+  int spectral(const Blk& k) {
+    const BlockPath& P = k.P;
+    const sdy_sht_plan *pin = P.in.plan, *pout = P.out.plan;
+    if (k.Bf > 0) {
+      // (the forward FFT stores the residual norm0(x) unless it is the round trip below or its consumers apply a*x + d)
+      float* xn_out = (P.scale_residual || P.lazy_norm) ? nullptr : xn;
+      SDY_STAGE_N(ST_FFT_FWD, k.Bf, sdy_fft_launch_fwd(pin->fft, cur, ca, cd, xn_out, Xf, k.Bf, E, pin->nlat, pin->mtr, P.in.ilv,
+                                                       P.in.mcut, stream, k.rows, (k.i == 0 && enc_once) ? Be : 0));
+      SDY_STAGE_N(ST_LEG_FWD, k.Bf, legendre_fwd_impl(pin, Xf, Cs, k.Bf, E, P.in.polar, stream, P.in.tiled, P.cs_tiled));
+      if (P.scale_residual) {  // residual = inverse_transform(forward_transform(x)); in the order `perm` when rows were dropped
+        SDY_STAGE(ST_LEG_INV, legendre_inv_impl(pout, Cs, Xf, B, E, P.out.polar, stream, P.out.tiled, P.cs_tiled));
+        SDY_STAGE(ST_FFT_INV, sdy_fft_launch_inv(pout->fft, Xf, nullptr, xn, B, E, pout->nlat, pout->mtr, P.out.ilv, P.out.mcut,
+                                                 stream));
+      }
+    }
+    if (k.Bp == 0) return SDY_OK;
+    if (P.dh == DH_FOLDED || P.dh == DH_FRAG)
+      SDY_STAGE_N(ST_DHCONV, k.Bp, sdy_dh_h3_launch(Cs, k.w.fw.frag, k.w.fw.frag_scale, Cs2, c.lmax, pin->mtr, k.Bp, ilv, stream,
+                                                    P.cs_tiled ? 1 : 0, k.Bf));
+    else if (P.dh == DH_GEMM_H3)
+      SDY_STAGE(ST_DHCONV, sdy_dhconv_h3(Cs, k.w.fw.h3, k.w.fw.h3_scale, Cs2, c.lmax, pin->mtr, B, E, E, stream));
+    else
+      SDY_STAGE(ST_DHCONV, sdy_dhconv(Cs, k.w.fw.p, Cs2, c.lmax, pin->mtr, B, E, E, stream));
+    SDY_STAGE_N(ST_LEG_INV, k.Bp, legendre_inv_impl(pout, Cs2, Xf, k.Bp, E, P.out.polar, stream, P.out.tiled, P.cs_tiled));
+    // grid-changing block with the inner skip folded into the dhconv weights (skip_foldable): y = filter + skip + both biases
+    // ... and on the fft360 path with the tile-major conv -> MLP tensor the act itself rides on the inverse FFT's stores
+    // (GELU, tile-major layout, per-ring norm1 statistics): no pass over y at all
+    const float* bias = P.dh == DH_FOLDED ? k.w.fbs.p : k.w.fb.p;
+    if (P.skip == BlockPath::SKIP_IN_FFT)
+      SDY_STAGE_N(ST_FFT_INV, k.Bp, sdy_fft360_launch_inv(pout->fft, Xf, bias, nullptr, k.Bp, E, pout->nlat, pout->mtr, P.out.ilv,
+                                                          P.out.mcut, stream, zt, zt_bs, sp));
+    else
+      SDY_STAGE_N(ST_FFT_INV, k.Bp, sdy_fft_launch_inv(pout->fft, Xf, bias, y, k.Bp, E, pout->nlat, pout->mtr, P.out.ilv,
+                                                       P.out.mcut, stream));
+    return SDY_OK;
+  }
+
+  // x = GELU(y + inner_skip(residual)) (sfnonet.py:303-311) into the MLP's input, and norm1's coefficients
+  int inner_skip(const Blk& k) {
+    const BlockPath& P = k.P;
+    const BlockW& bw = k.w;
+    if (P.skip == BlockPath::SKIP_IN_FFT) {   // (the inverse FFT stored x and its per-ring statistics)
+      SDY_STAGE_N(ST_NORM_COEFFS, k.Bp, sdy_instnorm_from_partials_launch(sp, P.out.plan->nlat, k.Bp, E, HW, bw.n1w.p, bw.n1b.p,
+                                                                          1e-6f, ca1, cd1, stream));
+      return SDY_OK;
+    }
+    if (P.skip == BlockPath::SKIP_GELU) {
+      // x = GELU(y): the 256 -> 256 convolution has become a matrix addition at load time; norm1 statistics from this pass
+      SDY_STAGE_N(ST_SKIP_GELU, k.Bp, sdy_gelu_stats_launch(y, xbs, k.z, k.z_bs, P.z_tiled ? 1 : 0, st1, k.Bp, E, HW, stream));
+    } else {   // in place over y
+      sdy_conv_args cv = conv_args(bw.skw, k.Bp);
+      cv.x_rows = P.lazy_norm ? k.rows : nullptr;   // (xn is in the launch's own row order)
+      cv.x = P.lazy_norm ? cur : xn; cv.x_bstride = xbs;
+      if (P.lazy_norm) { cv.pa = ca; cv.pd = cd; }
+      cv.ldw = E; cv.out = k.z; cv.out_bstride = k.z_bs; cv.out_tiled = P.z_tiled ? 1 : 0;
+      cv.Cin = E; cv.Cout = E; cv.bias = bw.skb.p; cv.add = y; cv.add_bstride = xbs; cv.add_mode = 1; cv.act = 1; cv.kernel_tag = 3;
+      if (P.stats1) cv.stats = st1;
+      SDY_STAGE_N(ST_SKIP_CONV, k.Bp, sdy_conv1x1(&cv, stream));
+    }
+    // norm1 (sfnonet.py:313-320) folded into the fc1 prologue; its statistics come from the pass that produced x
+    if (P.skip == BlockPath::SKIP_GELU || P.stats1)
+      SDY_STAGE_N(ST_NORM_COEFFS, k.Bp, sdy_instnorm_from_stats(st1, k.Bp, E, HW, bw.n1w.p, bw.n1b.p, nullptr, 0, 1e-6f, ca1, cd1,
+                                                                stream));
+    else
+      SDY_STAGE(ST_NORM_COEFFS, sdy_instnorm_coeffs_launch(y, B, E, HW, bw.n1w.p, bw.n1b.p, nullptr, 0, 1e-6f, ca1, cd1, stream));
+    return SDY_OK;
+  }
+
+  // MLP (layers.py:73-80): fc1 + GELU + dropout, then fc2 + dropout, DropPath, + residual (sfnonet.py:325-335)
+  int mlp(const Blk& k) {
+    const BlockW& bw = k.w;
+    const int i = k.i, Hd = c.mlp_hidden;
+    const float* dps = (drop && n->tm.dp_rate[i] > 0.f) ? dp + (size_t)i * B : nullptr;   // dp is laid out [layer][b]
+    // tests: the reference's recorded masks drive the dropout (the fused kernel's INJECT instantiation)
+    const float* keep1 = (pm > 0.f && a->keep_masks) ? a->keep_masks[2 * i] : nullptr;
+    const float* keep2 = (pm > 0.f && a->keep_masks) ? a->keep_masks[2 * i + 1] : nullptr;
+    if (k.P.fused_mlp) {   // all in one launch: the hidden activation stays on the CU
+      sdy_mlp_args ma;
+      std::memset(&ma, 0, sizeof(ma));
+      ma.x = k.z; ma.x_bstride = k.z_bs; ma.x_tiled = k.P.z_tiled ? 1 : 0; ma.pa = ca1; ma.pd = cd1;
+      ma.w = bw.mlp; ma.w1_scale = bw.mlp_s1; ma.w2_scale = bw.mlp_s2; ma.b1 = bw.b1.p; ma.b2 = bw.b2.p;
+      ma.out = k.dst; ma.out_bstride = k.dst_bs;
+      if (k.P.lazy_norm) { ma.add = cur; ma.add_bstride = xbs; ma.add_a = ca; ma.add_d = cd; }
+      else { ma.add = xn; ma.add_bstride = xbs; ma.add_by_launch_row = k.rows ? 1 : 0; }
+      ma.B = k.Bp; ma.out_rows = k.rows; ma.E = E; ma.hidden = Hd; ma.HW = HW;
+      ma.drop_p = pm; ma.seed = a->seed; ma.call = a->call; ma.stream_fc1 = 2u * i; ma.stream_fc2 = 2u * i + 1u;
+      ma.batch_offset = a->batch_offset; ma.rows_per_call = rpc;
+      ma.batch_scale = dps; ma.keep_hidden = keep1; ma.keep_out = keep2; ma.stats = k.st_out;
+      SDY_STAGE_N(pm > 0.f ? ST_MLP_FUSED_DROP : ST_MLP_FUSED, k.Bp, sdy_mlp_h3(&ma, stream));
+      return SDY_OK;
+    }
+    sdy_conv_args cv = conv_args(bw.w1, B);
+    cv.x = y; cv.x_bstride = xbs; cv.ldw = Hd; cv.out = hid; cv.out_bstride = (long)Hd * HW;
+    cv.Cin = E; cv.Cout = Hd; cv.pa = ca1; cv.pd = cd1; cv.bias = bw.b1.p; cv.act = 1; cv.kernel_tag = 1;
+    cv.drop_p = pm; cv.stream_id = 2u * i; cv.keep_mask = keep1;
+    SDY_STAGE(ST_FC1, sdy_conv1x1(&cv, stream));
+    cv = conv_args(bw.w2, B);
+    cv.x = hid; cv.x_bstride = (long)Hd * HW; cv.ldw = E; cv.out = k.dst; cv.out_bstride = k.dst_bs;
+    cv.Cin = Hd; cv.Cout = E; cv.bias = bw.b2.p; cv.kernel_tag = 2;
+    cv.drop_p = pm; cv.stream_id = 2u * i + 1u; cv.keep_mask = keep2; cv.batch_scale = dps;
+    cv.add = xn; cv.add_bstride = xbs; cv.add_mode = 2;
+    SDY_STAGE(ST_FC2, sdy_conv1x1(&cv, stream));
+    return SDY_OK;
+  }
+
+  // dropped trajectories: block output = the residual; their share of the next block's statistics
+  int drop_copy(const Blk& k) {
+    if (k.P.lazy_norm)
+      SDY_STAGE_N(ST_DROP_COPY, k.nD, sdy_affine_copy_stats_launch(cur, xbs, ca, cd, k.dst, k.dst_bs, k.st_out, E, HW,
+                                                                   k.perm + k.Bp, k.nD, stream));
+    else
+      SDY_STAGE_N(ST_DROP_COPY, k.nD, sdy_affine_copy_stats_launch(xn, xbs, nullptr, nullptr, k.dst, k.dst_bs, k.st_out, E, HW,
+                                                                   k.perm + k.Bp, k.nD, stream, k.Bp));
+    return SDY_OK;
+  }
+
+  // decoder (sfnonet.py:734-744,831-837)
+  int decoder() {
+    if (n->dec.w) {
+      sdy_pair_args pa{};
+      pa.x = cat; pa.x_bstride = cat_bs; pa.w = n->dec.w; pa.w1_scale = n->dec.s1; pa.w2_scale = n->dec.s2;
+      pa.b1 = n->d0b.p; pa.out = a->out; pa.out_bstride = (long)c.out_chans * HW;
+      pa.B = B; pa.Cin = n->decC; pa.hidden = E; pa.Cout = c.out_chans; pa.HW = HW;
+      SDY_STAGE(ST_DEC_PAIR, sdy_pair_h3(&pa, stream));
+      return SDY_OK;
+    }
+    sdy_conv_args cv = conv_args(n->d0w, B);
+    cv.x = cat; cv.x_bstride = cat_bs; cv.ldw = E;
+    cv.out = xa; cv.out_bstride = xbs; cv.Cin = n->decC; cv.Cout = E; cv.bias = n->d0b.p; cv.act = 1;
+    SDY_STAGE(ST_DEC0, sdy_conv1x1(&cv, stream));
+    cv = conv_args(n->d2w, B);
+    cv.x = xa; cv.x_bstride = xbs; cv.ldw = n->ldo; cv.out = a->out; cv.out_bstride = (long)c.out_chans * HW;
+    cv.Cin = E; cv.Cout = c.out_chans;
+    SDY_STAGE(ST_DEC2, sdy_conv1x1(&cv, stream));
+    return SDY_OK;
+  }
+};
+}  // namespace
+
+extern "C" int sdy_sfno_forward(sdy_sfno* n, const sdy_sfno_fwd_args* a, void* stream) {
+  if (!n || !a || !a->out || !a->ws || a->B <= 0) return SDY_ERR_ARG;
+  SDY_TRY(sdy_sfno_ready(n));
+  SfnoCall f(n, a, (hipStream_t)stream);
+  SDY_TRY(f.check());
+  SDY_TRY(f.inputs());
+  SDY_TRY(f.time_mlp());
+  SDY_TRY(f.encoder());
+  for (int i = 0; i < n->cfg.num_layers; ++i) SDY_TRY(f.block(i));
+  return f.decoder();
 }

@@ -11,6 +11,7 @@ struct SdyFftDesc {
   const float* pw; // dev [n+1][2]  exp(-2*pi*i*m/nlon)
   int guard_f16;   // the consumer of the forward transform stages it as fp16 (split-precision Legendre kernels): fft360 raises
                    // SDY_FLAG_F16_RANGE for the folded analysis kernel, which has no register left for a tracker of its own
+  int fft360;      // n = 180 may take the 360-point kernels (fft360.hip); 0 keeps the generic ones (set by the plan)
 };
 
 // Polar cut-off (fused forward only): for latitude ring k only the orders m < mcut[k] are written (forward) / read (inverse);
