@@ -506,6 +506,24 @@ int sdy_profile_read(double* total_ms, long* launches, int n);   /* arrays of n 
  * the drop-path skip a block's kernels run on the trajectories its DropPath draw keeps). */
 int sdy_profile_read_rows(double* total_ms, long* launches, long* rows, int n);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Relay hand-over between processes by SDMA copy (ensemble.RelayComm(transport="peer")).  The sender
+ * copies a relayed trajectory's state into a slot of a pool it has exported; the receiver maps the pool once and pulls the
+ * slot into its own memory.  Neither side launches a kernel or enqueues anything that waits for the other process.
+ *   sdy_relay_pool_create   one hipMalloc of n_slots x slot_bytes (dev), rounded up to 2 MiB, and the 64-byte IPC handle of
+ *                           the whole allocation (hipIpcGetMemHandle on its base: never a suballocation).  Allocates.
+ *   sdy_relay_pool_destroy  hipFree of the pool (synchronises the device).  Only once every process that opened the pool
+ *                           has closed its mapping: a mapping left open onto freed memory faults on its next access.
+ *   sdy_ipc_open / close    hipIpcOpenMemHandle (hipIpcMemLazyEnablePeerAccess) / hipIpcCloseMemHandle of another
+ *                           process's handle; works between two processes on one device as well as across devices.
+ *   sdy_copy_nocu           hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDeviceNoCU, stream): enqueued on the copy
+ *                           engines, no compute unit used. */
+int sdy_relay_pool_create(size_t slot_bytes, int n_slots, void** base, unsigned char handle[64]);
+int sdy_relay_pool_destroy(void* base);
+int sdy_ipc_open(const unsigned char handle[64], void** ptr);
+int sdy_ipc_close(void* ptr);
+int sdy_copy_nocu(void* dst, const void* src, size_t bytes, void* stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

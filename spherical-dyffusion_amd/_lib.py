@@ -226,6 +226,11 @@ SIGNATURES = {
     "sdy_profile_stage_name": (C.c_char_p, [C.c_int]),
     "sdy_profile_read": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_long), C.c_int]),
     "sdy_profile_read_rows": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_long), C.POINTER(C.c_long), C.c_int]),
+    "sdy_relay_pool_create": (C.c_int, [C.c_size_t, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_ubyte)]),
+    "sdy_relay_pool_destroy": (C.c_int, [C.c_void_p]),
+    "sdy_ipc_open": (C.c_int, [C.POINTER(C.c_ubyte), C.POINTER(C.c_void_p)]),
+    "sdy_ipc_close": (C.c_int, [C.c_void_p]),
+    "sdy_copy_nocu": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
 

@@ -127,20 +127,31 @@ class RelayComm:
     it is there), and a blocking `recv(task, like)` only happens at the end of the job, when there is nothing left to overlap.  An early-posted RCCL receive would sit on the GPU
     spinning for the whole time its sender needs to get there; this way the only wait is the sender's `isend`, which the
     receiver picks up at its next window boundary.  `job` keys one run (ranks must agree on it: a counter per process).
+
+    `transport="peer"` (opt-in; `PeerRelayComm`) hands the state over by an SDMA copy between device buffers instead, with no
+    RCCL and no kernel on either GPU; it takes `store=`, `plan=` and `like=` as well.  Any other name than None / "peer" raises.
     """
     _jobs = 0
+    TRANSPORTS = (None, "peer")
 
-    def __init__(self, device=None, job=None):
+    def __new__(cls, *args, transport=None, **kwargs):
+        if transport not in cls.TRANSPORTS:
+            raise ValueError(f"unknown relay transport {transport!r}: None (torch.distributed isend / recv) or 'peer' "
+                             "(SDMA copy between processes)")
+        return super().__new__(PeerRelayComm if (transport == "peer" and cls is RelayComm) else cls)
+
+    def __init__(self, device=None, job=None, transport=None, store=None):
         import torch
         import torch.distributed as dist
 
         assert dist.is_initialized(), "RelayComm needs an initialised torch.distributed process group"
         self._torch, self._dist = torch, dist
+        self.transport = None
         self.rank, self.world = dist.get_rank(), dist.get_world_size()
         self.on_device = dist.get_backend() == "nccl"
         self.device = torch.device(device) if device is not None else (
             torch.device("cuda", torch.cuda.current_device()) if self.on_device else torch.device("cpu"))
-        self.store = dist.distributed_c10d._get_default_store()
+        self.store = store if store is not None else dist.distributed_c10d._get_default_store()
         if job is None:
             job = RelayComm._jobs
             RelayComm._jobs += 1
@@ -214,6 +225,292 @@ class RelayComm:
             req.wait()
         self._sends.clear()
 
+    def close(self) -> None:
+        """Nothing to release (the peer transport's `close` is its teardown)."""
+
+
+class PeerRelayComm(RelayComm):
+    """`RelayComm(transport="peer", store=, plan=, like=)`: the hand-over is a copy on the SDMA engines, and nothing is enqueued
+    on either GPU that waits for the other rank.
+
+    The sender copies the state into the next slot of a pool it exported (`sdy_relay_pool_create`: one slot per send of its
+    plan, so no slot is reused within a job and no send waits for a free one); the receiver, which mapped that pool once in
+    `warm_up`, pulls the slot into a buffer of its own when it sees the announcement.  Store handshake per hand-over of
+    trajectory u into window w (keys under `sdy_relay_peer/<job>/`):
+      ready/u/w  "slot,u,w,send-copy ms"  set by the sender once `query` reports its copy done (checked in poll / send / ready,
+                                          never waited for)
+      taken/u/w                           set by the receiver once its pull has landed
+      closed/<owner>/<opener>             set by `close()` once the opener has unmapped the owner's pool
+    The receiver pulls, so the sender never has an operation addressed to the receiver pending: two relay chains crossing one
+    pair in opposite directions cannot wait on each other.  Teardown: `finish()` waits until every sent slot is taken;
+    `close()` unmaps every pool this rank opened, announces it, and frees this rank's pool only after every rank that opened it
+    has announced `closed` (a mapping left open onto freed memory faults on its next access).  Call `close()` on every rank
+    before `destroy_process_group`.
+
+    Every rank constructs the comm for every job, hosting a slice or not: the job id is agreed through the store (rank 0 draws
+    it from a counter there and publishes it for the others), so keys of consecutive jobs never meet.  `engine` is the copy
+    engine (`HipPeerEngine` on the GPU by default; the CPU tests inject a host-memory one with the same surface)."""
+
+    POLL_S = 0.0005
+
+    def __init__(self, device=None, job=None, transport="peer", store=None, plan=None, like=None, engine=None,
+                 timeout_s: float = 600.0):
+        import torch
+        import torch.distributed as dist
+
+        if store is None or plan is None or like is None:
+            raise ValueError("transport='peer' needs store= (the job's key-value store), plan= (this rank's relay_plan) and "
+                             "like= (a tensor of the state's shape, dtype and device)")
+        assert dist.is_initialized(), "RelayComm needs an initialised torch.distributed process group"
+        self._torch = torch
+        self.transport = "peer"
+        self.rank, self.world = dist.get_rank(), dist.get_world_size()
+        self.store, self.plan, self.timeout_s = store, plan, timeout_s
+        self.device = torch.device(device) if device is not None else like.device
+        self._shape, self._dtype = tuple(like.shape), like.dtype
+        self.state_bytes = like.numel() * like.element_size()
+        self.slot_bytes = -(-self.state_bytes // 4096) * 4096
+        self.engine = engine if engine is not None else HipPeerEngine(self.device)
+        self.job = self._agree_job() if job is None else job
+        self._pool, self._n_slots, self._next_slot = None, 0, 0
+        self._peers = {}               # source rank -> base of its pool mapped here
+        self._bufs = []                # one local buffer per incoming hand-over, allocated in warm_up
+        self._sending = []             # (task, slot, copy token, state kept alive until the copy is done)
+        self._untaken = []             # (unit, window) announced ready, not yet taken
+        self._pulling = []             # (unit, window, copy token, send-copy ms)
+        self._inbox = {}               # (unit, window) -> (buffer, copy token)
+        self.handover_ms: List[float] = []     # send copy + pull copy of every hand-over received here
+        self.recv_wait_s = 0.0
+        self._warm = self._closed = False
+
+    def _agree_job(self) -> int:
+        n = self.store.add(f"sdy_relay_peer/comms/{self.rank}", 1)       # this rank's n-th peer comm over this store
+        key = f"sdy_relay_peer/job_of/{n}"
+        if self.rank == 0:
+            job = self.store.add("sdy_relay_peer/jobs", 1)
+            self.store.set(key, str(job))
+            return job
+        return int(self.store.get(key).decode())
+
+    def _key(self, *parts) -> str:
+        return "/".join(["sdy_relay_peer", str(self.job)] + [str(p) for p in parts])
+
+    def _wait(self, cond: Callable[[], bool], what: str) -> None:
+        """Waits for `cond`, polling this rank's own copies meanwhile (its announcements are what others wait for)."""
+        import time
+
+        deadline = time.monotonic() + self.timeout_s
+        while not cond():
+            if time.monotonic() > deadline:
+                from ._lib import SdyError
+
+                raise SdyError(f"relay (peer transport, job {self.job}, rank {self.rank}): timed out waiting for {what}")
+            time.sleep(self.POLL_S)
+            self.poll()
+
+    def warm_up(self) -> None:
+        """Creates and publishes this rank's pool, maps the pools of the plan's sources (once per pair), allocates the receive
+        buffers and runs one copy over every path, so that a refused mapping or copy raises SdyError here, before timed work."""
+        t = self._torch
+        n_send = sum(task.dst is not None for task in self.plan.tasks)
+        srcs = sorted({task.src for task in self.plan.tasks if task.src is not None})
+        if n_send:
+            self._pool, handle = self.engine.create(self.slot_bytes, n_send)
+            self._n_slots = n_send
+            self.store.set(self._key("pool", self.rank), handle)
+        for s in srcs:
+            self._peers[s] = self.engine.open(self.store.get(self._key("pool", s)))
+        self._bufs = [t.empty(self._shape, dtype=self._dtype, device=self.device)
+                      for task in self.plan.tasks if task.src is not None]
+        if n_send:
+            zero = t.zeros(self._shape, dtype=self._dtype, device=self.device)
+            self.engine.sync(self.engine.copy(self._pool, zero.data_ptr(), self.state_bytes, after_compute=True))
+        for s in srcs:
+            self.engine.sync(self.engine.copy(self._bufs[0].data_ptr(), self._peers[s], self.state_bytes, after_compute=False))
+        self.engine.sync(None)
+        self._warm = True
+
+    def poll(self) -> None:
+        """Non-blocking: announces every send copy that has completed (ready) and every pull that has landed (taken)."""
+        sending = []
+        for task, slot, tok, state in self._sending:
+            if self.engine.query(tok):
+                ms = self.engine.elapsed_ms(tok)
+                self.store.set(self._key("ready", task.unit, task.w_end), f"{slot},{task.unit},{task.w_end},{ms!r}")
+                self._untaken.append((task.unit, task.w_end))
+            else:
+                sending.append((task, slot, tok, state))
+        self._sending = sending
+        pulling = []
+        for unit, w, tok, send_ms in self._pulling:
+            if self.engine.query(tok):
+                self.handover_ms.append(send_ms + self.engine.elapsed_ms(tok))
+                self.store.set(self._key("taken", unit, w), "1")
+            else:
+                pulling.append((unit, w, tok, send_ms))
+        self._pulling = pulling
+
+    def send(self, task: "RelayTask", state) -> None:
+        """Non-blocking: the copy into the next slot is enqueued on a side stream behind the state's producer; the state is
+        kept alive until the copy is done, and announced by the poll that sees it done."""
+        from ._lib import SdyError
+
+        assert self._warm, "warm_up() first"
+        self.poll()
+        src = state.detach().contiguous()
+        if src.numel() * src.element_size() != self.state_bytes or src.dtype != self._dtype:
+            raise SdyError(f"relay state {tuple(src.shape)} {src.dtype} is not the {self._shape} {self._dtype} of like=")
+        if self._next_slot >= self._n_slots:
+            raise SdyError(f"rank {self.rank}: more sends than its plan's {self._n_slots} slots")
+        slot = self._next_slot
+        self._next_slot += 1
+        tok = self.engine.copy(self._pool + slot * self.slot_bytes, src.data_ptr(), self.state_bytes, after_compute=True)
+        self._sending.append((task, slot, tok, src))
+
+    def _pull(self, task: "RelayTask") -> None:
+        slot, _, _, send_ms = self.store.get(self._key("ready", task.unit, task.w_begin)).decode().split(",")
+        buf = self._bufs.pop()
+        tok = self.engine.copy(buf.data_ptr(), self._peers[task.src] + int(slot) * self.slot_bytes, self.state_bytes,
+                               after_compute=False)
+        self._inbox[(task.unit, task.w_begin)] = (buf, tok)
+        self._pulling.append((task.unit, task.w_begin, tok, float(send_ms)))
+
+    def ready(self, task: "RelayTask", like) -> bool:
+        """Non-blocking: True once the state's pull has been enqueued (it is, here, if the sender has announced it)."""
+        self.poll()
+        if (task.unit, task.w_begin) in self._inbox:
+            return True
+        if not self.store.check([self._key("ready", task.unit, task.w_begin)]):
+            return False
+        self._pull(task)
+        return True
+
+    def recv(self, task: "RelayTask", like):
+        """The state of this slice.  The compute stream waits for the pull on the device; the host does not, unless the state
+        has not been announced yet (the end of the job: nothing left to overlap)."""
+        import time
+
+        if (task.unit, task.w_begin) not in self._inbox:
+            t0 = time.perf_counter()
+            self._wait(lambda: self.ready(task, like), f"the state of trajectory {task.unit} for window {task.w_begin}")
+            self.recv_wait_s += time.perf_counter() - t0
+        buf, tok = self._inbox.pop((task.unit, task.w_begin))
+        self.engine.wait(tok)
+        return buf
+
+    def _all_taken(self) -> bool:
+        if self._sending:
+            return False
+        if self._untaken and not self.store.check([self._key("taken", u, w) for u, w in self._untaken]):
+            return False
+        self._untaken.clear()
+        return True
+
+    def finish(self) -> None:
+        """Waits until every slot this rank sent has been taken by its receiver."""
+        self._wait(self._all_taken, "the receivers to take this rank's sends")
+
+    def close(self) -> None:
+        """Teardown, on every rank: finish, unmap the pools this rank opened and announce it, then free this rank's pool once
+        every rank that opened it has announced the same."""
+        if self._closed:
+            return
+        if self._warm:
+            self.finish()
+            self._wait(lambda: not self._pulling, "this rank's pulls to land")
+            self.engine.sync(None)
+        for s in sorted(self._peers):
+            self.engine.close(self._peers.pop(s))
+            self.store.set(self._key("closed", s, self.rank), "1")
+        if self._pool is not None:
+            keys = [self._key("closed", self.rank, d) for d in sorted({t.dst for t in self.plan.tasks if t.dst is not None})]
+            self._wait(lambda: self.store.check(keys), "the ranks that mapped this rank's pool to close it")
+            self.engine.destroy(self._pool)
+            self._pool = None
+        self._closed = True
+
+
+class HipPeerEngine:
+    """The peer transport's copy engine on the GPU: pool / mapping through the C ABI (`sdy_relay_pool_create`, `sdy_ipc_open`,
+    ...) and `sdy_copy_nocu` copies on two side streams (sends, pulls), each bracketed by timing events.  A send copy waits
+    for the compute stream (the state's producer) through an event; a pull copy waits for nothing (its buffer is one of the
+    comm's own, written once).  `wait` is a device-side wait of the compute stream; nothing here synchronises the host except
+    `sync`, which warm-up and teardown use."""
+
+    def __init__(self, device):
+        import torch
+
+        self._torch, self.device = torch, torch.device(device)
+        self._streams = {True: torch.cuda.Stream(self.device), False: torch.cuda.Stream(self.device)}
+
+    def create(self, slot_bytes: int, n_slots: int):
+        import ctypes as C
+
+        from ._lib import check, lib
+
+        base, handle = C.c_void_p(), (C.c_ubyte * 64)()
+        with self._torch.cuda.device(self.device):
+            check(lib.sdy_relay_pool_create(slot_bytes, n_slots, C.byref(base), handle), "sdy_relay_pool_create")
+        return base.value, bytes(handle)
+
+    def destroy(self, base: int) -> None:
+        from ._lib import check, lib
+
+        with self._torch.cuda.device(self.device):
+            check(lib.sdy_relay_pool_destroy(base), "sdy_relay_pool_destroy")
+
+    def open(self, handle: bytes) -> int:
+        import ctypes as C
+
+        from ._lib import check, lib
+
+        ptr = C.c_void_p()
+        with self._torch.cuda.device(self.device):
+            check(lib.sdy_ipc_open((C.c_ubyte * 64).from_buffer_copy(handle), C.byref(ptr)), "sdy_ipc_open (hipIpcOpenMemHandle)")
+        return ptr.value
+
+    def close(self, ptr: int) -> None:
+        from ._lib import check, lib
+
+        with self._torch.cuda.device(self.device):
+            check(lib.sdy_ipc_close(ptr), "sdy_ipc_close (hipIpcCloseMemHandle)")
+
+    def copy(self, dst: int, src: int, nbytes: int, after_compute: bool):
+        from ._lib import check, lib
+
+        t = self._torch
+        side = self._streams[after_compute]
+        with t.cuda.device(self.device):
+            if after_compute:
+                produced = t.cuda.Event()
+                produced.record(t.cuda.current_stream(self.device))
+                side.wait_event(produced)
+            t0, t1 = t.cuda.Event(enable_timing=True), t.cuda.Event(enable_timing=True)
+            t0.record(side)
+            check(lib.sdy_copy_nocu(dst, src, nbytes, side.cuda_stream), "sdy_copy_nocu")
+            t1.record(side)
+        return t0, t1
+
+    def query(self, tok) -> bool:
+        return tok[1].query()
+
+    def elapsed_ms(self, tok) -> float:
+        return tok[0].elapsed_time(tok[1])
+
+    def wait(self, tok) -> None:
+        self._torch.cuda.current_stream(self.device).wait_event(tok[1])
+
+    def sync(self, tok) -> None:
+        from ._lib import SdyError
+
+        try:
+            if tok is None:
+                self._torch.cuda.synchronize(self.device)
+            else:
+                tok[1].synchronize()
+        except RuntimeError as e:
+            raise SdyError(f"relay copy failed: {e}") from e
+
 
 class RelayRunner:
     """One rank's relay work, driven from its window loop.  Policy: LOCKSTEP WITH CATCH-UP -- after the rank has seen window
@@ -264,6 +561,9 @@ class RelayRunner:
 
     def after_window(self, w: int) -> None:
         """The caller has loaded window w (and advanced its resident batch through it)."""
+        poll = getattr(self.comm, "poll", None)
+        if poll is not None:        # (a rank that only sends announces its finished copies here, not only at drain())
+            poll()
         for e in list(self._todo):
             if e["task"].w_begin <= w and self._acquire(e, block=False):
                 self._advance(e, w)

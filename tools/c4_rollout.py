@@ -16,7 +16,9 @@ that has).  A job whose trajectories divide by the ranks runs `run_inference(uni
 one that does not (25 over 8) runs `run_inference(relay=ensemble.relay_plan(...))`: equal resident blocks and the remainder
 trajectories relayed between the ranks in time slices (`--no-relay`: the static 4,3,3,... split, whose largest share sets the
 pace).  No collective on the data path; the `TimeMeanAggregator(dist=TorchDistributed())` combines the ranks' maps once, at
-log time (RCCL).
+log time (RCCL).  `--transport peer` hands relayed states over by SDMA copy between the processes (`RelayComm(transport="peer")`)
+instead of torch.distributed send / recv; the JSON's `relay` object then has the hand-over times (send copy + pull copy, by
+events), and with either transport the sha256 of every relay trajectory's final carried state.
 """
 import argparse
 import json
@@ -47,7 +49,7 @@ def windows(names, n_windows, window, nlat, nlon, seed=1234, n_ics=1):
 
 
 def run(device, steps, members, window=6, layers=8, embed=256, nlat=180, nlon=360, aggregate=True, warmup=True, n_ics=1,
-        rank=0, world=1, prefetch=2, max_batch=None, dist=None, relay=True):
+        rank=0, world=1, prefetch=2, max_batch=None, dist=None, relay=True, transport=None, store=None):
     import torch
 
     import sdy_amd
@@ -72,12 +74,16 @@ def run(device, steps, members, window=6, layers=8, embed=256, nlat=180, nlon=36
         w = sdy_amd.metrics.spherical_area_weights(torch.linspace(-89.5, 89.5, nlat), nlon)
         agg = sdy_amd.metrics.TimeMeanAggregator(w, is_ensemble=members > 1, dist=dist)
     finite = {"ok": True}
+    ends_here = {t.unit for t in plan.tasks if t.dst is None} if plan is not None else set()
+    relay_last = {}          # relay trajectory ending on this rank -> (start time step, prediction) of its latest window
 
     class Writer:     # stands for the reference's data writer: only checks what it is handed
         def append_batch(self, target, prediction, start_timestep, start_sample, batch_times=None):
             v = prediction[out_names[0]]
             finite["ok"] = finite["ok"] and bool(torch.isfinite(v).all())
             finite["shape"] = tuple(v.shape)
+            if start_sample in ends_here and v.shape[0] == 1 and start_timestep >= relay_last.get(start_sample, (-1,))[0]:
+                relay_last[start_sample] = (start_timestep, prediction)
 
     def loader(n_windows, seed):     # a rank's loader delivers only the initial conditions its share touches
         for wdw in windows(names, n_windows, window, nlat, nlon, seed=seed, n_ics=n_ics):
@@ -95,7 +101,11 @@ def run(device, steps, members, window=6, layers=8, embed=256, nlat=180, nlon=36
             sdy_amd.run_inference(None, stepper, loader(1, 7), window, window, **dict(wkw, unit_range=(plan.tasks[0].unit, 1)))
     comm = None
     if plan is not None:
-        comm = ensemble.RelayComm(device=device)
+        if transport == "peer":     # (on every rank, hosting a slice or not: the ranks agree on the job id through the store)
+            like = torch.empty(len(out_names), nlat, nlon, dtype=torch.float32, device=device)
+            comm = ensemble.RelayComm(device=device, transport="peer", store=store, plan=plan, like=like)
+        else:
+            comm = ensemble.RelayComm(device=device)
         comm.warm_up()
         kw.update(relay_comm=comm)
     exp.set_dropout_calls((0, 0))        # every rank numbers the job's dropout calls from the same origin
@@ -106,6 +116,8 @@ def run(device, steps, members, window=6, layers=8, embed=256, nlat=180, nlon=36
     t0 = time.perf_counter()
     timers = sdy_amd.run_inference(agg, stepper, loader(steps // window, 1234), steps, window, writer=Writer(), **kw)
     wall = time.perf_counter() - t0
+    if comm is not None:
+        comm.close()
     res = {"steps": steps, "members": members, "ics": n_ics, "rows": cnt, "windows": steps // window, "wall_s": round(wall, 2),
            "relayed_windows": sum(t.w_end - t.w_begin for t in plan.tasks) if plan is not None else 0,
            "relay_recv_wait_s": round(timers.get("relay_recv_wait", 0.0), 3),
@@ -117,6 +129,15 @@ def run(device, steps, members, window=6, layers=8, embed=256, nlat=180, nlon=36
            "finite": finite["ok"], "prediction_shape": finite.get("shape")}
     if agg is not None:
         res["time_mean_rmse_channel_mean"] = round(agg.get_logs("")["rmse/channel_mean"], 5)
+    if plan is not None:
+        import hashlib
+
+        finals = {}
+        for u, (_, pred) in relay_last.items():      # the final carried state: every generated variable's last time step
+            state = torch.stack([pred[k][0, -1] for k in out_names]).contiguous().cpu()
+            finals[str(u)] = hashlib.sha256(state.numpy().tobytes()).hexdigest()
+        res["relay"] = {"transport": transport or "default", "handover_ms_list": list(getattr(comm, "handover_ms", [])),
+                        "final_sha256": finals}
     return res
 
 
@@ -165,6 +186,8 @@ def main():
     ap.add_argument("--grid", type=int, nargs=2, default=(180, 360))
     ap.add_argument("--no-relay", action="store_true",
                     help="uneven jobs as a static split (25 over 8 = 4,3,3,...) instead of equal blocks + relayed remainder")
+    ap.add_argument("--transport", choices=("default", "peer"), default="default",
+                    help="relay hand-over: torch.distributed send / recv (default) or an SDMA copy between the processes (peer)")
     ap.add_argument("--share-gpu", action="store_true",
                     help="TEST ONLY: all ranks on GPU 0 with the gloo backend (exercises the N>1 path on a 1-GPU box)")
     a = ap.parse_args()
@@ -185,16 +208,22 @@ def main():
         raise SystemExit(f"--gpus {a.gpus} but WORLD_SIZE={world}")
     dev = torch.device("cuda", local)
     torch.cuda.set_device(dev)
-    dist = None
+    dist = store = None
     if world > 1:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        pg = {}
+        if a.transport == "peer":       # the peer transport's handshake goes through this store (it is given, not looked up)
+            store = td.TCPStore(os.environ["MASTER_ADDR"], int(os.environ["MASTER_PORT"]), world, rank == 0)
+            pg = dict(store=store, rank=rank, world_size=world)
         if a.share_gpu:
-            td.init_process_group("gloo")
+            td.init_process_group("gloo", **pg)
         else:
-            td.init_process_group("nccl", device_id=dev)       # "nccl" is RCCL on ROCm
+            td.init_process_group("nccl", device_id=dev, **pg)       # "nccl" is RCCL on ROCm
         dist = sdy_amd.metrics.TorchDistributed() if not a.share_gpu else _HostDist(td)
     r = run(dev, a.steps, a.members, layers=a.layers, embed=a.embed, nlat=a.grid[0], nlon=a.grid[1], n_ics=a.ics, rank=rank,
-            world=world, prefetch=a.prefetch, max_batch=a.max_batch, dist=dist, relay=not a.no_relay)
+            world=world, prefetch=a.prefetch, max_batch=a.max_batch, dist=dist, relay=not a.no_relay,
+            transport=None if a.transport == "default" else a.transport,
+            store=td.PrefixStore("c4_relay", store) if store is not None else None)
     if world > 1:     # whole-job rate: every rank's trajectories over the slowest rank's wall time
         t = torch.tensor([r.get("wall_s", 0.0), float(r.get("trajectory_steps", 0.0))], dtype=torch.float64,
                          device="cpu" if a.share_gpu else dev)
@@ -204,6 +233,14 @@ def main():
         r["n_gpus"] = world
         r["job_wall_s"] = round(float(tmax[0]), 2)
         r["job_member_forecast_steps_per_s"] = round(float(tsum[1]) / max(float(tmax[0]), 1e-9), 2)
+        if "relay" in r:              # every rank's hand-overs and final states (a relay trajectory ends on any rank)
+            parts = [None] * world
+            td.all_gather_object(parts, r["relay"])
+            ms = sorted(x for p in parts for x in p["handover_ms_list"])
+            r["relay"] = {"transport": r["relay"]["transport"],
+                          "handover_ms": {"n": len(ms), "median": ms[len(ms) // 2] if ms else None,
+                                          "max": ms[-1] if ms else None} if r["relay"]["transport"] == "peer" else None,
+                          "final_sha256": {u: h for p in parts for u, h in p["final_sha256"].items()}}
     if rank == 0:
         rate = r.get("job_member_forecast_steps_per_s", r.get("member_forecast_steps_per_s", 0.0))
         if rate:
