@@ -442,6 +442,18 @@ int sdy_ensemble_series(const float* pred, int M, long member_stride, long sampl
                         long truth_sample_stride, const float* weights, int n_sample, int T, int HW, double* out,
                         void* stream);
 
+/* sdy_ensemble_series plus the two sums of weighted_grad_mag_percent_diff (gradient_magnitude_percent_diff,
+ * src/ace_inference/core/metrics.py:210-241; fed the member-stacked prediction by reduced.py:178,225-227 and
+ * one_step/reduced.py:75,121-123), in the same pass.  Planes are (nlat, nlon) rows of width nlon (HW = nlat*nlon), the
+ * other arguments as for sdy_ensemble_series.  |grad x| = sqrt(g_lat^2 + g_lon^2) with torch.gradient's unit spacing and
+ * edge_order 1: (x[i+1] - x[i-1]) / 2 inside, x[1] - x[0] and x[n-1] - x[n-2] at the edges, longitude NOT periodic.
+ *   out[p][0..7] as sdy_ensemble_series;  out[p][8] += sum_w |grad truth|;  out[p][9] += sum_m sum_w |grad x_m|
+ * (the caller divides [9] by M for the reference's mean over members).  nlat < 2 or nlon < 2: SDY_ERR_ARG (torch.gradient
+ * refuses them too), as is nlat*nlon > 2^30.  out: dev double [n_sample*T*10], zeroed by the caller. */
+int sdy_ensemble_series_grad(const float* pred, int M, long member_stride, long sample_stride, const float* truth,
+                             long truth_sample_stride, const float* weights, int n_sample, int T, int nlat, int nlon,
+                             double* out, void* stream);
+
 /* Time-mean accumulation of the inference aggregator (src/ace_inference/core/aggregator/inference/time_mean.py:97-117,
  * _add_or_initialize_time_mean): acc[p] += scale * sum over rows (r0, r1) and times t0 <= t < T of
  * x[r0*stride0 + r1*stride1 + t*HW + p].  x: dev, one variable of a window, (n0, n1, T, HW) with float strides for the

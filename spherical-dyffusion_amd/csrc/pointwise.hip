@@ -696,22 +696,53 @@ __global__ __launch_bounds__(256) void ens_metrics_kernel(const float* __restric
 // area-weighted mean / standard deviation of the ensemble mean and of the target (metrics.py:32-82):
 //   out[p][0..7] += sum_w (mean - t)^2 | sum_w var_m | sum_w fair CRPS | sum_w (mean - t) | sum_w mean | sum_w mean^2 |
 //                   sum_w t | sum_w t^2
-__global__ __launch_bounds__(256) void ens_series_kernel(const float* __restrict__ pred, int M, long member_stride,
-                                                          long sample_stride, const float* __restrict__ truth,
-                                                          long truth_sample_stride, const float* __restrict__ w, int T, int HW,
-                                                          double* __restrict__ out) {
+// GRAD adds the two sums of weighted_grad_mag_percent_diff (metrics.py:210-241, torch.gradient over (lat, lon) with unit
+// spacing, edge_order 1, longitude NOT periodic):
+//   out[p][8..9] += sum_w |grad t| | sum_m sum_w |grad x_m|
+// in the same pass.  A GRAD block walks one contiguous span of the plane (rows of width nlon), so the rows above and below
+// a point were just read by the same block and come from L1/L2; the gradients need no per-member storage.  GRAD = false is
+// the kernel as it was: grid-stride over the plane, nlon unused, and ens_series_kernel keeps the old arguments, so it
+// assembles to the same instructions as before.
+template <bool GRAD>
+__device__ __forceinline__ void ens_series_pass(const float* __restrict__ pred, int M, long member_stride, long sample_stride,
+                                                const float* __restrict__ truth, long truth_sample_stride,
+                                                const float* __restrict__ w, int T, int HW, int nlon, double* __restrict__ out) {
+  constexpr int NQ = GRAD ? 10 : 8, UNROLL = GRAD ? 1 : 8;
   const int pl = blockIdx.y;
   const int smp = pl / T, t_i = pl - smp * T;
   const float* pp = pred + (long)smp * sample_stride + (long)t_i * HW;
   const float* tp = truth + (long)smp * truth_sample_stride + (long)t_i * HW;
-  double a[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < HW; i += gridDim.x * 256) {
+  double a[NQ];
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) a[q] = 0.0;
+  // GRAD: block b walks [b * span, (b + 1) * span) in steps of 256; otherwise grid-stride
+  const int span = GRAD ? (HW + gridDim.x * 256 - 1) / (gridDim.x * 256) * 256 : 0;
+  const int i_end = GRAD ? min(HW, (int)(blockIdx.x + 1) * span) : HW;
+  for (int i = (GRAD ? blockIdx.x * span : blockIdx.x * 256) + threadIdx.x; i < i_end; i += GRAD ? 256 : gridDim.x * 256) {
+    // neighbours of torch.gradient: central (x[+1] - x[-1]) / 2 inside, one-sided x[1] - x[0] / x[n-1] - x[n-2] at the
+    // edges (nlat, nlon >= 2, so every index stays inside the plane)
+    unsigned iw = i, ie = i, in_ = i, is = i;
+    float sx = 1.f, sy = 1.f;
+    if constexpr (GRAD) {
+      const int r = i / nlon, c = i - r * nlon;
+      iw = c > 0 ? i - 1 : i;
+      ie = c < nlon - 1 ? i + 1 : i;
+      in_ = r > 0 ? i - nlon : i;
+      is = i + nlon < HW ? i + nlon : i;
+      sx = (c > 0 && c < nlon - 1) ? 0.5f : 1.f;
+      sy = (r > 0 && i + nlon < HW) ? 0.5f : 1.f;
+    }
     float x[ENS_MAX];
-    float mean = 0.f;
-#pragma unroll 8
+    float mean = 0.f, gsum = 0.f;
+#pragma unroll UNROLL
     for (int m = 0; m < M; ++m) {
       x[m] = pp[(long)m * member_stride + i];
       mean += x[m];
+      if constexpr (GRAD) {
+        const float* pm = pp + (long)m * member_stride;
+        const float gy = (pm[is] - pm[in_]) * sy, gx = (pm[ie] - pm[iw]) * sx;
+        gsum += sqrtf(gy * gy + gx * gx);
+      }
     }
     mean /= (float)M;
     const float t = tp[i], wi = w[i];
@@ -734,21 +765,38 @@ __global__ __launch_bounds__(256) void ens_series_kernel(const float* __restrict
     a[5] += wd * ((double)mean * mean);
     a[6] += wd * t;
     a[7] += wd * ((double)t * t);
+    if constexpr (GRAD) {
+      const float gy = (tp[is] - tp[in_]) * sy, gx = (tp[ie] - tp[iw]) * sx;
+      a[8] += wd * sqrtf(gy * gy + gx * gx);
+      a[NQ - 1] += wd * gsum;
+    }
   }
-  __shared__ double sh[32];
+  __shared__ double sh[4 * NQ];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
-  for (int q = 0; q < 8; ++q) {
+  for (int q = 0; q < NQ; ++q) {
     double v = a[q];
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
     if (lane == 0) sh[4 * q + wave] = v;
   }
   __syncthreads();
-  if (threadIdx.x < 8) {
+  if (threadIdx.x < NQ) {
     const int q = threadIdx.x;
-    atomicAdd(&out[8 * pl + q], sh[4 * q] + sh[4 * q + 1] + sh[4 * q + 2] + sh[4 * q + 3]);
+    atomicAdd(&out[NQ * pl + q], sh[4 * q] + sh[4 * q + 1] + sh[4 * q + 2] + sh[4 * q + 3]);
   }
+}
+__global__ __launch_bounds__(256) void ens_series_kernel(const float* __restrict__ pred, int M, long member_stride,
+                                                          long sample_stride, const float* __restrict__ truth,
+                                                          long truth_sample_stride, const float* __restrict__ w, int T, int HW,
+                                                          double* __restrict__ out) {
+  ens_series_pass<false>(pred, M, member_stride, sample_stride, truth, truth_sample_stride, w, T, HW, 0, out);
+}
+__global__ __launch_bounds__(256) void ens_series_grad_kernel(const float* __restrict__ pred, int M, long member_stride,
+                                                               long sample_stride, const float* __restrict__ truth,
+                                                               long truth_sample_stride, const float* __restrict__ w, int T,
+                                                               int HW, int nlon, double* __restrict__ out) {
+  ens_series_pass<true>(pred, M, member_stride, sample_stride, truth, truth_sample_stride, w, T, HW, nlon, out);
 }
 
 }  // namespace
@@ -800,6 +848,21 @@ extern "C" int sdy_ensemble_series(const float* pred, int M, long member_stride,
   if (gx > 64) gx = 64;
   hipLaunchKernelGGL(ens_series_kernel, dim3(gx, n_sample * T), dim3(256), 0, (hipStream_t)stream, pred, M, member_stride,
                      sample_stride, truth, truth_sample_stride, weights, T, HW, out);
+  return sdy_launch_status();
+}
+
+extern "C" int sdy_ensemble_series_grad(const float* pred, int M, long member_stride, long sample_stride, const float* truth,
+                                        long truth_sample_stride, const float* weights, int n_sample, int T, int nlat, int nlon,
+                                        double* out, void* stream) {
+  if (!pred || !truth || !weights || !out || M < 1 || n_sample < 1 || T < 1 || nlat < 2 || nlon < 2) return SDY_ERR_ARG;
+  if ((long)nlat * nlon > (1L << 30)) return SDY_ERR_ARG;
+  if (M > ENS_MAX) return SDY_ERR_UNSUPPORTED;
+  if ((long)n_sample * T > 65535) return SDY_ERR_UNSUPPORTED;
+  const int HW = nlat * nlon;
+  int gx = (HW + 255) / 256;
+  if (gx > 64) gx = 64;
+  hipLaunchKernelGGL(ens_series_grad_kernel, dim3(gx, n_sample * T), dim3(256), 0, (hipStream_t)stream, pred, M,
+                     member_stride, sample_stride, truth, truth_sample_stride, weights, T, HW, nlon, out);
   return sdy_launch_status();
 }
 

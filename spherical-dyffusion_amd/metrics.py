@@ -203,13 +203,20 @@ class TimeMeanAggregator:
 SERIES_METRICS = ("weighted_rmse", "weighted_bias", "weighted_mean_gen", "weighted_mean_target", "weighted_std_gen",
                   "weighted_std_target")
 SERIES_METRICS_ENSEMBLE = ("weighted_crps", "weighted_ssr")
+GRAD_MAG_METRIC = "weighted_grad_mag_percent_diff"
 
 
-def ensemble_series(truth: torch.Tensor, predicted: torch.Tensor, weights: torch.Tensor) -> torch.Tensor:
+def ensemble_series(truth: torch.Tensor, predicted: torch.Tensor, weights: torch.Tensor,
+                    grad_mag: bool = False) -> torch.Tensor:
     """truth (n_sample, T, H, W), predicted (members, n_sample, T, H, W) -- any strides on the two leading axes, so the window
     driver's member-stacked VIEW is read in place -- weights (H, W)  ->  (n_sample, T, 8) fp64: the area-weighted means of
     (ens. mean - truth)^2 | member variance (unbiased) | fair CRPS | ens. mean - truth | ens. mean | (ens. mean)^2 | truth |
-    truth^2 per (sample, time) plane (`sdy_ensemble_series`: one pass, members in registers)."""
+    truth^2 per (sample, time) plane (`sdy_ensemble_series`: one pass, members in registers).
+
+    `grad_mag=True` -> (n_sample, T, 10): the same eight, then the area-weighted mean gradient magnitude of the truth and the
+    mean over members of each member's (`weighted_mean_gradient_magnitude`, `metrics.py:210-220`: torch.gradient over
+    (H, W) with unit spacing, edge_order 1, longitude not periodic) -- the T and P of `gradient_magnitude_percent_diff`
+    (`:223-241`), from the same pass (`sdy_ensemble_series_grad`).  H, W >= 2."""
     if not predicted.is_cuda:
         raise RuntimeError("sdy_amd metrics run on the GPU only (no CPU fallback)")
     assert predicted.dim() == 5 and predicted.shape[1:] == truth.shape, \
@@ -223,11 +230,22 @@ def ensemble_series(truth: torch.Tensor, predicted: torch.Tensor, weights: torch
     if t.stride(-1) != 1 or t.stride(-2) != W or t.stride(-3) != H * W:
         t = t.contiguous()
     w = weights.to(dev, torch.float32).contiguous()
-    out = torch.zeros(n_sample, T, 8, dtype=torch.float64, device=dev)
+    out = torch.zeros(n_sample, T, 10 if grad_mag else 8, dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
-        check(lib.sdy_ensemble_series(ptr(p), M, p.stride(0), p.stride(1), ptr(t), t.stride(0), ptr(w), n_sample, T, H * W,
-                                      ptr(out), current_stream()), "sdy_ensemble_series")
+        if grad_mag:
+            check(lib.sdy_ensemble_series_grad(ptr(p), M, p.stride(0), p.stride(1), ptr(t), t.stride(0), ptr(w), n_sample, T,
+                                               H, W, ptr(out), current_stream()), "sdy_ensemble_series_grad")
+            out[..., 9] /= M                      # sum over members -> mean over members
+        else:
+            check(lib.sdy_ensemble_series(ptr(p), M, p.stride(0), p.stride(1), ptr(t), t.stride(0), ptr(w), n_sample, T,
+                                          H * W, ptr(out), current_stream()), "sdy_ensemble_series")
     return out / w.double().sum()
+
+
+def grad_mag_percent_diff(s: torch.Tensor) -> torch.Tensor:
+    """`gradient_magnitude_percent_diff` (`metrics.py:223-241`) from `ensemble_series(..., grad_mag=True)` rows:
+    100 (P - T) / T per plane; a truth plane without gradient gives inf / nan, as in the reference."""
+    return 100.0 * (s[..., 9] - s[..., 8]) / s[..., 8]
 
 
 class MeanAggregator:
@@ -239,29 +257,35 @@ class MeanAggregator:
     `{"<metric>/<variable>": (n_timesteps,) fp64 tensor}` -- the arrays the reference puts into its table: mean over the
     windows' samples, accumulated at `i_time_start ...` and divided by the number of windows that touched a time index, then
     averaged over ranks (`dist.reduce_mean`, `reduced.py:247`).  Metrics: `weighted_rmse`, `weighted_bias` (of the ensemble
-    mean), `weighted_mean_gen / _target`, `weighted_std_gen / _target`, and for ensembles `weighted_crps` (fair) and
-    `weighted_ssr`; the reference's `weighted_grad_mag_percent_diff` is not computed (out of scope).
-    One `sdy_ensemble_series` launch per variable and window reads the member-stacked view in place; the accumulators are
-    (n_timesteps,) fp64 tensors on the device.
+    mean), `weighted_mean_gen / _target`, `weighted_std_gen / _target`, for ensembles `weighted_crps` (fair) and
+    `weighted_ssr`, and with `grad_mag_percent_diff=True` the reference's `weighted_grad_mag_percent_diff` (per plane
+    100 (P - T) / T of the area-weighted mean gradient magnitudes, P the mean over members: `reduced.py:178,225-227`).
+    One `sdy_ensemble_series` (`sdy_ensemble_series_grad`) launch per variable and window reads the member-stacked view in
+    place; the accumulators are (n_timesteps,) fp64 tensors on the device.
+
+    `grad_mag_percent_diff` is off by default so that the key set of the series stays what existing callers rely on; a
+    drop-in caller passes `grad_mag_percent_diff=True` to get the reference's full key set.
 
     Ensemble metrics need every member of an initial condition on one rank (the reference's IC sharding): a ragged share
     (`run_inference(unit_range=...)` cutting through an IC's members) hands over flat rows and is refused."""
 
     def __init__(self, area_weights: torch.Tensor, target: str = "denorm", n_timesteps: int = 1, is_ensemble: bool = False,
-                 dist=None, device=None, metadata=None):
+                 dist=None, device=None, metadata=None, grad_mag_percent_diff: bool = False):
         if target not in ("norm", "denorm"):
             raise ValueError(f"target must be 'norm' or 'denorm', got {target!r}")
         self._area_weights = area_weights
         self._target = target
         self._n_timesteps = int(n_timesteps)
         self.is_ensemble = is_ensemble
+        self._grad_mag = bool(grad_mag_percent_diff)
         self._dist = TorchDistributed() if dist is None else dist
         self._total: Dict[str, Dict[str, torch.Tensor]] = {}      # metric -> variable -> (n_timesteps,) fp64
         self._n_batches: Optional[torch.Tensor] = None            # (n_timesteps,) int32, as AreaWeightedReducedMetric
 
     @property
     def metric_names(self) -> List[str]:
-        return list(SERIES_METRICS + (SERIES_METRICS_ENSEMBLE if self.is_ensemble else ()))
+        return list(SERIES_METRICS + (SERIES_METRICS_ENSEMBLE if self.is_ensemble else ()) +
+                    ((GRAD_MAG_METRIC,) if self._grad_mag else ()))
 
     @torch.no_grad()
     def record_batch(self, loss, target_data, gen_data, target_data_norm, gen_data_norm, i_time_start: int = 0):
@@ -277,9 +301,9 @@ class MeanAggregator:
                 pred = gen
             else:
                 pred = gen[None]
-            s = ensemble_series(target_data[name], pred, self._area_weights)       # (n_sample, T, 8)
+            s = ensemble_series(target_data[name], pred, self._area_weights, grad_mag=self._grad_mag)  # (n_sample, T, 8|10)
             E = pred.shape[0]
-            mse, var, crps, bias, mg, mg2, mt, mt2 = s.unbind(dim=-1)
+            mse, var, crps, bias, mg, mg2, mt, mt2 = s[..., :8].unbind(dim=-1)
             rmse = mse.sqrt()
             vals = {"weighted_rmse": rmse, "weighted_bias": bias, "weighted_mean_gen": mg, "weighted_mean_target": mt,
                     "weighted_std_gen": (mg2 - mg * mg).clamp_min(0.0).sqrt(),
@@ -287,6 +311,8 @@ class MeanAggregator:
             if self.is_ensemble:
                 vals["weighted_crps"] = crps
                 vals["weighted_ssr"] = var.sqrt() * ((E + 1) / E) ** 0.5 / rmse
+            if self._grad_mag:
+                vals[GRAD_MAG_METRIC] = grad_mag_percent_diff(s)
             n_time = s.shape[1]
             sl = slice(i_time_start, i_time_start + n_time)
             for metric, v in vals.items():
@@ -355,17 +381,25 @@ def to_inference_logs(log: Mapping[str, object]) -> List[Dict[str, float]]:
 class OneStepMeanAggregator:
     """Metrics of ONE forecast step averaged over the windows that contain it (`one_step/reduced.py:35-147`, the reference's
     `mean_step_20`): `weighted_rmse`, `weighted_bias` (of the ensemble mean), `weighted_mean_gen`, for ensembles
-    `weighted_crps` and `weighted_ssr`, and the mean of the `loss` values handed to `record_batch`.  The reference's
-    `weighted_grad_mag_percent_diff` is not computed (as in `MeanAggregator`)."""
+    `weighted_crps` and `weighted_ssr`, with `grad_mag_percent_diff=True` the reference's `weighted_grad_mag_percent_diff`
+    (`one_step/reduced.py:75,121-123`; off by default, as in `MeanAggregator`), and the mean of the `loss` values handed to
+    `record_batch`."""
 
-    def __init__(self, area_weights: torch.Tensor, target_time: int = 1, is_ensemble: bool = False, dist=None, device=None):
+    def __init__(self, area_weights: torch.Tensor, target_time: int = 1, is_ensemble: bool = False, dist=None, device=None,
+                 grad_mag_percent_diff: bool = False):
         self._area_weights = area_weights
         self._target_time = int(target_time)
         self.is_ensemble = is_ensemble
+        self._grad_mag = bool(grad_mag_percent_diff)
         self._dist = TorchDistributed() if dist is None else dist
         self._loss = 0.0
         self._n_batches = 0
         self._total: Dict[str, Dict[str, torch.Tensor]] = {}
+
+    @property
+    def metric_names(self) -> List[str]:
+        return list(("weighted_rmse", "weighted_bias", "weighted_mean_gen") +
+                    (SERIES_METRICS_ENSEMBLE if self.is_ensemble else ()) + ((GRAD_MAG_METRIC,) if self._grad_mag else ()))
 
     @torch.no_grad()
     def record_batch(self, loss, target_data, gen_data, target_data_norm, gen_data_norm, i_time_start: int = 0):
@@ -376,13 +410,16 @@ class OneStepMeanAggregator:
             return
         for name, gen in gen_data.items():
             pred = gen if self.is_ensemble else gen[None]
-            s = ensemble_series(target_data[name][:, t:t + 1], pred[:, :, t:t + 1], self._area_weights)[:, 0]    # (n_sample, 8)
+            s = ensemble_series(target_data[name][:, t:t + 1], pred[:, :, t:t + 1], self._area_weights,
+                                grad_mag=self._grad_mag)[:, 0]                                         # (n_sample, 8|10)
             E = pred.shape[0]
             mse, var, crps, bias, mg = s[:, 0], s[:, 1], s[:, 2], s[:, 3], s[:, 4]
             vals = {"weighted_rmse": mse.sqrt(), "weighted_bias": bias, "weighted_mean_gen": mg}
             if self.is_ensemble:
                 vals["weighted_crps"] = crps
                 vals["weighted_ssr"] = var.sqrt() * ((E + 1) / E) ** 0.5 / mse.sqrt()
+            if self._grad_mag:
+                vals[GRAD_MAG_METRIC] = grad_mag_percent_diff(s)
             for metric, v in vals.items():
                 per_var = self._total.setdefault(metric, {})
                 per_var[name] = per_var.get(name, 0.0) + v.mean()
@@ -407,14 +444,18 @@ class InferenceAggregator:
     `sigma_coordinates` and `metadata` are accepted and unused (they feed derived variables and image captions).  The
     image products of the reference -- snapshots, videos, zonal-mean hovmollers, the time-mean maps as pictures -- are out of
     scope (DESIGN.md section 8): `log_video` / `log_zonal_mean_images` raise, snapshots are not produced;
-    `get_time_mean_maps()` returns what `get_datasets(["time_mean"])` would hold, as device tensors."""
+    `get_time_mean_maps()` returns what `get_datasets(["time_mean"])` would hold, as device tensors.
+
+    `grad_mag_percent_diff=True` adds the reference's `weighted_grad_mag_percent_diff/<var>` to `mean`, `mean_norm` and
+    `mean_step_20`.  It is off by default: the default key set of the logs stays what existing callers rely on, and a
+    drop-in caller of the reference passes `grad_mag_percent_diff=True` to get the reference's full key set."""
 
     accepts_sample_weights = True
 
     def __init__(self, area_weights: torch.Tensor, sigma_coordinates=None, n_timesteps: Optional[int] = None,
                  n_ensemble_members: int = 1, record_step_20: bool = False, log_video: bool = False,
                  enable_extended_videos: bool = False, log_zonal_mean_images: bool = False, dist=None, metadata=None,
-                 device=None):
+                 device=None, grad_mag_percent_diff: bool = False):
         if log_video or enable_extended_videos or log_zonal_mean_images:
             raise NotImplementedError("video / zonal-mean image logging is out of scope of sdy_amd (DESIGN.md section 8)")
         if n_timesteps is None:
@@ -422,7 +463,8 @@ class InferenceAggregator:
         self._is_ensemble = n_ensemble_members > 1
         if device is not None:
             area_weights = area_weights.to(device)
-        kw = dict(area_weights=area_weights, dist=dist, is_ensemble=self._is_ensemble)
+        kw = dict(area_weights=area_weights, dist=dist, is_ensemble=self._is_ensemble,
+                  grad_mag_percent_diff=grad_mag_percent_diff)
         self._aggregators = {
             "mean": MeanAggregator(target="denorm", n_timesteps=n_timesteps, **kw),
             "mean_norm": MeanAggregator(target="norm", n_timesteps=n_timesteps, **kw),

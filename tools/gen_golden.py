@@ -690,6 +690,87 @@ def gen_mean_series(tag="fx_mean_series"):
     print(f"{tag}: ens weighted_crps/a {out['ens::series::weighted_crps/a'][:3]}, saved")
 
 
+def gen_mean_series_grad(tag="fx_mean_series_grad"):
+    """The reference's own inference MeanAggregator (reduced.py:144-266) and one-step MeanAggregator
+    (one_step/reduced.py:35-147) WITH weighted_grad_mag_percent_diff (metrics.py:210-241), fed three windows the way
+    run_inference feeds them (loop.py:133-149), ensemble and deterministic, on a 16x32 and an odd 7x10 grid.  The truth has
+    spatial structure; prediction "a" is a smoothed truth (negative percent difference), "b" a noisier one (positive).  The
+    one-step aggregator's target time lies inside the second window."""
+    from src.ace_inference.core import metrics as M
+    from src.ace_inference.core.aggregator.inference.reduced import MeanAggregator
+    from src.ace_inference.core.aggregator.one_step.reduced import MeanAggregator as OneStepMeanAggregator
+
+    class NoDist:            # single process: reduce_mean is the identity (core/distributed.py)
+        def reduce_mean(self, t):
+            return t
+
+    g = torch.Generator(device="cpu").manual_seed(47)
+    E, S, T = 5, 2, 2
+    names = ["a", "b"]
+    target_time = 4                                # windows cover times 0-2, 3-4, 5-6
+    n_timesteps = 1 + 3 * T
+
+    def field(shape, H, W):                        # a few large-scale waves with random phases + small-scale noise
+        lat = torch.linspace(0, np.pi, H)[:, None]
+        lon = torch.linspace(0, 2 * np.pi, W + 1)[:-1][None, :]
+        ph = torch.rand(*shape, 3, 1, 1, generator=g) * 2 * np.pi
+        x = (torch.sin(2 * lat + ph[..., 0, :, :]) * torch.cos(lon + ph[..., 1, :, :])
+             + 0.5 * torch.cos(3 * lon + 2 * lat + ph[..., 2, :, :]))
+        return 2.0 * x + 1.0 + 0.3 * torch.randn(*shape, H, W, generator=g)
+
+    def smooth(x):                                 # 3-point box filter along both axes, edges replicated
+        xp = torch.nn.functional.pad(x.reshape(-1, 1, *x.shape[-2:]), (1, 1, 1, 1), mode="replicate")
+        return torch.nn.functional.avg_pool2d(xp, 3, stride=1).reshape(x.shape)
+
+    out = dict(names=json.dumps(names), n_timesteps=n_timesteps, target_time=target_time, shapes=json.dumps([]))
+    shapes = []
+    for H, W in ((16, 32), (7, 10)):
+        shp_tag = f"{H}x{W}"
+        shapes.append(shp_tag)
+        lats = torch.linspace(-84.375, 84.375, H) if H == 16 else torch.linspace(-80.0, 80.0, H)
+        w = M.spherical_area_weights(lats, W)
+        out[f"{shp_tag}::lats"] = lats.numpy()
+        for is_ens in (True, False):
+            key = f"{shp_tag}::{'ens' if is_ens else 'det'}"
+            agg = MeanAggregator(w, target="denorm", n_timesteps=n_timesteps, is_ensemble=is_ens, dist=NoDist(),
+                                 device=torch.device("cpu"))
+            one = OneStepMeanAggregator(w, target_time=target_time, is_ensemble=is_ens, dist=NoDist(),
+                                        device=torch.device("cpu"))
+            i_time = 0
+            for win in range(3):
+                nt = T + 1 if win == 0 else T       # the first window keeps its initial condition (loop.py:133-141)
+                tgt = {n: field((S, nt), H, W) for n in names}
+                mshp = (E, S, nt) if is_ens else (S, nt)
+                base = {n: tgt[n][None] if is_ens else tgt[n] for n in names}
+                gen = {"a": smooth(base["a"].expand(*mshp, H, W).clone()) + 0.1 * torch.randn(*mshp, H, W, generator=g),
+                       "b": base["b"] + 0.6 * torch.randn(*mshp, H, W, generator=g) + 0.1}
+                loss = 0.25 * (win + 1)
+                for a in (agg, one):
+                    a.record_batch(loss=loss, target_data=tgt, gen_data=gen, target_data_norm=tgt, gen_data_norm=gen,
+                                   i_time_start=i_time)
+                for n in names:
+                    out[f"{key}::tgt{win}::{n}"] = tgt[n].numpy()
+                    out[f"{key}::gen{win}::{n}"] = gen[n].numpy()
+                out[f"{key}::i_time_start{win}"] = i_time
+                out[f"{key}::loss{win}"] = loss
+                i_time += nt
+            metrics = []
+            for d in agg._get_series_data():
+                out[f"{key}::series::{d.metric_name}/{d.var_name}"] = np.asarray(d.data, dtype=np.float64)
+                metrics.append(d.metric_name)
+            out[f"{key}::metrics"] = json.dumps(sorted(set(metrics)))
+            logs = one.get_logs("one")
+            for k, v in logs.items():
+                out[f"{key}::one_step::{k[len('one/'):]}"] = np.float64(v)
+            out[f"{key}::one_step_keys"] = json.dumps(sorted(k[len("one/"):] for k in logs))
+            gm = [out[f"{key}::series::weighted_grad_mag_percent_diff/{n}"] for n in names]
+            assert (gm[0] < 0).all() and (gm[1] > 0).all(), gm      # both signs of the percent difference occur
+    out["shapes"] = json.dumps(shapes)
+    path = os.path.join(OUT, f"{tag}.npz")
+    np.savez_compressed(path, **out)
+    print(f"{tag}: 16x32 ens grad_mag a {out['16x32::ens::series::weighted_grad_mag_percent_diff/a'][:3]}, "
+          f"b {out['16x32::ens::series::weighted_grad_mag_percent_diff/b'][:3]}; {os.path.getsize(path)} bytes, saved")
+
 if __name__ == "__main__":
     torch.set_num_threads(8)
     if len(sys.argv) > 1:      # regenerate selected fixtures only: python tools/gen_golden.py gen_time_mean
@@ -720,6 +801,7 @@ if __name__ == "__main__":
     gen_metrics()
     gen_time_mean()
     gen_mean_series()
+    gen_mean_series_grad()
     gen_sfno_wide_masks()
     gen_sfno_full()
     sizes = {n: os.path.getsize(os.path.join(OUT, n)) for n in sorted(os.listdir(OUT))}
