@@ -15,33 +15,20 @@
 static inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 static inline size_t round_up_sz(size_t v, size_t m) { return (v + m - 1) / m * m; }
 
-// Generic host-side splitter: value(b, r, k) -> fp16 hi | lo planes [nb][rows_pad][Kpad], scaled by a power of two so
-// that max|v|*scale is in [2^12, 2^13) (hi stays far below the fp16 maximum, lo parts stay out of the subnormals).
+// Generic host-side splitter: value(b, r, k) -> fp16 hi | lo planes [nb][rows_pad][Kpad] of the split-fp16 format (common.h)
 template <class F>
 static float h3_pack_host(std::vector<_Float16>& buf, int nb, int rows, int K, int rows_pad, int Kpad, F value) {
   float mx = 0.f;
   for (int b = 0; b < nb; ++b)
     for (int r = 0; r < rows; ++r)
       for (int k = 0; k < K; ++k) mx = std::fmax(mx, std::fabs(value(b, r, k)));
-  float s = 1.0f;
-  if (mx > 0.f && std::isfinite(mx)) {
-    int e;
-    std::frexp(mx, &e);            // mx = f * 2^e, f in [0.5, 1)
-    s = std::ldexp(1.0f, 13 - e);
-  }
+  const float s = sdy_h3_scale(mx);
   const size_t plane = (size_t)nb * rows_pad * Kpad;
   buf.assign(2 * plane, (_Float16)0.0f);
-  _Float16* hi = buf.data();
-  _Float16* lo = hi + plane;
   for (int b = 0; b < nb; ++b)
     for (int r = 0; r < rows; ++r) {
       const size_t base = ((size_t)b * rows_pad + r) * Kpad;
-      for (int k = 0; k < K; ++k) {
-        const float v = value(b, r, k) * s;
-        const _Float16 hv = (_Float16)v;
-        hi[base + k] = hv;
-        lo[base + k] = (_Float16)(v - (float)hv);
-      }
+      for (int k = 0; k < K; ++k) sdy_h3_split(value(b, r, k) * s, buf[base + k], buf[plane + base + k]);
     }
   return s;
 }

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <atomic>
+#include <cmath>
 #include <type_traits>
 
 #include "../../include/sdy_amd.h"
@@ -121,6 +122,32 @@ __device__ __forceinline__ void sdy_split8(const float* v, sdy_f16x8& hi, sdy_f1
 #ifndef SDY_ACT_SX
 #define SDY_ACT_SX 16.0f
 #endif
+// The constant operand (a weight or an SHT table) of the split-fp16 kernels, packed on the host: fp16 hi | lo parts of w * s,
+// s the power of two that puts max |w| in [2^12, 2^13) (hi stays far below the fp16 maximum, lo out of the subnormals).  The
+// fragment-stream kernels read it as MFMA A-fragment GROUPS of a 32 x 16 block: 64 lanes x 8 halves of hi, then the same of
+// lo; lane ln, element e holds row ln & 31, column 8 (ln >> 5) + e.
+constexpr int SDY_GROUP = 2 * 64;   // sdy_f16x8 per group (hi | lo)
+static inline float sdy_h3_absmax(const float* w, size_t n) {
+  float mx = 0.f;
+  for (size_t i = 0; i < n; ++i) mx = std::fmax(mx, std::fabs(w[i]));
+  return mx;
+}
+static inline float sdy_h3_scale(float absmax) {   // 1 when the max is 0 or not finite
+  if (!(absmax > 0.f) || !std::isfinite(absmax)) return 1.0f;
+  int e;
+  std::frexp(absmax, &e);   // absmax = f * 2^e, f in [0.5, 1)
+  return std::ldexp(1.0f, 13 - e);
+}
+static inline void sdy_h3_split(float v, _Float16& hi, _Float16& lo) {   // v already scaled
+  hi = (_Float16)v;
+  lo = (_Float16)(v - (float)hi);
+}
+// one group (SDY_GROUP * 8 halves at dst) from value(row 0..31, k 0..15): the unscaled element, 0 outside the matrix
+template <class F>
+static inline void sdy_h3_put_group(_Float16* dst, float s, F&& value) {
+  for (int ln = 0; ln < 64; ++ln)
+    for (int e = 0; e < 8; ++e) sdy_h3_split(value(ln & 31, 8 * (ln >> 5) + e) * s, dst[ln * 8 + e], dst[64 * 8 + ln * 8 + e]);
+}
 // Sticky status word of a device (include/sdy_amd.h, sdy_status_flags): bits are only ever set by kernels.
 #define SDY_F16_LIMIT 65504.0f
 __device__ __forceinline__ void sdy_flag_range(unsigned* flags, float amax) {

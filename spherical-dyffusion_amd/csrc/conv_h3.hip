@@ -19,15 +19,12 @@
 
 #include "common.h"
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
 namespace {
 
 constexpr int CE = 256;          // output channels
 constexpr int CTN = 64;          // pixels per tile
 constexpr int CKMAX = 384;       // input channels supported
 constexpr int CRING = 4;         // weight groups in flight: one "window" of the stream
-constexpr int CGROUP = 2 * 64;   // f16x8 elements per group (hi | lo)
 constexpr float CSX = SDY_ACT_SX;
 constexpr int CSTAT_BYTES = CE * 2 * 8;
 #ifndef SDY_CONV_STAMP_T0
@@ -59,7 +56,7 @@ struct ConvCfg {
 struct ConvParams {
   const float* x; long x_bs;
   const float* pa; const float* pd;
-  const f16x8* w;                  // [NW waves][GPW groups][hi | lo][64 lanes]
+  const sdy_f16x8* w;              // [NW waves][GPW groups][hi | lo][64 lanes]
   const float* bias;
   const float* add; long add_bs; int add_mode;   // 1: before the activation, 2: after it
   int act;
@@ -103,10 +100,10 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void conv_h3_kernel(const
   const int t_begin = (int)blockIdx.x * t_per;
   const int t_end = (t_begin + t_per < ntiles) ? t_begin + t_per : ntiles;
 
-  f16x8 r_hi[CRING], r_lo[CRING];
+  sdy_f16x8 r_hi[CRING], r_lo[CRING];
   // ring loads: (wave-uniform stream base in SGPRs) + (the lane's running offset), sdy_ring_ld in common.h; the stream of a
   // tile (NWIN windows of CRING groups) is fetched front to back, one window ahead of its use, and wraps
-  constexpr int CGROUP_BYTES = CGROUP * (int)sizeof(f16x8);
+  constexpr int CGROUP_BYTES = SDY_GROUP * (int)sizeof(sdy_f16x8);
   const char* const wbase = reinterpret_cast<const char*>(p.w) + (size_t)__builtin_amdgcn_readfirstlane(wave) * CGPW * CGROUP_BYTES;
   unsigned woff = (unsigned)lane * 16u;
 #pragma unroll
@@ -203,14 +200,14 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void conv_h3_kernel(const
         }
 #pragma unroll
         for (int pp = 0; pp < 4; ++pp) {
-          f16x8 vh, vl;
+          sdy_f16x8 vh, vl;
           float v[8];
 #pragma unroll
           for (int e = 0; e < 8; ++e) v[e] = (ok && c0 + e < p.Cin) ? fmaf(xr[oc][e][pp], av[e], dv[e]) : 0.0f;
           sdy_split8(v, vh, vl, amax);
           const int off = cv_off<KROW>(4 * q0 + pp, o0 + CRS * oc);
-          *reinterpret_cast<f16x8*>(Xs_hi + off) = vh;
-          *reinterpret_cast<f16x8*>(Xs_lo + off) = vl;
+          *reinterpret_cast<sdy_f16x8*>(Xs_hi + off) = vh;
+          *reinterpret_cast<sdy_f16x8*>(Xs_lo + off) = vl;
         }
       }
       sdy_flag_range(p.flags, amax, p.head);
@@ -246,12 +243,12 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void conv_h3_kernel(const
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int ks = 4 * kb + i;
-        f16x8 bh[2], bl[2];
+        sdy_f16x8 bh[2], bl[2];
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
           const int off = cv_off<KROW>(32 * j + l31, 2 * ks + h);
-          bh[j] = *reinterpret_cast<const f16x8*>(Xs_hi + off);
-          bl[j] = *reinterpret_cast<const f16x8*>(Xs_lo + off);
+          bh[j] = *reinterpret_cast<const sdy_f16x8*>(Xs_hi + off);
+          bl[j] = *reinterpret_cast<const sdy_f16x8*>(Xs_lo + off);
         }
 #pragma unroll
         for (int mi = 0; mi < CMT; ++mi) {
@@ -374,37 +371,26 @@ static void conv_layout(int Cin, int* nw, int* ksw, int* mt) {
 extern "C" size_t sdy_conv256_h3_pack_bytes_cin(int Cin) {
   int nw, ksw, mt;
   conv_layout(Cin < 1 ? 1 : Cin, &nw, &ksw, &mt);
-  return (size_t)nw * mt * ksw * CGROUP * sizeof(f16x8);
+  return (size_t)nw * mt * ksw * SDY_GROUP * sizeof(sdy_f16x8);
 }
 extern "C" size_t sdy_conv256_h3_pack_bytes(void) { return sdy_conv256_h3_pack_bytes_cin(CE); }
 
 // w_host: (256, Cin) row-major (Cout, Cin), Cin <= 384 (zero-padded in the stream)
 extern "C" int sdy_conv256_h3_pack_cin(const float* w_host, int Cin, void* dev, float* scale) {
   if (!w_host || !dev || !scale || Cin < 1 || Cin > CKMAX) return SDY_ERR_ARG;
-  float mx = 0.f;
-  for (int i = 0; i < CE * Cin; ++i) mx = std::fmax(mx, std::fabs(w_host[i]));
-  float s = 1.0f;
-  if (mx > 0.f && std::isfinite(mx)) {
-    int e;
-    std::frexp(mx, &e);
-    s = std::ldexp(1.0f, 13 - e);
-  }
+  const float s = sdy_h3_scale(sdy_h3_absmax(w_host, (size_t)CE * Cin));
   int nw, ksw, mt;
   conv_layout(Cin, &nw, &ksw, &mt);
-  const size_t gh = (size_t)CGROUP * 8;
+  const size_t gh = (size_t)SDY_GROUP * 8;
   std::vector<_Float16> buf((size_t)nw * mt * ksw * gh);
   _Float16* d = buf.data();
   for (int w = 0; w < nw; ++w)
     for (int ks = 0; ks < ksw; ++ks)
       for (int mi = 0; mi < mt; ++mi, d += gh)
-        for (int ln = 0; ln < 64; ++ln)
-          for (int e = 0; e < 8; ++e) {
-            const int kk = 16 * ks + 8 * (ln >> 5) + e;
-            const float v = kk < Cin ? w_host[(size_t)(32 * (mt * w + mi) + (ln & 31)) * Cin + kk] * s : 0.0f;
-            const _Float16 hv = (_Float16)v;
-            d[ln * 8 + e] = hv;
-            d[64 * 8 + ln * 8 + e] = (_Float16)(v - (float)hv);
-          }
+        sdy_h3_put_group(d, s, [&](int r, int k) {
+          const int kk = 16 * ks + k;
+          return kk < Cin ? w_host[(size_t)(32 * (mt * w + mi) + r) * Cin + kk] : 0.0f;
+        });
   SDY_HIP_TRY(hipMemcpy(dev, buf.data(), buf.size() * sizeof(_Float16), hipMemcpyHostToDevice));
   *scale = s;
   return SDY_OK;
@@ -430,7 +416,7 @@ int sdy_conv256_h3_launch(const sdy_conv_args* a, hipStream_t stream) {
   if ((long)a->HW * CKMAX * 4 >= (1L << 32)) return SDY_ERR_UNSUPPORTED;   // 32-bit lane offsets inside an image
   ConvParams p;
   p.x = a->x; p.x_bs = a->x_bstride; p.pa = a->pa; p.pd = a->pd;
-  p.w = reinterpret_cast<const f16x8*>(a->w_frag);
+  p.w = reinterpret_cast<const sdy_f16x8*>(a->w_frag);
   p.bias = a->bias;
   p.add = a->add_mode ? a->add : nullptr; p.add_bs = a->add_bstride; p.add_mode = a->add_mode;
   p.act = a->act;

@@ -26,8 +26,6 @@
 
 #include "common.h"
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
 namespace {
 
 constexpr int DE = 256;            // channels in = out
@@ -38,14 +36,13 @@ constexpr int DCB = DE / 16;       // blocks of 16 input channels (16): one re k
 constexpr int DWAVES = 8;
 constexpr int DRING = 8;           // groups in flight (4 channel blocks x (wr, wi))
 constexpr int DGPW = 2 * DCB;      // groups per wave and degree (32)
-constexpr int DGROUP = 2 * 64;     // f16x8 elements per group (hi | lo)
-constexpr long DLSTRIDE = (long)DWAVES * DGPW * DGROUP;   // f16x8 elements per degree (512 KB)
+constexpr long DLSTRIDE = (long)DWAVES * DGPW * SDY_GROUP;   // sdy_f16x8 elements per degree (512 KB)
 constexpr float DSX = SDY_ACT_SX;
 
 struct DhParams {
   const float* X; long sX;         // Cs_in,  per-degree stride (floats)
   float* out; long sC;             // Cs_out, per-degree stride
-  const f16x8* w;                  // [l][8 waves][16 channel blocks][wr | wi][hi | lo][64 lanes]
+  const sdy_f16x8* w;              // [l][8 waves][16 channel blocks][wr | wi][hi | lo][64 lanes]
   int L, mtr, B;
   int ilv;                         // order of the 2C axis: 0 = [ri][c], 1 = [c / 16][ri][16] (fft.h)
   int tiled;                       // coefficient tensors TILE-MAJOR by order (ilv == 1 only): [m][column tile j][l][64] with
@@ -105,11 +102,11 @@ __global__ __launch_bounds__(512) void dh_h3_kernel(const DhParams p) {
   dh_advance(p, cur, xcd, nslots);
   if (cur.l < 0) return;
 
-  f16x8 r_hi[DRING], r_lo[DRING];
+  sdy_f16x8 r_hi[DRING], r_lo[DRING];
   // ring loads: (wave-uniform stream base of the degree in SGPRs) + (the lane's running offset), sdy_ring_ld in common.h
-  constexpr int DGROUP_BYTES = DGROUP * (int)sizeof(f16x8);
+  constexpr int DGROUP_BYTES = SDY_GROUP * (int)sizeof(sdy_f16x8);
   auto w_base = [&](int l) {
-    return reinterpret_cast<const char*>(p.w) + ((size_t)l * DLSTRIDE + (size_t)wave * DGPW * DGROUP) * sizeof(f16x8);
+    return reinterpret_cast<const char*>(p.w) + ((size_t)l * DLSTRIDE + (size_t)wave * DGPW * SDY_GROUP) * sizeof(sdy_f16x8);
   };
   const char* wbase = w_base(cur.l);
   unsigned woff = (unsigned)lane * 16u;
@@ -167,14 +164,14 @@ __global__ __launch_bounds__(512) void dh_h3_kernel(const DhParams p) {
     for (int i = 0; i < 8; ++i) {
       const int r = r0 + 8 * i;
       const float sc = (row0 + r < M) ? DSX : 0.0f;   // rows past the ragged edge (clamped re-reads of a valid row): zero
-      f16x8 vh, vl;
+      sdy_f16x8 vh, vl;
       float v[8];
 #pragma unroll
       for (int e = 0; e < 8; ++e) v[e] = xr[i][e >> 2][e & 3] * sc;
       sdy_split8(v, vh, vl, amax);
       const int off = dh_off(r, oc);
-      *reinterpret_cast<f16x8*>(Xs_hi + off) = vh;
-      *reinterpret_cast<f16x8*>(Xs_lo + off) = vl;
+      *reinterpret_cast<sdy_f16x8*>(Xs_hi + off) = vh;
+      *reinterpret_cast<sdy_f16x8*>(Xs_lo + off) = vl;
     }
     sdy_flag_range(p.flags, amax, p.head_in);
     stamp(1);
@@ -194,7 +191,7 @@ __global__ __launch_bounds__(512) void dh_h3_kernel(const DhParams p) {
       for (int j = 0; j < 2; ++j)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[t][j][r] = 0.0f;
-    auto mma3 = [&](f32x16& c, const f16x8& ah, const f16x8& al, const f16x8& bhi, const f16x8& blo) {
+    auto mma3 = [&](f32x16& c, const sdy_f16x8& ah, const sdy_f16x8& al, const sdy_f16x8& bhi, const sdy_f16x8& blo) {
       SDY_CROSS_TERM(c = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bhi, c, 0, 0, 0));
       SDY_CROSS_TERM(c = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, blo, c, 0, 0, 0));
       c = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bhi, c, 0, 0, 0);
@@ -203,13 +200,13 @@ __global__ __launch_bounds__(512) void dh_h3_kernel(const DhParams p) {
     // profiles/r4c/e2e_ab_dh_frag_ahead.txt): x_im's of a channel block are requested before the MFMAs on x_re run, the next
     // block's x_re before those on x_im -- a wave that has the SIMD to itself (the younger four at the end of the phase, all of
     // them whenever their partner waits) no longer sits out an LDS round trip per half block.
-    f16x8 fa_h[2], fa_l[2], fb_h[2], fb_l[2];
-    auto ld_frags = [&](f16x8* fh, f16x8* fl, int kstep) {
+    sdy_f16x8 fa_h[2], fa_l[2], fb_h[2], fb_l[2];
+    auto ld_frags = [&](sdy_f16x8* fh, sdy_f16x8* fl, int kstep) {
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         const int off = dh_off(32 * j + l31, 2 * kstep + h);
-        fh[j] = *reinterpret_cast<const f16x8*>(Xs_hi + off);
-        fl[j] = *reinterpret_cast<const f16x8*>(Xs_lo + off);
+        fh[j] = *reinterpret_cast<const sdy_f16x8*>(Xs_hi + off);
+        fl[j] = *reinterpret_cast<const sdy_f16x8*>(Xs_lo + off);
       }
     };
     ld_frags(fa_h, fa_l, p.ilv ? 0 : 0);
@@ -239,8 +236,8 @@ __global__ __launch_bounds__(512) void dh_h3_kernel(const DhParams p) {
         for (int j = 0; j < 2; ++j) {   // -x_im
           typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
           u32x4 uh = __builtin_bit_cast(u32x4, fb_h[j]) ^ 0x80008000u, ul = __builtin_bit_cast(u32x4, fb_l[j]) ^ 0x80008000u;
-          fb_h[j] = __builtin_bit_cast(f16x8, uh);
-          fb_l[j] = __builtin_bit_cast(f16x8, ul);
+          fb_h[j] = __builtin_bit_cast(sdy_f16x8, uh);
+          fb_l[j] = __builtin_bit_cast(sdy_f16x8, ul);
         }
 #pragma unroll
         for (int j = 0; j < 2; ++j) mma3(acc[0][j], fb_h[j], fb_l[j], r_hi[s1], r_lo[s1]);   // re -= x_im . wi
@@ -328,37 +325,26 @@ SDY_DEBUG_EXPORT int sdy_dhconv_frag_debug_stamps(unsigned long long* host384) {
 
 extern "C" int sdy_dhconv_frag_supported(int Ci, int Co) { return (Ci == DE && Co == DE) ? 1 : 0; }
 
-extern "C" size_t sdy_dhconv_frag_pack_bytes(int L) { return L > 0 ? (size_t)L * DLSTRIDE * sizeof(f16x8) : 0; }
+extern "C" size_t sdy_dhconv_frag_pack_bytes(int L) { return L > 0 ? (size_t)L * DLSTRIDE * sizeof(sdy_f16x8) : 0; }
 
 // w_host: (256, 256, L, 2) reference layout (i, o, l, re | im).  The stream does not depend on the order of the 2C axis
 // (the kernel maps its k-steps and output columns); `ilv` is accepted for the caller's convenience and ignored.
 int sdy_dh_h3_pack(const float* w, int L, void* dev, float* scale, int ilv) {
   (void)ilv;
   if (!w || !dev || !scale || L <= 0) return SDY_ERR_ARG;
-  float mx = 0.f;
-  for (size_t i = 0; i < (size_t)DE * DE * L * 2; ++i) mx = std::fmax(mx, std::fabs(w[i]));
-  float s = 1.0f;
-  if (mx > 0.f && std::isfinite(mx)) {
-    int e;
-    std::frexp(mx, &e);
-    s = std::ldexp(1.0f, 13 - e);
-  }
-  const size_t gh = (size_t)DGROUP * 8;   // halves per group
+  const float s = sdy_h3_scale(sdy_h3_absmax(w, (size_t)DE * DE * L * 2));
+  const size_t gh = (size_t)SDY_GROUP * 8;   // halves per group
   std::vector<_Float16> buf((size_t)DWAVES * DGPW * gh);
   for (int l = 0; l < L; ++l) {
     _Float16* d = buf.data();
     for (int wv = 0; wv < DWAVES; ++wv)
       for (int cb = 0; cb < DCB; ++cb)
         for (int comp = 0; comp < 2; ++comp, d += gh)
-          for (int ln = 0; ln < 64; ++ln)
-            for (int e = 0; e < 8; ++e) {
-              const int i = 16 * cb + 8 * (ln >> 5) + e, o = 32 * wv + (ln & 31);
-              const float v = w[(((size_t)i * DE + o) * L + l) * 2 + comp] * s;
-              const _Float16 hv = (_Float16)v;
-              d[ln * 8 + e] = hv;
-              d[64 * 8 + ln * 8 + e] = (_Float16)(v - (float)hv);
-            }
-    SDY_HIP_TRY(hipMemcpy(reinterpret_cast<char*>(dev) + (size_t)l * DLSTRIDE * sizeof(f16x8), buf.data(),
+          sdy_h3_put_group(d, s, [&](int r, int k) {
+            const int i = 16 * cb + k, o = 32 * wv + r;
+            return w[(((size_t)i * DE + o) * L + l) * 2 + comp];
+          });
+    SDY_HIP_TRY(hipMemcpy(reinterpret_cast<char*>(dev) + (size_t)l * DLSTRIDE * sizeof(sdy_f16x8), buf.data(),
                           buf.size() * sizeof(_Float16), hipMemcpyHostToDevice));
   }
   *scale = s;
@@ -377,7 +363,7 @@ int sdy_dh_h3_launch(const float* Cs_in, const void* packed, float scale, float*
   DhParams p;
   p.X = Cs_in; p.sX = (long)mtr * B * DK;
   p.out = Cs_out; p.sC = (long)mtr * B * DN;
-  p.w = reinterpret_cast<const f16x8*>(packed);
+  p.w = reinterpret_cast<const sdy_f16x8*>(packed);
   p.L = L; p.mtr = mtr; p.B = B; p.ilv = ilv ? 1 : 0; p.tiled = tiled ? 1 : 0;
   p.B_in = B_in; p.b_magic = (unsigned)((1ull << 32) / (unsigned)B) + 1u;
   p.out_scale = 1.0f / (scale * DSX);

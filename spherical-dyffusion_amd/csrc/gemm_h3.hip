@@ -26,7 +26,6 @@
 #include "common.h"
 #include "gemm_epilogue.h"
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
 namespace {
@@ -252,18 +251,18 @@ __global__ __launch_bounds__(256, 2) void gemm_h3_kernel(const GemmParams p, con
   auto compute_tile = [&]() {
 #pragma unroll
     for (int s = 0; s < HBK / 16; ++s) {
-      f16x8 ah[WM], al[WM], bh[WN], bl[WN];
+      sdy_f16x8 ah[WM], al[WM], bh[WN], bl[WN];
 #pragma unroll
       for (int i = 0; i < WM; ++i) {
         const int off = (wr * (32 * WM) + i * 32 + l31) * HLD + s * 16 + h * 8;
-        ah[i] = *reinterpret_cast<const f16x8*>(As_hi + off);
-        al[i] = *reinterpret_cast<const f16x8*>(As_lo + off);
+        ah[i] = *reinterpret_cast<const sdy_f16x8*>(As_hi + off);
+        al[i] = *reinterpret_cast<const sdy_f16x8*>(As_lo + off);
       }
 #pragma unroll
       for (int j = 0; j < WN; ++j) {
         const int off = (wc * (32 * WN) + j * 32 + l31) * HLD + s * 16 + h * 8;
-        bh[j] = *reinterpret_cast<const f16x8*>(Bs_hi + off);
-        bl[j] = *reinterpret_cast<const f16x8*>(Bs_lo + off);
+        bh[j] = *reinterpret_cast<const sdy_f16x8*>(Bs_hi + off);
+        bl[j] = *reinterpret_cast<const sdy_f16x8*>(Bs_lo + off);
       }
 #pragma unroll
       for (int i = 0; i < WM; ++i)
@@ -449,18 +448,18 @@ __global__ __launch_bounds__(512) void gemm_h3_wide_kernel(const GemmParams p, c
     if (!wave_dead) {
 #pragma unroll
       for (int s = 0; s < WBK / 16; ++s) {
-        f16x8 ah[WM], al[WM], bh[WN], bl[WN];
+        sdy_f16x8 ah[WM], al[WM], bh[WN], bl[WN];
 #pragma unroll
         for (int i = 0; i < WM; ++i) {
           const int off = (wr * 64 + i * 32 + l31) * WLD + s * 16 + h * 8;
-          ah[i] = *reinterpret_cast<const f16x8*>(As_hi + off);
-          al[i] = *reinterpret_cast<const f16x8*>(As_lo + off);
+          ah[i] = *reinterpret_cast<const sdy_f16x8*>(As_hi + off);
+          al[i] = *reinterpret_cast<const sdy_f16x8*>(As_lo + off);
         }
 #pragma unroll
         for (int j = 0; j < WN; ++j) {
           const int off = (wc * 64 + j * 32 + l31) * WLD + s * 16 + h * 8;
-          bh[j] = *reinterpret_cast<const f16x8*>(Bs_hi + off);
-          bl[j] = *reinterpret_cast<const f16x8*>(Bs_lo + off);
+          bh[j] = *reinterpret_cast<const sdy_f16x8*>(Bs_hi + off);
+          bl[j] = *reinterpret_cast<const sdy_f16x8*>(Bs_lo + off);
         }
 #pragma unroll
         for (int i = 0; i < WM; ++i)

@@ -16,8 +16,6 @@
 
 #include "common.h"
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
 namespace {
 
 constexpr int LM = 192;          // rows per workgroup (>= lmax, nlat)
@@ -26,11 +24,10 @@ constexpr int LTN = 64;          // columns per workgroup
 constexpr int LKS = 12;          // k-steps of 16
 constexpr int LRING = 8;         // groups in flight = one block of 4 k-steps x 2 m-tiles
 constexpr int LGPW = 2 * LKS;    // groups per (m, wave)
-constexpr int LGROUP = 2 * 64;   // f16x8 elements per group
 constexpr float LSX = SDY_ACT_SX;
 
 struct LegParams {
-  const f16x8* table;            // [nz][3 waves][LGPW groups][hi | lo][64 lanes] (+ LRING groups of padding)
+  const sdy_f16x8* table;        // [nz][3 waves][LGPW groups][hi | lo][64 lanes] (+ LRING groups of padding)
   const float* X; long ldx, sX;  // activations: row k at X + z * sX + k * ldx, columns contiguous
   float* C; long ldc, sC;        // result: row r at C + z * sC + r * ldc
   int M_store, K, N;
@@ -64,14 +61,14 @@ __global__ __launch_bounds__(192, 3) void leg_h3_kernel(const LegParams p) {
   const int k_lo = fwd ? 0 : z;                          // synthesis: rows l < m of the coefficients were never written
 
   // ---- table ring (slot = 2 * (k-step % 4) + m-tile)
-  f16x8 r_hi[LRING], r_lo[LRING];
-  const f16x8* __restrict__ wp = p.table + ((size_t)(z * 3 + wave) * LGPW + 8 * kb0) * LGROUP + lane;
+  sdy_f16x8 r_hi[LRING], r_lo[LRING];
+  const sdy_f16x8* __restrict__ wp = p.table + ((size_t)(z * 3 + wave) * LGPW + 8 * kb0) * SDY_GROUP + lane;
 #pragma unroll
   for (int s = 0; s < LRING; ++s) {
-    r_hi[s] = wp[s * LGROUP];
-    r_lo[s] = wp[s * LGROUP + 64];
+    r_hi[s] = wp[s * SDY_GROUP];
+    r_lo[s] = wp[s * SDY_GROUP + 64];
   }
-  wp += LRING * LGROUP;
+  wp += LRING * SDY_GROUP;
 
   // ---- phase 0: activation tile -> LDS (fp16 hi / lo, [n][k]); thread = (column quad q, octets o and o + 12)
   {
@@ -93,7 +90,7 @@ __global__ __launch_bounds__(192, 3) void leg_h3_kernel(const LegParams p) {
       const int c = o + 12 * oc;
 #pragma unroll
       for (int pp = 0; pp < 4; ++pp) {
-        f16x8 vh, vl;
+        sdy_f16x8 vh, vl;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
           const int k = 8 * c + e;
@@ -104,8 +101,8 @@ __global__ __launch_bounds__(192, 3) void leg_h3_kernel(const LegParams p) {
           vl[e] = (_Float16)(v - (float)hv);
         }
         const int off = lg_off(4 * q + pp, c);
-        *reinterpret_cast<f16x8*>(Xs_hi + off) = vh;
-        *reinterpret_cast<f16x8*>(Xs_lo + off) = vl;
+        *reinterpret_cast<sdy_f16x8*>(Xs_hi + off) = vh;
+        *reinterpret_cast<sdy_f16x8*>(Xs_lo + off) = vl;
       }
     }
     sdy_flag_range(p.flags, amax);
@@ -125,12 +122,12 @@ __global__ __launch_bounds__(192, 3) void leg_h3_kernel(const LegParams p) {
     for (int i = 0; i < 4; ++i) {
       const int ks = 4 * kb + i;
       if (!wave_dead && ks >= ks0) {
-        f16x8 bh[2], bl[2];
+        sdy_f16x8 bh[2], bl[2];
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
           const int off = lg_off(32 * j + l31, 2 * ks + h);
-          bh[j] = *reinterpret_cast<const f16x8*>(Xs_hi + off);
-          bl[j] = *reinterpret_cast<const f16x8*>(Xs_lo + off);
+          bh[j] = *reinterpret_cast<const sdy_f16x8*>(Xs_hi + off);
+          bl[j] = *reinterpret_cast<const sdy_f16x8*>(Xs_lo + off);
         }
 #pragma unroll
         for (int mi = 0; mi < 2; ++mi) {
@@ -146,12 +143,12 @@ __global__ __launch_bounds__(192, 3) void leg_h3_kernel(const LegParams p) {
 #pragma unroll
       for (int mi = 0; mi < 2; ++mi) {
         const int s = 2 * i + mi;
-        r_hi[s] = wp[s * LGROUP];
-        r_lo[s] = wp[s * LGROUP + 64];
+        r_hi[s] = wp[s * SDY_GROUP];
+        r_lo[s] = wp[s * SDY_GROUP + 64];
       }
       __builtin_amdgcn_sched_barrier(0);   // keep the refill here (the scheduler otherwise sinks it next to its use)
     }
-    wp += LRING * LGROUP;
+    wp += LRING * SDY_GROUP;
   }
 
   // ---- epilogue: accumulators -> LDS [row][col] -> 16-byte row stores of the live rows
@@ -185,7 +182,7 @@ __global__ __launch_bounds__(192, 3) void leg_h3_kernel(const LegParams p) {
 
 }  // namespace
 
-size_t sdy_leg_h3_table_bytes(int nz) { return ((size_t)nz * 3 * LGPW + LRING) * LGROUP * sizeof(f16x8); }
+size_t sdy_leg_h3_table_bytes(int nz) { return ((size_t)nz * 3 * LGPW + LRING) * SDY_GROUP * sizeof(sdy_f16x8); }
 
 int sdy_leg_h3_supported(int rows, int K) { return (rows <= LM && K <= LKS * 16) ? 1 : 0; }
 
@@ -196,27 +193,18 @@ int sdy_leg_h3_pack(int nz, int rows, int K, sdy_leg_value_fn value, void* ctx, 
   for (int z = 0; z < nz; ++z)
     for (int r = 0; r < rows; ++r)
       for (int k = 0; k < K; ++k) mx = std::fmax(mx, std::fabs(value(ctx, z, r, k)));
-  float s = 1.0f;
-  if (mx > 0.f && std::isfinite(mx)) {
-    int e;
-    std::frexp(mx, &e);
-    s = std::ldexp(1.0f, 13 - e);
-  }
-  const size_t gh = (size_t)LGROUP * 8;
+  const float s = sdy_h3_scale(mx);
+  const size_t gh = (size_t)SDY_GROUP * 8;
   std::vector<_Float16> buf(((size_t)nz * 3 * LGPW + LRING) * gh, (_Float16)0.0f);
   for (int z = 0; z < nz; ++z)
     for (int w = 0; w < 3; ++w) {
       _Float16* d = buf.data() + (size_t)(z * 3 + w) * LGPW * gh;
       for (int ks = 0; ks < LKS; ++ks)
         for (int mi = 0; mi < 2; ++mi, d += gh)
-          for (int ln = 0; ln < 64; ++ln)
-            for (int e = 0; e < 8; ++e) {
-              const int row = 64 * w + 32 * mi + (ln & 31), k = 16 * ks + 8 * (ln >> 5) + e;
-              const float v = (row < rows && k < K) ? value(ctx, z, row, k) * s : 0.0f;
-              const _Float16 hv = (_Float16)v;
-              d[ln * 8 + e] = hv;
-              d[64 * 8 + ln * 8 + e] = (_Float16)(v - (float)hv);
-            }
+          sdy_h3_put_group(d, s, [&](int r, int k) {
+            const int row = 64 * w + 32 * mi + r, kk = 16 * ks + k;
+            return (row < rows && kk < K) ? value(ctx, z, row, kk) : 0.0f;
+          });
     }
   SDY_HIP_TRY(hipMemcpy(dev, buf.data(), buf.size() * sizeof(_Float16), hipMemcpyHostToDevice));
   *scale = s;
@@ -230,7 +218,7 @@ int sdy_leg_h3_launch(const void* table, float scale, int nz, const float* X, lo
   if ((N & 3) || (ldx & 3) || (sX & 3) || (ldc & 3) || (sC & 3)) return SDY_ERR_ALIGN;
   if (tri != SDY_TRI_LEG_FWD && tri != SDY_TRI_LEG_INV) return SDY_ERR_ARG;
   LegParams p;
-  p.table = reinterpret_cast<const f16x8*>(table);
+  p.table = reinterpret_cast<const sdy_f16x8*>(table);
   p.X = X; p.ldx = ldx; p.sX = sX;
   p.C = C; p.ldc = ldc; p.sC = sC;
   p.M_store = M_store; p.K = K; p.N = N; p.tri = tri;

@@ -22,8 +22,6 @@
 
 #include "common.h"
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
 namespace {
 
 constexpr int PM = 192;          // output rows a workgroup covers
@@ -32,11 +30,10 @@ constexpr int PTN = 64;          // columns per workgroup
 constexpr int PKS = 6;           // k-steps of 16 per half
 constexpr int PRING = 8;         // groups in flight = 4 k-steps x (E, O)
 constexpr int PGPW = 2 * PKS;    // groups per (m, wave)
-constexpr int PGROUP = 2 * 64;   // f16x8 elements per group
 constexpr float PSX = SDY_ACT_SX;
 
 struct ParParams {
-  const f16x8* table;            // [nz][3 waves][PGPW groups: (k-step, E | O)][hi | lo][64 lanes]
+  const sdy_f16x8* table;        // [nz][3 waves][PGPW groups: (k-step, E | O)][hi | lo][64 lanes]
   const float* X; long ldx, sX;  // input rows (latitudes / degrees) at X + z * sX + row * ldx, columns contiguous
   float* C; long ldc, sC;        // output rows at C + z * sC + row * ldc
   long tsx, tsc;                 // != 0: that side is TILE-MAJOR (fft.h, ilv == 2): the workgroup's 64 columns start at
@@ -88,9 +85,9 @@ __global__ __launch_bounds__(192, 3) void leg_par_kernel(const ParParams p) {
   stamp(0);
 
   // ---- table ring (slot = 2 * (k-step % 4) + half)
-  f16x8 r_hi[PRING], r_lo[PRING];
+  sdy_f16x8 r_hi[PRING], r_lo[PRING];
   // (wave-uniform stream base in SGPRs) + (the lane's running offset): sdy_ring_ld in common.h
-  constexpr int PGROUP_BYTES = PGROUP * (int)sizeof(f16x8);
+  constexpr int PGROUP_BYTES = SDY_GROUP * (int)sizeof(sdy_f16x8);
   const char* const wbase = reinterpret_cast<const char*>(p.table) +
                             (size_t)__builtin_amdgcn_readfirstlane(z * 3 + wave) * PGPW * PGROUP_BYTES;
   unsigned woff = (unsigned)lane * 16u;
@@ -164,7 +161,7 @@ __global__ __launch_bounds__(192, 3) void leg_par_kernel(const ParParams p) {
     for (int hf = 0; hf < 2; ++hf) {
 #pragma unroll
       for (int pp = 0; pp < 4; ++pp) {
-        f16x8 vh, vl;
+        sdy_f16x8 vh, vl;
         float v[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
@@ -177,8 +174,8 @@ __global__ __launch_bounds__(192, 3) void leg_par_kernel(const ParParams p) {
         }
         sdy_split8(v, vh, vl);
         const int off = pr_off(4 * q + pp, o + 12 * hf);
-        *reinterpret_cast<f16x8*>(Xs_hi + off) = vh;
-        *reinterpret_cast<f16x8*>(Xs_lo + off) = vl;
+        *reinterpret_cast<sdy_f16x8*>(Xs_hi + off) = vh;
+        *reinterpret_cast<sdy_f16x8*>(Xs_lo + off) = vl;
       }
     }
   }
@@ -199,12 +196,12 @@ __global__ __launch_bounds__(192, 3) void leg_par_kernel(const ParParams p) {
     if (ks >= ks0) {
 #pragma unroll
       for (int hf = 0; hf < 2; ++hf) {
-        f16x8 bh[2], bl[2];
+        sdy_f16x8 bh[2], bl[2];
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
           const int off = pr_off(32 * j + l31, 12 * hf + 2 * ks + h);
-          bh[j] = *reinterpret_cast<const f16x8*>(Xs_hi + off);
-          bl[j] = *reinterpret_cast<const f16x8*>(Xs_lo + off);
+          bh[j] = *reinterpret_cast<const sdy_f16x8*>(Xs_hi + off);
+          bl[j] = *reinterpret_cast<const sdy_f16x8*>(Xs_lo + off);
         }
         const int s = 2 * (ks & 3) + hf;
 #pragma unroll
@@ -314,7 +311,7 @@ SDY_DEBUG_EXPORT int sdy_leg_par_debug_stamps(unsigned long long* host96) {
 }
 #endif
 
-size_t sdy_leg_par_table_bytes(int nz) { return ((size_t)nz * 3 * PGPW + PRING) * PGROUP * sizeof(f16x8); }
+size_t sdy_leg_par_table_bytes(int nz) { return ((size_t)nz * 3 * PGPW + PRING) * SDY_GROUP * sizeof(sdy_f16x8); }
 
 // rows_out x K problem of leg_h3 (analysis: lmax x nlat, synthesis: nlat x lmax); the folded axis (nlat) must be even
 // (nlat, lmax >= 16: inside a live octet of the load phase every row is then in bounds, see the kernel)
@@ -331,13 +328,8 @@ int sdy_leg_par_pack(int nz, int nlat, int lmax, int fwd, sdy_leg_value_fn value
   for (int z = 0; z < nz; ++z)
     for (int l = 0; l < lmax; ++l)
       for (int k = 0; k < Kh; ++k) mx = std::fmax(mx, std::fabs(fwd ? value(ctx, z, l, k) : value(ctx, z, k, l)));
-  float s = 1.0f;
-  if (mx > 0.f && std::isfinite(mx)) {
-    int e;
-    std::frexp(mx, &e);
-    s = std::ldexp(1.0f, 13 - e);
-  }
-  const size_t gh = (size_t)PGROUP * 8;
+  const float s = sdy_h3_scale(mx);
+  const size_t gh = (size_t)SDY_GROUP * 8;
   std::vector<_Float16> buf(((size_t)nz * 3 * PGPW + PRING) * gh, (_Float16)0.0f);
   for (int z = 0; z < nz; ++z) {
     const int cE = z & 1;
@@ -346,21 +338,15 @@ int sdy_leg_par_pack(int nz, int nlat, int lmax, int fwd, sdy_leg_value_fn value
       for (int ks = 0; ks < PKS; ++ks)
         for (int hf = 0; hf < 2; ++hf, d += gh) {
           const int cls = hf == 0 ? cE : cE ^ 1;
-          for (int ln = 0; ln < 64; ++ln)
-            for (int e = 0; e < 8; ++e) {
-              const int rt = 32 * w + (ln & 31), kk = 16 * ks + 8 * (ln >> 5) + e;
-              float v = 0.0f;
-              if (fwd) {   // row: degree 2 rt + cls, contraction: latitude kk of the first hemisphere
-                const int l = 2 * rt + cls;
-                if (l < lmax && kk < Kh) v = value(ctx, z, l, kk) * s;
-              } else {     // row: latitude rt, contraction: degree 2 kk + cls
-                const int l = 2 * kk + cls;
-                if (rt < Kh && l < lmax) v = value(ctx, z, rt, l) * s;
-              }
-              const _Float16 hv = (_Float16)v;
-              d[ln * 8 + e] = hv;
-              d[64 * 8 + ln * 8 + e] = (_Float16)(v - (float)hv);
+          sdy_h3_put_group(d, s, [&](int r, int k) {
+            const int rt = 32 * w + r, kk = 16 * ks + k;
+            if (fwd) {   // row: degree 2 rt + cls, contraction: latitude kk of the first hemisphere
+              const int l = 2 * rt + cls;
+              return (l < lmax && kk < Kh) ? value(ctx, z, l, kk) : 0.0f;
             }
+            const int l = 2 * kk + cls;   // row: latitude rt, contraction: degree 2 kk + cls
+            return (rt < Kh && l < lmax) ? value(ctx, z, rt, l) : 0.0f;
+          });
         }
     }
   }
@@ -377,7 +363,7 @@ int sdy_leg_par_launch(const void* table, float scale, int nz, const float* X, l
   if ((fwd ? K : rows_out) & 1) return SDY_ERR_UNSUPPORTED;
   if ((N & 3) || (ldx & 3) || (sX & 3) || (ldc & 3) || (sC & 3)) return SDY_ERR_ALIGN;
   ParParams p;
-  p.table = reinterpret_cast<const f16x8*>(table);
+  p.table = reinterpret_cast<const sdy_f16x8*>(table);
   p.X = X; p.ldx = ldx; p.sX = sX;
   p.C = C; p.ldc = ldc; p.sC = sC;
   p.tsx = tsx; p.tsc = tsc;

@@ -32,10 +32,9 @@
 
 #include "common.h"
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 // explicit global address space: a pointer laundered through an empty asm loses its provenance, and hipcc then emits
 // FLAT loads, which also count in lgkmcnt -- every LDS-fragment wait became lgkmcnt(0), i.e. a wait for the weight refills
-typedef const f16x8 __attribute__((address_space(1)))* wptr_t;
+typedef const sdy_f16x8 __attribute__((address_space(1)))* wptr_t;
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
 namespace {
@@ -51,13 +50,12 @@ constexpr int RING = 16;                // groups in flight = groups per block (
 constexpr int NGROUPS = NCH * 2 * RING;      // 128
 static_assert(KS1 == RING && 2 * KSC == RING, "ring slot = index inside a block");
 constexpr float SX = SDY_ACT_SX;    // activation pre-scale (keeps lo parts out of the fp16 subnormals)
-constexpr int GROUP_F8 = 2 * 64;        // f16x8 elements per group (hi fragment, lo fragment)
 
 struct MlpParams {
   const float* x; long x_bs;
   int x_tiled;                             // x TILE-MAJOR: [b][64-pixel tile][256 rows][64] (sdy_mlp_args.x_tiled), x_bs per image
   const float* pa; const float* pd;
-  const f16x8* w;                          // [4 waves][NGROUPS + RING groups][hi | lo][64 lanes]
+  const sdy_f16x8* w;                      // [4 waves][NGROUPS + RING groups][hi | lo][64 lanes]
   const float* b1; const float* b2;
   float* out; long out_bs;
   const float* add; long add_bs;
@@ -117,16 +115,16 @@ __global__ __launch_bounds__(256, 1) void mlp_h3_kernel(const MlpParams p) {
   bool full = true;
 
   // ---- weight ring: slot s holds group s of the block being consumed; refilled for the next block right after its use
-  f16x8 r_hi[RING], r_lo[RING];
+  sdy_f16x8 r_hi[RING], r_lo[RING];
   // (recomputed where it is needed, from a laundered lane index: kept in a register pair across the tile it is spilled)
-  auto wbase_of = [&](int ln) { return (wptr_t)(p.w + (size_t)wave * (NGROUPS + RING) * GROUP_F8 + ln); };
+  auto wbase_of = [&](int ln) { return (wptr_t)(p.w + (size_t)wave * (NGROUPS + RING) * SDY_GROUP + ln); };
   wptr_t wp = wbase_of(lane);
 #pragma unroll
   for (int s = 0; s < RING; ++s) {
-    r_hi[s] = wp[s * GROUP_F8];
-    r_lo[s] = wp[s * GROUP_F8 + 64];
+    r_hi[s] = wp[s * SDY_GROUP];
+    r_lo[s] = wp[s * SDY_GROUP + 64];
   }
-  wp += RING * GROUP_F8;   // from here on wp[i * GROUP_F8] is group i of the block AFTER the one being consumed
+  wp += RING * SDY_GROUP;   // from here on wp[i * SDY_GROUP] is group i of the block AFTER the one being consumed
 
   // ---- x tile prefetch: thread = (pixel quad q, channel octets o and o + 16)
   int q0 = tid & 15, o0 = tid >> 4;
@@ -230,14 +228,14 @@ __global__ __launch_bounds__(256, 1) void mlp_h3_kernel(const MlpParams p) {
 #pragma unroll
       for (int pp = 0; pp < 4; ++pp) {
         const int px = 4 * q0 + pp;
-        f16x8 vh, vl;
+        sdy_f16x8 vh, vl;
         float v[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = (kFull || ok) ? fmaf(xr[oc][e][pp], av[e], dv[e]) : 0.0f;
         sdy_split8(v, vh, vl, amax);
         const int off = xs_off(px, o0 + 16 * oc);
-        *reinterpret_cast<f16x8*>(Xs_hi + off) = vh;
-        *reinterpret_cast<f16x8*>(Xs_lo + off) = vl;
+        *reinterpret_cast<sdy_f16x8*>(Xs_hi + off) = vh;
+        *reinterpret_cast<sdy_f16x8*>(Xs_lo + off) = vl;
       }
     }
     sdy_flag_range(p.flags, amax, p.head);
@@ -309,12 +307,12 @@ __global__ __launch_bounds__(256, 1) void mlp_h3_kernel(const MlpParams p) {
     for (int j = 0; j < 2; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[j][r] = 0.0f;
-    f16x8 bh[2][2], bl[2][2];
+    sdy_f16x8 bh[2][2], bl[2][2];
     auto ldb1 = [&](int set, int ks, int part) {   // part: (hi j0, hi j1, lo j0, lo j1)
       const int j = part & 1;
       const int off = xs_off(32 * j + l31, 2 * ks + h);
-      if (part < 2) bh[set][j] = *reinterpret_cast<const f16x8*>(Xs_hi + off);
-      else bl[set][j] = *reinterpret_cast<const f16x8*>(Xs_lo + off);
+      if (part < 2) bh[set][j] = *reinterpret_cast<const sdy_f16x8*>(Xs_hi + off);
+      else bl[set][j] = *reinterpret_cast<const sdy_f16x8*>(Xs_lo + off);
     };
 #pragma unroll
     for (int part = 0; part < 4; ++part) ldb1(0, 0, part);
@@ -323,15 +321,15 @@ __global__ __launch_bounds__(256, 1) void mlp_h3_kernel(const MlpParams p) {
       const int c = ks & 1;
       if constexpr (SDY_MLP_PINNED) {
       __builtin_amdgcn_sched_barrier(0);
-      const f16x8 a_lo = r_lo[ks], a_hi = r_hi[ks];
+      const sdy_f16x8 a_lo = r_lo[ks], a_hi = r_hi[ks];
 #pragma unroll
       for (int k = 0; k < 6; ++k) {
         const int j = k & 1;
         if (SDY_H3_PASSES == 3 || k >= 4)   // (k < 4: the cross terms, dropped by single-pass measurement builds only)
           acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(k < 2 ? a_lo : a_hi, (k >= 2 && k < 4) ? bl[c][j] : bh[c][j], acc[j], 0, 0, 0);
         if (k < 4) { if (ks + 1 < KS1) ldb1(c ^ 1, ks + 1, k); }
-        else if (k == 4) r_lo[ks] = wp[ks * GROUP_F8 + 64];
-        else r_hi[ks] = wp[ks * GROUP_F8];
+        else if (k == 4) r_lo[ks] = wp[ks * SDY_GROUP + 64];
+        else r_hi[ks] = wp[ks * SDY_GROUP];
         if (DROP && !INJECT && (6 * ks + k) % PSTEP == 0 && (6 * ks + k) / PSTEP < 4 * PR) philox_ahead(hc_fc1, (6 * ks + k) / PSTEP);
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -346,8 +344,8 @@ __global__ __launch_bounds__(256, 1) void mlp_h3_kernel(const MlpParams p) {
       for (int j = 0; j < 2; ++j) SDY_CROSS_TERM(acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(r_hi[ks], bl[c][j], acc[j], 0, 0, 0));
 #pragma unroll
       for (int j = 0; j < 2; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(r_hi[ks], bh[c][j], acc[j], 0, 0, 0);
-      r_hi[ks] = wp[ks * GROUP_F8];
-      r_lo[ks] = wp[ks * GROUP_F8 + 64];
+      r_hi[ks] = wp[ks * SDY_GROUP];
+      r_lo[ks] = wp[ks * SDY_GROUP + 64];
       // one non-MFMA instruction per MFMA: each MFMA shadows ~24 issue cycles, bunched LDS reads / loads do not hide
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
@@ -362,7 +360,7 @@ __global__ __launch_bounds__(256, 1) void mlp_h3_kernel(const MlpParams p) {
       __builtin_amdgcn_sched_barrier(0);   // keep the refill here: the scheduler otherwise sinks it next to its use
       }
     }
-    wp += RING * GROUP_F8;
+    wp += RING * SDY_GROUP;
   };
   // One eighth of chain(hc): 4 accumulator values (tile j, row group g4): bias + exact-erf GELU (same arithmetic as
   // gelu_erf in common.h) + Philox dropout, x16, fp16 hi/lo split -> LDS.  Cut into 12 stages of a few VALU instructions
@@ -599,20 +597,20 @@ __global__ __launch_bounds__(256, 1) void mlp_h3_kernel(const MlpParams p) {
     constexpr bool CHAIN = decltype(with_chain)::value;
     const _Float16* Hh = Hs + (hc2 & 1) * (2 * TN * HC);
     const _Float16* Hl = Hh + TN * HC;
-    f16x8 bh[2][2], bl[2][2];
+    sdy_f16x8 bh[2][2], bl[2][2];
     auto ldb = [&](int set, int t) {
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         const int off = hs_off(32 * j + l31, 2 * t + h);
-        bh[set][j] = *reinterpret_cast<const f16x8*>(Hh + off);
-        bl[set][j] = *reinterpret_cast<const f16x8*>(Hl + off);
+        bh[set][j] = *reinterpret_cast<const sdy_f16x8*>(Hh + off);
+        bl[set][j] = *reinterpret_cast<const sdy_f16x8*>(Hl + off);
       }
     };
     auto ldb1 = [&](int set, int t, int part) {   // one of a k-step's four fragment reads: (hi j0, hi j1, lo j0, lo j1)
       const int j = part & 1;
       const int off = hs_off(32 * j + l31, 2 * t + h);
-      if (part < 2) bh[set][j] = *reinterpret_cast<const f16x8*>(Hh + off);
-      else bl[set][j] = *reinterpret_cast<const f16x8*>(Hl + off);
+      if (part < 2) bh[set][j] = *reinterpret_cast<const sdy_f16x8*>(Hh + off);
+      else bl[set][j] = *reinterpret_cast<const sdy_f16x8*>(Hl + off);
     };
     ldb(0, 0);
 #pragma unroll
@@ -627,8 +625,8 @@ __global__ __launch_bounds__(256, 1) void mlp_h3_kernel(const MlpParams p) {
 #pragma unroll
         for (int k = 0; k < 6; ++k) {
           const int j = k & 1;
-          const f16x8 a = (k < 2) ? r_lo[s] : r_hi[s];
-          const f16x8 b = (k >= 2 && k < 4) ? bl[c][j] : bh[c][j];
+          const sdy_f16x8 a = (k < 2) ? r_lo[s] : r_hi[s];
+          const sdy_f16x8 b = (k >= 2 && k < 4) ? bl[c][j] : bh[c][j];
           if (SDY_H3_PASSES == 3 || k >= 4) oacc[mi][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, oacc[mi][j], 0, 0, 0);
           if (SDY_MLP_PINNED && mi == 0 && k < 4 && t + 1 < KSC) ldb1(c ^ 1, t + 1, k);   // one LDS read behind each MFMA
           if (SDY_MLP_PINNED && !CHAIN) __builtin_amdgcn_sched_barrier(0);
@@ -638,12 +636,12 @@ __global__ __launch_bounds__(256, 1) void mlp_h3_kernel(const MlpParams p) {
             __builtin_amdgcn_sched_barrier(0);
           }
         }
-        r_hi[s] = wp[s * GROUP_F8];
-        r_lo[s] = wp[s * GROUP_F8 + 64];
+        r_hi[s] = wp[s * SDY_GROUP];
+        r_lo[s] = wp[s * SDY_GROUP + 64];
         __builtin_amdgcn_sched_barrier(0);
       }
     }
-    wp += RING * GROUP_F8;
+    wp += RING * SDY_GROUP;
   };
   using T_ = std::integral_constant<bool, true>;
   using F_ = std::integral_constant<bool, false>;
@@ -804,27 +802,6 @@ __global__ __launch_bounds__(256, 1) void mlp_h3_kernel(const MlpParams p) {
   }   // tile loop
 }
 
-// power-of-two scale that puts max|w| in [2^12, 2^13) (same rule as the other split-fp16 packers)
-float pick_scale(const float* w, size_t n) {
-  float mx = 0.f;
-  for (size_t i = 0; i < n; ++i) mx = std::fmax(mx, std::fabs(w[i]));
-  if (!(mx > 0.f) || !std::isfinite(mx)) return 1.0f;
-  int e;
-  std::frexp(mx, &e);
-  return std::ldexp(1.0f, 13 - e);
-}
-
-// one MFMA A-fragment pair (hi, lo) of rows 32 mt .. +32, columns 16 ks .. +16 of the row-major [.][K] matrix w
-void put_group(_Float16* dst, const float* w, int K, int mt, int ks, float s) {
-  for (int ln = 0; ln < 64; ++ln)
-    for (int e = 0; e < 8; ++e) {
-      const float v = w[(size_t)(32 * mt + (ln & 31)) * K + 16 * ks + 8 * (ln >> 5) + e] * s;
-      const _Float16 hv = (_Float16)v;
-      dst[ln * 8 + e] = hv;
-      dst[64 * 8 + ln * 8 + e] = (_Float16)(v - (float)hv);
-    }
-}
-
 }  // namespace
 
 #ifndef SDY_MLP_INJECT_TU
@@ -843,7 +820,7 @@ extern "C" int sdy_mlp_h3_supported(int E, int hidden) { return (E == ME && hidd
 
 extern "C" size_t sdy_mlp_h3_pack_bytes(int E, int hidden) {
   if (!sdy_mlp_h3_supported(E, hidden)) return 0;
-  return (size_t)4 * (NGROUPS + RING) * GROUP_F8 * sizeof(f16x8);
+  return (size_t)4 * (NGROUPS + RING) * SDY_GROUP * sizeof(sdy_f16x8);
 }
 
 // w1_host: (hidden, E) row-major = mlp.fwd.0.weight;  w2_host: (E, hidden) row-major = mlp.fwd.{2|3}.weight
@@ -851,17 +828,24 @@ extern "C" int sdy_mlp_h3_pack(const float* w1_host, const float* w2_host, int E
                                float* scale1, float* scale2) {
   if (!w1_host || !w2_host || !packed_dev || !scale1 || !scale2) return SDY_ERR_ARG;
   if (!sdy_mlp_h3_supported(E, hidden)) return SDY_ERR_UNSUPPORTED;
-  const float s1 = pick_scale(w1_host, (size_t)E * hidden), s2 = pick_scale(w2_host, (size_t)E * hidden);
-  const size_t gh = (size_t)GROUP_F8 * 8;   // halfs per group
+  const float s1 = sdy_h3_scale(sdy_h3_absmax(w1_host, (size_t)E * hidden));
+  const float s2 = sdy_h3_scale(sdy_h3_absmax(w2_host, (size_t)E * hidden));
+  const size_t gh = (size_t)SDY_GROUP * 8;   // halfs per group
   std::vector<_Float16> buf((size_t)4 * (NGROUPS + RING) * gh, (_Float16)0.0f);
   for (int w = 0; w < 4; ++w) {
     _Float16* d = buf.data() + (size_t)w * (NGROUPS + RING) * gh;
     auto put_fc1 = [&](int hc) {   // hidden rows 128 hc + 32 w .. +32, all of K = E
-      for (int ks = 0; ks < KS1; ++ks, d += gh) put_group(d, w1_host, ME, 4 * hc + w, ks, s1);
+      for (int ks = 0; ks < KS1; ++ks, d += gh) {
+        const float* blk = w1_host + (size_t)(128 * hc + 32 * w) * ME + 16 * ks;
+        sdy_h3_put_group(d, s1, [&](int r, int k) { return blk[(size_t)r * ME + k]; });
+      }
     };
     auto put_fc2 = [&](int hc) {   // output rows 64 w .. +64, K = hidden chunk hc
       for (int t = 0; t < KSC; ++t)
-        for (int mi = 0; mi < 2; ++mi, d += gh) put_group(d, w2_host, MH, 2 * w + mi, KSC * hc + t, s2);
+        for (int mi = 0; mi < 2; ++mi, d += gh) {
+          const float* blk = w2_host + (size_t)(64 * w + 32 * mi) * MH + 16 * (KSC * hc + t);
+          sdy_h3_put_group(d, s2, [&](int r, int k) { return blk[(size_t)r * MH + k]; });
+        }
     };
     // block order of the kernel's chunk pipeline
     put_fc1(0);
@@ -903,7 +887,7 @@ extern "C" int sdy_mlp_h3(const sdy_mlp_args* a, void* stream) {
   MlpParams p{};
   p.x = a->x; p.x_bs = a->x_bstride; p.x_tiled = a->x_tiled; p.pa = a->pa; p.pd = a->pd;
   if (a->x_tiled && !a->add) return SDY_ERR_ARG;   // (without `add` the residual is x itself, read in NCHW order)
-  p.w = reinterpret_cast<const f16x8*>(a->w);
+  p.w = reinterpret_cast<const sdy_f16x8*>(a->w);
   p.b1 = a->b1; p.b2 = a->b2;
   p.out = a->out; p.out_bs = a->out_bstride; p.add = a->add; p.add_bs = a->add_bstride;
   p.add_a = a->add ? a->add_a : nullptr; p.add_d = a->add ? a->add_d : nullptr;

@@ -27,7 +27,6 @@
 
 #include "common.h"
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
 namespace {
@@ -37,7 +36,6 @@ constexpr int PTN = 64;        // pixels per workgroup
 constexpr int PHC = 128;       // hidden channels per chunk
 constexpr int PKSC = PHC / 16; // k-steps of fc2 per chunk
 constexpr int PRING = 16;
-constexpr int PGROUP = 2 * 64; // f16x8 elements per group (hi | lo)
 constexpr float PSX = SDY_ACT_SX;   // activation pre-scale
 
 template <int KSP, int NPART, int MO>
@@ -53,7 +51,7 @@ struct PairCfg {
   static constexpr size_t XS_BYTES = (size_t)2 * PTN * XROW * 2;
   static constexpr size_t HS_BYTES = (size_t)4 * PTN * PHC * 2;
   static constexpr size_t LDS_BYTES = XS_BYTES + HS_BYTES + PH * 4 + 64;   // + 8 wave maxima of the tile's dynamic scale
-  static constexpr size_t STREAM_BYTES = (size_t)4 * (NPAD + PRING) * PGROUP * 16;   // weight stream; 64 bytes of tail follow
+  static constexpr size_t STREAM_BYTES = (size_t)4 * (NPAD + PRING) * SDY_GROUP * 16;   // weight stream; 64 bytes of tail follow
   static_assert(N >= PRING, "the first ring fill takes 16 real groups");
   static_assert(NPART <= 2, "two slots of part maxima in LDS");
   static_assert(MO == 8 || XS_BYTES >= (size_t)64 * PTN * 4, "the 64-row output tile is staged in the x tile's storage");
@@ -70,7 +68,7 @@ constexpr bool kChainInFc1 = SDY_PAIR_FC1_CHAIN != 0;
 
 struct PairParams {
   const float* x; long x_bs; int Cin;
-  const f16x8* w;                          // [4 waves][NPAD + 16 groups][hi | lo][64 lanes]
+  const sdy_f16x8* w;                      // [4 waves][NPAD + 16 groups][hi | lo][64 lanes]
   const float* b1;
   float* out; long out_bs; int Cout;
   const float* add; long add_bs;
@@ -190,8 +188,8 @@ __global__ __launch_bounds__(256, 1) void pair_h3_kernel(const PairParams p) {
   const int t_end = (t_begin + t_per < ntiles) ? t_begin + t_per : ntiles;
 
   // ---- weight ring
-  f16x8 r_hi[PRING], r_lo[PRING];
-  constexpr int GROUP_BYTES = PGROUP * (int)sizeof(f16x8);
+  sdy_f16x8 r_hi[PRING], r_lo[PRING];
+  constexpr int GROUP_BYTES = SDY_GROUP * (int)sizeof(sdy_f16x8);
   const char* const wbase = reinterpret_cast<const char*>(p.w) + (size_t)wave * (NPAD + PRING) * GROUP_BYTES;
   unsigned woff = (unsigned)lane * 16u;   // lane's byte offset of the NEXT position to fetch (sdy_ring_ld, common.h)
 #pragma unroll
@@ -443,12 +441,12 @@ __global__ __launch_bounds__(256, 1) void pair_h3_kernel(const PairParams p) {
       if (part + 1 < NPART) load_x(tile, part + 1);   // the x registers are free: they take the next part
       __syncthreads();
       stamp(1 + 2 * part);
-      f16x8 bh[2][2], bl[2][2];
+      sdy_f16x8 bh[2][2], bl[2][2];
       auto ldb1 = [&](int set, int ks, int what) {   // (hi j0, hi j1, lo j0, lo j1)
         const int j = what & 1;
         const int off = (32 * j + l31) * XROW + 8 * (2 * ks + h);
-        if (what < 2) bh[set][j] = *reinterpret_cast<const f16x8*>(Xs_hi + off);
-        else bl[set][j] = *reinterpret_cast<const f16x8*>(Xs_lo + off);
+        if (what < 2) bh[set][j] = *reinterpret_cast<const sdy_f16x8*>(Xs_hi + off);
+        else bl[set][j] = *reinterpret_cast<const sdy_f16x8*>(Xs_lo + off);
       };
 #pragma unroll
       for (int what = 0; what < 4; ++what) ldb1(0, 0, what);
@@ -460,7 +458,7 @@ __global__ __launch_bounds__(256, 1) void pair_h3_kernel(const PairParams p) {
 #pragma unroll
           for (int c = 0; c < 2; ++c) {
             const int g = 2 * (part * KSP + ks) + c;
-            const f16x8 a_lo = r_lo[g & 15], a_hi = r_hi[g & 15];
+            const sdy_f16x8 a_lo = r_lo[g & 15], a_hi = r_hi[g & 15];
 #pragma unroll
             for (int k = 0; k < 6; ++k) {
               const int j = k & 1;
@@ -481,7 +479,7 @@ __global__ __launch_bounds__(256, 1) void pair_h3_kernel(const PairParams p) {
           constexpr int i = decltype(i_c)::value;
           constexpr int c = i / KSP, ks = i % KSP, cur = i & 1;
           const int g = 2 * part * KSP + i;
-          const f16x8 a_lo = r_lo[g & 15], a_hi = r_hi[g & 15];
+          const sdy_f16x8 a_lo = r_lo[g & 15], a_hi = r_hi[g & 15];
           __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
           for (int k = 0; k < 6; ++k) {
@@ -551,12 +549,12 @@ __global__ __launch_bounds__(256, 1) void pair_h3_kernel(const PairParams p) {
         stamp(11);
       }
       if constexpr (MO == 8) {
-        f16x8 bh[2][2], bl[2][2];
+        sdy_f16x8 bh[2][2], bl[2][2];
         auto ldb1 = [&](int set, int t, int what) {
           const int j = what & 1;
           const int off = hs_off(32 * j + l31, 2 * t + h);
-          if (what < 2) bh[set][j] = *reinterpret_cast<const f16x8*>(Hh + off);
-          else bl[set][j] = *reinterpret_cast<const f16x8*>(Hl + off);
+          if (what < 2) bh[set][j] = *reinterpret_cast<const sdy_f16x8*>(Hh + off);
+          else bl[set][j] = *reinterpret_cast<const sdy_f16x8*>(Hl + off);
         };
 #pragma unroll
         for (int what = 0; what < 4; ++what) ldb1(0, 0, what);
@@ -568,7 +566,7 @@ __global__ __launch_bounds__(256, 1) void pair_h3_kernel(const PairParams p) {
 #pragma unroll
           for (int mi = 0; mi < 2; ++mi) {
             const int g = NF1 + NF2 * c + 2 * t + mi;
-            const f16x8 a_lo = r_lo[g & 15], a_hi = r_hi[g & 15];
+            const sdy_f16x8 a_lo = r_lo[g & 15], a_hi = r_hi[g & 15];
 #pragma unroll
             for (int k = 0; k < 6; ++k) {
               const int j = k & 1;
@@ -586,18 +584,18 @@ __global__ __launch_bounds__(256, 1) void pair_h3_kernel(const PairParams p) {
       } else {
         const int mi = wave >> 1, j = wave & 1;   // this wave's output tile
         (void)mi;
-        f16x8 bh[2], bl[2];
+        sdy_f16x8 bh[2], bl[2];
         auto ldb1 = [&](int set, int t, int what) {
           const int off = hs_off(32 * j + l31, 2 * t + h);
-          if (what == 0) bh[set] = *reinterpret_cast<const f16x8*>(Hh + off);
-          else bl[set] = *reinterpret_cast<const f16x8*>(Hl + off);
+          if (what == 0) bh[set] = *reinterpret_cast<const sdy_f16x8*>(Hh + off);
+          else bl[set] = *reinterpret_cast<const sdy_f16x8*>(Hl + off);
         };
         ldb1(0, 0, 0); ldb1(0, 0, 1);
 #pragma unroll
         for (int t = 0; t < PKSC; ++t) {
           const int cur = t & 1;
           const int g = NF1 + NF2 * c + t;
-          const f16x8 a_lo = r_lo[g & 15], a_hi = r_hi[g & 15];
+          const sdy_f16x8 a_lo = r_lo[g & 15], a_hi = r_hi[g & 15];
           __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
           for (int k = 0; k < 3; ++k) {
@@ -699,27 +697,6 @@ __global__ __launch_bounds__(256, 1) void pair_h3_kernel(const PairParams p) {
   if (bad && p.flags) atomicOr(p.flags, (unsigned)SDY_FLAG_NONFINITE);   // (once, outside the tile loop: no live state across it)
 }
 
-float pick_scale(const float* w, size_t n) {   // power of two that puts max|w| in [2^12, 2^13)
-  float mx = 0.f;
-  for (size_t i = 0; i < n; ++i) mx = std::fmax(mx, std::fabs(w[i]));
-  if (!(mx > 0.f) || !std::isfinite(mx)) return 1.0f;
-  int e;
-  std::frexp(mx, &e);
-  return std::ldexp(1.0f, 13 - e);
-}
-
-// (hi, lo) A-fragment pair of rows 32 mt .. +32, columns 16 ks .. +16 of the row-major [rows][K] matrix w, zero outside it
-void put_group(_Float16* dst, const float* w, int rows, int K, int mt, int ks, float s) {
-  for (int ln = 0; ln < 64; ++ln)
-    for (int e = 0; e < 8; ++e) {
-      const int r = 32 * mt + (ln & 31), k = 16 * ks + 8 * (ln >> 5) + e;
-      const float v = (r < rows && k < K) ? w[(size_t)r * K + k] * s : 0.0f;
-      const _Float16 hv = (_Float16)v;
-      dst[ln * 8 + e] = hv;
-      dst[64 * 8 + ln * 8 + e] = (_Float16)(v - (float)hv);
-    }
-}
-
 struct Shape { int ksp, npart, mo; };
 bool pick_shape(int Cin, int hidden, int Cout, Shape* s) {
   if (hidden != PH || Cin < 1 || Cout < 1) return false;
@@ -742,8 +719,8 @@ size_t pack_bytes() { return PairCfg<KSP, NPART, MO>::STREAM_BYTES + 64; }
 template <int KSP, int NPART, int MO>
 void pack(const float* w1, const float* w2, int Cin, int Cout, float s1, float s2, std::vector<_Float16>& buf) {
   using Cfg = PairCfg<KSP, NPART, MO>;
-  const size_t gh = (size_t)PGROUP * 8;   // halfs per group
-  static_assert(Cfg::STREAM_BYTES == (size_t)4 * (Cfg::NPAD + PRING) * PGROUP * 8 * sizeof(_Float16), "stream size");
+  const size_t gh = (size_t)SDY_GROUP * 8;   // halfs per group
+  static_assert(Cfg::STREAM_BYTES == (size_t)4 * (Cfg::NPAD + PRING) * SDY_GROUP * 8 * sizeof(_Float16), "stream size");
   buf.assign((size_t)4 * (Cfg::NPAD + PRING) * gh + 32, (_Float16)0.0f);   // + 64 bytes of tail
   {
     float l1 = 0.0f;
@@ -757,18 +734,31 @@ void pack(const float* w1, const float* w2, int Cin, int Cout, float s1, float s
   for (int w = 0; w < 4; ++w) {
     _Float16* base = buf.data() + (size_t)w * (Cfg::NPAD + PRING) * gh;
     _Float16* d = base;
+    auto put_w1 = [&](int mt, int ks) {   // hidden rows 32 mt .. +32, k-step ks of W1 [PH][Cin], zero past Cin
+      sdy_h3_put_group(d, s1, [&](int r, int k) {
+        const int kk = 16 * ks + k;
+        return kk < Cin ? w1[(size_t)(32 * mt + r) * Cin + kk] : 0.0f;
+      });
+      d += gh;
+    };
+    auto put_w2 = [&](int mt, int ks) {   // output rows 32 mt .. +32, k-step ks of W2 [Cout][PH], zero past Cout
+      sdy_h3_put_group(d, s2, [&](int r, int k) {
+        const int row = 32 * mt + r;
+        return row < Cout ? w2[(size_t)row * PH + 16 * ks + k] : 0.0f;
+      });
+      d += gh;
+    };
     const int n_major = kChainInFc1 ? (NPART - 1) * KSP : NPART * KSP;
     for (int ks = 0; ks < n_major; ++ks)             // every part but the last: k-step major
-      for (int c = 0; c < 2; ++c, d += gh) put_group(d, w1, PH, Cin, 4 * c + w, ks, s1);   // hidden rows 128 c + 32 w
+      for (int c = 0; c < 2; ++c) put_w1(4 * c + w, ks);   // hidden rows 128 c + 32 w
     for (int c = 0; c < 2; ++c)                      // the last part: chunk major
-      for (int ks = n_major; ks < NPART * KSP; ++ks, d += gh) put_group(d, w1, PH, Cin, 4 * c + w, ks, s1);
+      for (int ks = n_major; ks < NPART * KSP; ++ks) put_w1(4 * c + w, ks);
     for (int c = 0; c < 2; ++c)
       for (int t = 0; t < PKSC; ++t) {
         if (MO == 8) {
-          for (int mi = 0; mi < 2; ++mi, d += gh) put_group(d, w2, Cout, PH, 2 * w + mi, PKSC * c + t, s2);
+          for (int mi = 0; mi < 2; ++mi) put_w2(2 * w + mi, PKSC * c + t);
         } else {
-          put_group(d, w2, Cout, PH, w >> 1, PKSC * c + t, s2);
-          d += gh;
+          put_w2(w >> 1, PKSC * c + t);
         }
       }
     // (holes stay zero) + the first 16 groups again: the ring's refills run one 16-block ahead across the tile boundary
@@ -836,7 +826,8 @@ extern "C" int sdy_pair_h3_pack(const float* w1_host, const float* w2_host, int 
   if (!w1_host || !w2_host || !packed_dev || !scale1 || !scale2) return SDY_ERR_ARG;
   Shape s;
   if (!pick_shape(Cin, hidden, Cout, &s)) return SDY_ERR_UNSUPPORTED;
-  const float s1 = pick_scale(w1_host, (size_t)hidden * Cin), s2 = pick_scale(w2_host, (size_t)Cout * hidden);
+  const float s1 = sdy_h3_scale(sdy_h3_absmax(w1_host, (size_t)hidden * Cin));
+  const float s2 = sdy_h3_scale(sdy_h3_absmax(w2_host, (size_t)Cout * hidden));
   std::vector<_Float16> buf;
 #define PK(K, P, M) pack<K, P, M>(w1_host, w2_host, Cin, Cout, s1, s2, buf)
   PAIR_DISPATCH(s, PK);
@@ -858,7 +849,7 @@ extern "C" int sdy_pair_h3(const sdy_pair_args* a, void* stream) {
   if (a->B > 65535) return SDY_ERR_UNSUPPORTED;
   PairParams p{};
   p.x = a->x; p.x_bs = a->x_bstride; p.Cin = a->Cin;
-  p.w = reinterpret_cast<const f16x8*>(a->w);
+  p.w = reinterpret_cast<const sdy_f16x8*>(a->w);
   p.b1 = a->b1;
   p.out = a->out; p.out_bs = a->out_bstride; p.Cout = a->Cout;
   p.add = a->add; p.add_bs = a->add_bstride;
