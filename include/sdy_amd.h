@@ -454,6 +454,37 @@ int sdy_ensemble_series_grad(const float* pred, int M, long member_stride, long 
                              long truth_sample_stride, const float* weights, int n_sample, int T, int nlat, int nlon,
                              double* out, void* stream);
 
+/* Derived water-budget variables of the inference loop (compute_derived_quantities,
+ * src/ace_inference/inference/derived_variables.py; formulas src/ace_inference/core/metrics.py:296-367), all requested
+ * outputs in one pass.  Per trajectory (i0, i1) and time t, at grid point p, with q_k = specific total water of level k:
+ *   dp_k  = (ak[k+1] + ps*bk[k+1]) - (ak[k] + ps*bk[k])
+ *   twp   = (1/g) * sum_k dp_k*q_k                                      (total_water_path)
+ *   dry   = ps - g*twp                                                  (surface_pressure_due_to_dry_air)
+ *   resid = 0 at t = 0, else (twp_t - twp_{t-1}) / 21600 - (lhf/2.5e6 - prate + adv)   (total_water_path_budget_residual)
+ * in the reference's fp32 operation order (no FMA contraction, levels summed in order).  The time difference is along THIS
+ * time axis for every trajectory (the reference differences axis 1 of whatever it is handed, which for member-stacked
+ * predictions is the sample axis).
+ *   inputs: dev float, element (i0, i1, t, p) at ptr + i0*s0 + i1*s1 + t*HW + p (the window driver's member-stacked view,
+ *           or flat rows with n0 = 1); q[0..K-1] and ps always; lhf, prate, adv when resid is requested
+ *   outputs: dev float, contiguous (n0, n1, T, HW); each may be NULL (not computed)
+ * SDY_ERR_ARG: K outside 1..SDY_DERIVED_MAX_LEVELS, a non-positive extent, HW or a stride not a multiple of 4, a required
+ * input NULL, a pointer not 16-byte aligned.  SDY_ERR_UNSUPPORTED: n0*n1 > 65535. */
+#define SDY_DERIVED_MAX_LEVELS 16
+typedef struct {
+  const float* q[SDY_DERIVED_MAX_LEVELS];
+  const float* ps;
+  const float* lhf;
+  const float* prate;
+  const float* adv;
+  long s0, s1;
+  int n0, n1, T, HW, K;
+  float ak[SDY_DERIVED_MAX_LEVELS + 1], bk[SDY_DERIVED_MAX_LEVELS + 1];
+  float* dry;
+  float* twp;
+  float* resid;
+} sdy_derived_args;
+int sdy_derived_water(const sdy_derived_args* args, void* stream);
+
 /* Time-mean accumulation of the inference aggregator (src/ace_inference/core/aggregator/inference/time_mean.py:97-117,
  * _add_or_initialize_time_mean): acc[p] += scale * sum over rows (r0, r1) and times t0 <= t < T of
  * x[r0*stride0 + r1*stride1 + t*HW + p].  x: dev, one variable of a window, (n0, n1, T, HW) with float strides for the

@@ -139,6 +139,20 @@ class SdySfnoFwdArgs(C.Structure):
     ]
 
 
+SDY_DERIVED_MAX_LEVELS = 16
+
+
+class SdyDerivedArgs(C.Structure):
+    _fields_ = [
+        ("q", C.c_void_p * SDY_DERIVED_MAX_LEVELS), ("ps", C.c_void_p),
+        ("lhf", C.c_void_p), ("prate", C.c_void_p), ("adv", C.c_void_p),
+        ("s0", C.c_long), ("s1", C.c_long),
+        ("n0", C.c_int), ("n1", C.c_int), ("T", C.c_int), ("HW", C.c_int), ("K", C.c_int),
+        ("ak", C.c_float * (SDY_DERIVED_MAX_LEVELS + 1)), ("bk", C.c_float * (SDY_DERIVED_MAX_LEVELS + 1)),
+        ("dry", C.c_void_p), ("twp", C.c_void_p), ("resid", C.c_void_p),
+    ]
+
+
 # name -> (restype, argtypes); every symbol include/sdy_amd.h declares
 SIGNATURES = {
     "sdy_version": (C.c_int, []),
@@ -223,6 +237,7 @@ SIGNATURES = {
                                      C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "sdy_ensemble_series_grad": (C.c_int, [C.c_void_p, C.c_int, C.c_long, C.c_long, C.c_void_p, C.c_long, C.c_void_p,
                                           C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "sdy_derived_water": (C.c_int, [C.POINTER(SdyDerivedArgs), C.c_void_p]),
     "sdy_profile_enable": (C.c_int, [C.c_int]),
     "sdy_profile_stage_count": (C.c_int, []),
     "sdy_profile_stage_name": (C.c_char_p, [C.c_int]),

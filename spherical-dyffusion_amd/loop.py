@@ -24,7 +24,12 @@ MI355X-first differences:
 * `forecast_steps_per_second` is the reference's "Total steps per second" (`src/ace_inference/inference/inference.py:294-298`:
   steps x trajectories over the WHOLE duration of the call, loading included); the rate over the device time of the windows
   alone is reported beside it (`forecast_steps_per_second_run_on_batch`).
-Derived variables (`compute_derived_quantities`) are not on the sampling path: pass `derive=` to apply your own.
+Derived variables (`compute_derived_quantities`, `loop.py:197,245`) are off by default (`derive=None`).  For the reference's
+behaviour pass `derive=sdy_amd.derived.deriver(data.sigma_coordinates)`: one launch per dict adds `surface_pressure_due_to_dry_air`,
+`total_water_path` and `total_water_path_budget_residual` to the targets and the predictions (denormalised only, as in the
+reference) before the first time of a window is dropped; the residual is differenced along time, also for member-stacked
+predictions, where the reference differences the sample axis (`sdy_amd.derived`).  Any other callable taking and
+returning a dict works too.
 """
 from __future__ import annotations
 

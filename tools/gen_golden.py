@@ -771,6 +771,166 @@ def gen_mean_series_grad(tag="fx_mean_series_grad"):
     print(f"{tag}: 16x32 ens grad_mag a {out['16x32::ens::series::weighted_grad_mag_percent_diff/a'][:3]}, "
           f"b {out['16x32::ens::series::weighted_grad_mag_percent_diff/b'][:3]}; {os.path.getsize(path)} bytes, saved")
 
+def gen_derived(tag="fx_derived"):
+    """The reference's own `compute_derived_quantities` (inference/derived_variables.py, metrics.py:296-367) on
+    function-level cases, and its own `run_inference` (inference/loop.py:158-264) with it on the tiny stepper of gen_loop.
+
+    Function level: 4-D (samples, time, lat, lon) and 5-D member-stacked (members, samples, time, lat, lon) dicts on a 7 x 12
+    grid, K = 4, 8 and 12 levels (12 inserted out of order, with the aliases PS / LHFLX / surface_precipitation_rate),
+    T = 1, FV3GFS-like magnitudes.  5-D cases also record the reference applied to each member alone (`member::`): the
+    values the port computes, since the reference differences the 5-D residual over samples.
+
+    Loop: fx_loop_tiny's series and network with the six generated variables renamed to specific_total_water_0 / _1
+    (K = 2), PRESsfc, LHTFLsfc, PRATEsfc and tendency_of_total_water_path_due_to_advection, two windows of 6 steps, 2 initial
+    conditions, run with 1 member and with 3.  Recorded: the derived arrays the writer received (those the aggregator
+    receives are the same dicts), on a spatial subsample [..., ::4, ::8] plus per-plane sums in fp64; and the reference
+    applied member by member to the 3-member predictions."""
+    import types
+
+    import src.ace_inference.inference.loop as L
+    from src.ace_inference.core.aggregator.null import NullAggregator
+    from src.ace_inference.core.data_loading.data_typing import SigmaCoordinates
+    from src.ace_inference.core.normalizer import StandardNormalizer
+    from src.ace_inference.core.prescriber import Prescriber
+    from src.ace_inference.core.stepper_multistep import run_on_batch_multistep
+    from src.ace_inference.inference.derived_variables import compute_derived_quantities
+    from src.ace_inference.training.utils.darcy_loss import LpLoss
+    from src.utilities.packer import Packer
+
+    derived = ["surface_pressure_due_to_dry_air", "total_water_path", "total_water_path_budget_residual"]
+    g = torch.Generator(device="cpu").manual_seed(4711)
+    ak8 = [3.0, 5238.4, 11815.8, 17263.1, 19929.5, 17023.4, 8970.5, 1537.5, 0.0]
+    bk8 = [0.0, 0.0, 0.0115, 0.0781, 0.2034, 0.4004, 0.6513, 0.9065, 1.0]
+    levels = {4: (ak8[::2], bk8[::2]), 8: (ak8, bk8),
+              12: ([3.0 + 1700.0 * k * (12 - k) / 3.0 for k in range(13)], [(k / 12.0) ** 1.8 for k in range(13)])}
+    H, W = 7, 12
+    out = dict(derived=json.dumps(derived))
+    cases = []
+
+    def fields(lead, K, aliases):
+        q_scale = torch.logspace(-2, -6, K)                   # moist near the surface, dry aloft
+        d = {}
+        order = list(range(K))
+        if K > 10:
+            order = order[::-1]                                 # insertion order != natural order (_10 after _2)
+        for k in order:
+            d[f"specific_total_water_{k}"] = q_scale[k] * torch.rand(*lead, H, W, generator=g) * 2.0
+        ps_name, lhf_name, pr_name = ("PS", "LHFLX", "surface_precipitation_rate") if aliases else \
+            ("PRESsfc", "LHTFLsfc", "PRATEsfc")
+        d[ps_name] = 1.0e5 + 2.5e3 * torch.randn(*lead, H, W, generator=g)
+        d[lhf_name] = 90.0 + 60.0 * torch.randn(*lead, H, W, generator=g)
+        d[pr_name] = 3.0e-5 * torch.rand(*lead, H, W, generator=g) * 2.0
+        d["tendency_of_total_water_path_due_to_advection"] = 2.0e-5 * torch.randn(*lead, H, W, generator=g)
+        d["TMP2m"] = 280.0 + torch.randn(*lead, H, W, generator=g)           # an unrelated variable passes through
+        return d
+
+    for name, lead, K, aliases in (("det_k4", (2, 3), 4, False), ("ens_k8", (3, 2, 4), 8, False),
+                                   ("det_k12_alias", (2, 3), 12, True), ("det_k8_t1", (2, 1), 8, False),
+                                   ("ens_k4_t1", (2, 2, 1), 4, True)):
+        ak, bk = levels[K]
+        sigma = SigmaCoordinates(ak=torch.tensor(ak), bk=torch.tensor(bk))
+        d = fields(lead, K, aliases)
+        res = compute_derived_quantities(d, sigma)
+        assert list(res)[-3:] == derived, list(res)
+        cases.append(name)
+        out[f"{name}::names"] = json.dumps(list(d))
+        out[f"{name}::ak"], out[f"{name}::bk"] = np.asarray(ak, np.float32), np.asarray(bk, np.float32)
+        out.update({f"{name}::in::{k}": v.numpy() for k, v in d.items()})
+        out.update({f"{name}::ref::{k}": res[k].numpy() for k in derived})
+        if len(lead) == 3:
+            per = [compute_derived_quantities({k: v[m] for k, v in d.items()}, sigma) for m in range(lead[0])]
+            out.update({f"{name}::member::{k}": torch.stack([p[k] for p in per]).numpy() for k in derived})
+    out["cases"] = json.dumps(cases)
+
+    # ---- the reference's window driver with the real compute_derived_quantities (the tiny stepper of gen_loop)
+    C, n_forc, Hl, Wl, E, Lr = 6, 2, 32, 64, 16, 2
+    fc, ipol, fcfg, icfg, fsd, isd, cs = build_experiments(C, n_forc, Hl, Wl, E, Lr, True, False, 11, 22)
+    old_in = ["HGTsfc"] + [f"v{i}" for i in range(1, cs)]
+    rename = dict(zip(old_in[1:], ["specific_total_water_0", "specific_total_water_1", "PRESsfc", "LHTFLsfc", "PRATEsfc",
+                                   "tendency_of_total_water_path_due_to_advection"]))
+    assert len(rename) == len(old_in) - 1
+    rn = lambda n: rename.get(n, n)  # noqa: E731
+    in_names = [rn(n) for n in old_in]
+    out_names = in_names[1:]
+    forcing_names = [f"f{i}" for i in range(n_forc)]
+    mask_name = "ocean_fraction"
+    n_total, n_mem_steps, B = 12, 6, 2
+    g = torch.Generator(device="cpu").manual_seed(777)      # gen_loop's series, draw for draw
+    names = old_in + forcing_names
+    means = {rn(n): torch.randn((), generator=g) * 3.0 for n in names}
+    stds = {rn(n): torch.rand((), generator=g) * 2.0 + 0.5 for n in names}
+    series = {rn(n): torch.randn(B, n_total + 1, Hl, Wl, generator=g) * stds[rn(n)] + means[rn(n)] for n in names}
+    series[mask_name] = torch.rand(B, n_total + 1, Hl, Wl, generator=g)
+    pres = Prescriber(prescribed_name=rn("v2"), mask_name=mask_name, mask_value=1, interpolate=False)
+    axis = -3
+    ak, bk = [0.0, 0.5, 0.0], [0.0, 0.4, 1.0]
+    sigma = SigmaCoordinates(ak=torch.tensor(ak), bk=torch.tensor(bk))
+    out["loop::ak"], out["loop::bk"] = np.float32(ak), np.float32(bk)
+    out["loop::rename"] = json.dumps(rename)
+
+    class _Stepper:
+        module = fc
+
+        def run_on_batch(self, data, optimization, n_forward_steps=1, aggregator=None):
+            return run_on_batch_multistep(
+                data=data, module=fc, normalizer=StandardNormalizer(means, stds), in_packer=Packer(in_names, axis=axis),
+                out_packer=Packer(out_names, axis=axis), forcings_packer=Packer(forcing_names, axis=axis),
+                optimization=optimization, loss_obj=LpLoss(), prescriber=pres,
+                aggregator=aggregator if aggregator is not None else NullAggregator(), n_forward_steps=n_forward_steps)
+
+    per_member = []           # 5-D (member-stacked) calls of the loop: the reference applied to each member alone
+
+    def recording(data, sigma_coordinates):
+        any_v = next(iter(data.values()))
+        if any_v.dim() == 5:
+            per = [compute_derived_quantities({k: v[m] for k, v in data.items()}, sigma_coordinates)
+                   for m in range(any_v.shape[0])]
+            per_member.append({k: torch.stack([p[k] for p in per]) for k in derived})
+        return compute_derived_quantities(data, sigma_coordinates)
+
+    L.compute_derived_quantities = recording
+    sub = (Ellipsis, slice(None, None, 4), slice(None, None, 8))
+    for members in (1, 3):
+        windows = [types.SimpleNamespace(
+            data={k: v[:, i * n_mem_steps:(i + 1) * n_mem_steps + 1].clone() for k, v in series.items()},
+            times=types.SimpleNamespace(isel=lambda time: None)) for i in range(n_total // n_mem_steps)]
+        rec = []
+
+        class _Writer:
+            def append_batch(self, target, prediction, start_timestep, start_sample, batch_times=None):
+                rec.append((int(start_timestep), {k: v.clone() for k, v in prediction.items()},
+                            {k: v.clone() for k, v in target.items()}))
+
+        class _Agg:
+            def record_batch(self, loss, target_data, gen_data, target_data_norm, gen_data_norm, i_time_start=0):
+                assert all(k in target_data and k in gen_data for k in derived)
+
+        L.run_inference(_Agg(), _Stepper(), types.SimpleNamespace(loader=windows, sigma_coordinates=sigma), n_total,
+                        n_mem_steps, members, "cpu", writer=_Writer())
+        key = f"loop::m{members}"
+        out[f"{key}::starts"] = np.array([r[0] for r in rec])
+        for w, (st, pred, tgt) in enumerate(rec):
+            assert list(pred)[-3:] == derived and list(tgt)[-3:] == derived
+            for kind, dct in (("pred", pred), ("tgt", tgt)):
+                for k in derived:
+                    out[f"{key}::{kind}{w}::{k}"] = dct[k][sub].numpy()
+                    out[f"{key}::{kind}{w}::{k}::sum"] = dct[k].double().sum(dim=(-2, -1)).numpy()
+            if members > 1:       # per member, with the first time dropped as the writer sees it (loop.py:133-141)
+                for k in derived:
+                    x = per_member[w][k][:, :, 1:] if w > 0 else per_member[w][k]
+                    assert x.shape == pred[k].shape
+                    out[f"{key}::member{w}::{k}"] = x[sub].numpy()
+                    out[f"{key}::member{w}::{k}::sum"] = x.double().sum(dim=(-2, -1)).numpy()
+        assert len(per_member) == (len(rec) if members > 1 else 0)
+        per_member.clear()
+    path = os.path.join(OUT, f"{tag}.npz")
+    np.savez_compressed(path, **out)
+    r = out["ens_k8::ref::total_water_path_budget_residual"]
+    print(f"{tag}: cases {cases}; ens_k8 residual ref (sample-axis) |max| {np.abs(r).max():.3e} vs per-member "
+          f"{np.abs(out['ens_k8::member::total_water_path_budget_residual']).max():.3e}; {os.path.getsize(path)} bytes, "
+          "saved")
+
+
 if __name__ == "__main__":
     torch.set_num_threads(8)
     if len(sys.argv) > 1:      # regenerate selected fixtures only: python tools/gen_golden.py gen_time_mean
@@ -802,6 +962,7 @@ if __name__ == "__main__":
     gen_time_mean()
     gen_mean_series()
     gen_mean_series_grad()
+    gen_derived()
     gen_sfno_wide_masks()
     gen_sfno_full()
     sizes = {n: os.path.getsize(os.path.join(OUT, n)) for n in sorted(os.listdir(OUT))}
