@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: 25-member ensemble DYffusion sampling on the 180x360 grid (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--scaling strong|weak] [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--scaling strong|weak] [--dump-outputs DIR] [--full]
 
 works by itself for any N (the parent starts one child process per GPU BEFORE anything touches HIP and relays rank 0's
 JSON line), and also under an external launcher:
@@ -18,20 +18,22 @@ on, cold-sampling updates, autoregressive feedback x0 <- t6) of the whole job.
       RELAYED (`ensemble.relay_plan`): each advances as a batch of one, hosted by one rank per slice of the timed windows and
       handed to the next with a send / recv of its state (N = 8: 3 members per GPU + member 24 visiting every GPU for 1/8 of
       the windows, instead of one GPU with 4 members setting the pace).  `--no-relay`: the static split of
-      `ensemble.partition` (N = 8: 4,3,3,3,3,3,3,3).  At N > 1 a weak-scaling leg (25 members of its own
+      `ensemble.partition` (N = 8: 4,3,3,3,3,3,3,3).  With `--full` at N > 1 a weak-scaling leg (25 members of its own
       initial condition on every rank, the reference's IC sharding: src/ace_inference/core/data_loading/inference.py:110-113)
       is timed as well and reported under config.weak_scaling.
   --scaling weak: only that leg; value = N * 150 member-forecast-steps per step.
 There is no collective on the data path; RCCL serves the barriers, the max-over-ranks time and the relay's hand-overs.
 
-Rank 0 prints ONE JSON line.  Beyond the contract keys:
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the contract
+keys with `config` and `c5_extrapolation` (10-year job = 4 ICs x 25 members x 14600 steps, at the measured rate).  Everything
+else takes runs of its own and comes with `--full` (`--no-extras` / `--no-cpu-baseline` leave parts of it out):
   roofline      dominant kernel (`mlp_h3_kernel<true>`, the fused MLP with the Philox dropout of the interpolator), timed
                 IN THE NETWORK with HIP events on the launch stream (sdy_profile_*), plus `kernels`: the same measurement
                 for every stage of the forward with its algorithmic flops / bytes and both roofline fractions.
   cpu_baseline  the CPU oracle (same torch op sequence as the reference's CPU path) on the host cores, bounded sample.
   latency       B = 1: one interpolator forward (BASELINE config C2) and one horizon-6 pass (C3).
   f32_fallback  the same 25-member pass with gemm_mode="f32" (the escape hatch when the fp16-range flag fires).
-  c5_extrapolation  wall time of the 10-year job (4 ICs x 25 members x 14600 steps) at the measured rate.
+  config.weak_scaling  the weak-scaling leg at N > 1 (above).
 """
 import argparse
 import json
@@ -331,8 +333,8 @@ def latency_b1(exp, device):
 def cpu_baseline(threads):
     """CPU oracle (same torch op sequence as the reference's CPU PyTorch path) on the host cores: one forecaster and one
     interpolator forward at B = 1 (about 20-30 s of CPU work), scaled to a horizon-6 pass = 6 + 10 forwards.  The only
-    place `oracle/` is imported, on rank 0 at N = 1 only; the oracle's weight generator produces the benchmark networks'
-    weights (tests/test_host_logic.py holds the two generators together)."""
+    place `oracle/` is imported, with --full on rank 0 at N = 1 only; the oracle's weight generator produces the benchmark
+    networks' weights (tests/test_host_logic.py holds the two generators together)."""
     import torch
 
     from oracle.sfno import OracleSFNO, SFNOConfig, make_state_dict
@@ -401,9 +403,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--scaling", choices=("strong", "weak"), default="strong")
     ap.add_argument("--members", type=int, default=MEMBERS, help="ensemble members of the job (strong) / per GPU (weak)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the stage profile / roofline, and at N = 1 the B=1 latencies, "
+                         "the f32 fallback and the CPU baseline, at N > 1 the weak-scaling leg")
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads of the CPU baseline (default: min(32, host CPUs))")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the stage profile, B=1 latencies and the weak leg")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="--full without the stage profile, B=1 latencies, f32 fallback and weak leg")
     ap.add_argument("--no-relay", action="store_true",
                     help="strong scaling with the static split only (25 over 8 = 4,3,3,...), no relayed remainder members")
     ap.add_argument("--digests", action="store_true", help="add (sum, norm) of every trajectory's final state to the JSON line")
@@ -417,6 +423,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    extras = args.full and not args.no_extras
+    cpu_base = args.full and not args.no_cpu_baseline
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # Stand-alone multi-GPU run: become the launcher.  Nothing in this process has touched HIP (torch is not even
@@ -464,6 +472,8 @@ def main():
     def digest(first_unit, x):
         """(sum, L2 norm) in float64 of every trajectory's final state: what `--digests` prints, so that runs with different
         world sizes / schedules can be compared trajectory by trajectory (tests/test_gpu_fullsize.py)."""
+        if not args.digests:
+            return
         for r in range(x.shape[0]):
             v = x[r].double()
             digests[first_unit + r] = [float(v.sum()), float(v.norm())]
@@ -564,7 +574,7 @@ def main():
     if args.scaling == "strong":
         start, cnt = parts[rank]
         legs["strong"] = (relay_leg(M, capture) if relay else timed_leg(0, start, cnt, capture), M)
-        if world > 1 and not args.no_extras:
+        if world > 1 and extras:
             legs["weak"] = (timed_leg(rank, rank * M, M), world * M)
     else:
         legs["weak"] = (timed_leg(rank, rank * M, M, capture), world * M)
@@ -639,7 +649,7 @@ def main():
             except Exception as e:      # noqa: BLE001
                 res[key] = {"error": "%s: %s" % (type(e).__name__, e)}
 
-        if not args.no_extras:
+        if extras:
             def roof():
                 x, forc = synthetic_state(0, B0, device)
                 exp.set_batch_offset(0)
@@ -656,7 +666,7 @@ def main():
                     return r
 
                 extra("f32_fallback", f32)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and cpu_base:
             extra("cpu_baseline", lambda: cpu_baseline(args.cpu_threads or min(32, os.cpu_count() or 1)))
         print(json.dumps(res), flush=True)
     if world > 1:

@@ -354,6 +354,36 @@ def test_bench_two_ranks_as_the_driver_launches_it():
     assert min(b - a for a, b in zip(norms, norms[1:])) > 5e-3 * norms[0], norms
 
 
+def test_bench_plain_run_is_the_headline_and_full_adds_the_extras():
+    """A plain `bench.py` run prints the headline and nothing that takes runs of its own; `--full` adds the stage roofline, the
+    B = 1 latencies and the f32 fallback, each a measurement and not an error record (the CPU baseline, half a minute of host
+    work, is left out here with --no-cpu-baseline)."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    extras = ("roofline", "latency", "f32_fallback", "cpu_baseline")
+
+    def run(*extra):
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "1", "--warmup", "0", "--members", "2", *extra]
+        p = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=900)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, p.stdout[-2000:]
+        return json.loads(lines[0])
+
+    plain = run()
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in plain, key
+    assert plain["value"] > 0 and not [k for k in extras if k in plain]
+    full = run("--full", "--no-cpu-baseline")
+    for key in extras[:3]:
+        assert key in full and "error" not in full[key], (key, full.get(key))
+    assert "cpu_baseline" not in full and full["roofline"]["kernels"] and full["f32_fallback"]["value"] > 0
+
+
 def test_rccl_path_when_two_devices_are_visible():
     """`bench.py --gpus 2` over RCCL proper (init_process_group("nccl"), barriers, the max-over-ranks all_reduce and the relay's
     send / recv between two GPUs).  The GPU boxes of the development pool have ONE device, where two ranks cannot share a

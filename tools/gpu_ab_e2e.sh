@@ -6,7 +6,7 @@ mkdir -p $(dirname $O); : > $O
 for round in 1 2 3; do
   for kv in "$@"; do
     n=${kv%%=*}; l=$GRAFT_REPO_ROOT/${kv#*=}
-    SDY_AMD_LIB=$l timeout 600 python bench.py --steps 4 --warmup 2 --no-cpu-baseline > /tmp/ab.json 2>/dev/null
+    SDY_AMD_LIB=$l timeout 600 python bench.py --steps 4 --warmup 2 --full --no-cpu-baseline > /tmp/ab.json 2>/dev/null
     echo "== round $round $n" >> $O; python tools/show_bench.py /tmp/ab.json | grep -E "^\{|$PAT" | sed "s/'unit'.*//" >> $O
   done
 done

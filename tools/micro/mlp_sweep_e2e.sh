@@ -8,7 +8,7 @@ for D in "$@"; do
   make > /dev/null 2>&1
   echo "== $D"
   cd $R
-  python bench.py --steps 4 --warmup 1 2>/dev/null | python -c "
+  python bench.py --steps 4 --warmup 1 --full 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 print('value', d['value'], ' '.join('%s %.4f' % (k['name'], k['ms']) for k in d['roofline']['kernels'] if 'mlp' in k['name'] or 'inner' in k['name']))

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Per-round profile set (GPU box, via gpurun): bash tools/profile_round.sh <tag>     (r2a, r2b, r3a, ...)
-#   1. bench line (default run) + rocprofv3 --kernel-trace --stats of the same command
+#   1. bench line (--full) + rocprofv3 --kernel-trace --stats of the same command
 #   2. PMC passes over one interpolator + one forecaster forward at B = 25 (tools/pmc_forward25.py), each counter group in its
 #      own pass with --kernel-trace only: FETCH_SIZE, WRITE_SIZE (HBM traffic), matrix-pipe / issue counters
 TAG=${1:-r3b}
@@ -9,7 +9,7 @@ OUT=$R/gpurun_out/$TAG
 export TMPDIR=/tmp
 mkdir -p $OUT
 cd $R
-python3 bench.py --steps 10 --warmup 2 > $OUT/bench.json 2> $OUT/bench.err
+python3 bench.py --steps 10 --warmup 2 --full > $OUT/bench.json 2> $OUT/bench.err
 echo "bench rc=$?"; head -c 600 $OUT/bench.json; echo
 cd /tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -- python3 $R/bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-extras > $OUT/prof.log 2>&1
