@@ -115,9 +115,15 @@ class InverseRealSHT(_ShtBase):
         C_ = cf.shape[0]
         plan = self._plan(c.device)
         out = torch.empty(C_, self.nlat, self.nlon, dtype=torch.float32, device=c.device)
-        nws = lib.sdy_sht_workspace_floats(plan.handle, 1, C_)
+        # One native call addresses its coefficients Cs[l][m][field][2] with 32-bit lane offsets: the Legendre synthesis
+        # reads up to 192 degree rows of row stride mtr * 2 * fields floats (leg_par.hip), so a call covers fewer than
+        # 2^32 / (8 * (192 * mtr + 1)) fields (15444 at mtr = 181: 60 rows of 256 channels); more run as several calls.
+        step = min(C_, (((1 << 32) - 1) // (8 * (192 * plan.mtr + 1))) // 4 * 4)
+        nws = lib.sdy_sht_workspace_floats(plan.handle, 1, step)
         ws = torch.empty(nws, dtype=torch.float32, device=c.device)
         with torch.cuda.device(c.device):
-            check(lib.sdy_sht_inverse(plan.handle, ptr(cf), ptr(out), 1, C_, ptr(ws), nws, current_stream()),
-                  "sdy_sht_inverse")
+            for c0 in range(0, C_, step):
+                k = min(step, C_ - c0)
+                check(lib.sdy_sht_inverse(plan.handle, ptr(cf[c0:c0 + k]), ptr(out[c0:c0 + k]), 1, k, ptr(ws), nws,
+                                          current_stream()), "sdy_sht_inverse")
         return out[:n].reshape(*lead, self.nlat, self.nlon)

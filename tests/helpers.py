@@ -46,3 +46,42 @@ class PhiloxMasks:
                                            self.rows, device=self.device)
         return torch.from_numpy(element_keep_mask(self.seed, self.call, layer, k, c.dropout_mlp, B, C, H, W,
                                                   self.batch_offset, self.rows))
+
+
+class SliceErrors:
+    """Relative L2 error of a batched result per slice -- (batch row, channel) for fields, (batch row, degree) for spectral
+    tensors -- next to the global one.  A global relative L2 over B rows divides the error of one wrong row by about sqrt(B);
+    the worst slice does not.  Chunks of rows are added in order (`rows`: their batch indices, default consecutive), the
+    sums are float64 on the tensors' device."""
+
+    def __init__(self, keep=(0, 1), what="(row, channel)"):
+        self.keep, self.what = keep, what
+        self.d2, self.r2, self.rows = [], [], []
+
+    def add(self, got, ref, rows=None):
+        got = torch.view_as_real(got) if got.is_complex() else got
+        ref = torch.view_as_real(ref) if ref.is_complex() else ref
+        g, r = got.to(ref.device, torch.float64), ref.to(torch.float64)
+        dims = [d for d in range(r.dim()) if d not in self.keep]
+        self.d2.append(((g - r) ** 2).sum(dims).cpu())
+        self.r2.append((r * r).sum(dims).cpu())
+        n0 = sum(len(x) for x in self.rows)
+        self.rows.append(list(range(n0, n0 + r.shape[0])) if rows is None else list(rows))
+
+    def result(self):
+        """(global relative L2, worst slice's relative L2, index of the worst slice with its batch row)"""
+        d2, r2 = torch.cat(self.d2), torch.cat(self.r2)
+        rows = [b for x in self.rows for b in x]
+        per = (d2 / r2.clamp_min(1e-300)).sqrt()
+        i = int(per.reshape(-1).argmax())
+        idx = [int(v) for v in torch.unravel_index(torch.tensor(i), per.shape)]
+        idx[0] = rows[idx[0]]
+        return float((d2.sum() / r2.sum().clamp_min(1e-300)).sqrt()), float(per.max()), tuple(idx)
+
+    def check(self, name, tol_global, tol_slice):
+        glob, worst, idx = self.result()
+        print(f"[slices] {name}: global {glob:.3e}, worst {self.what} slice {worst:.3e} at {idx}")
+        assert glob < tol_global, f"{name}: global rel L2 {glob:.3e} >= {tol_global:.1e} (worst slice {worst:.3e} at {idx})"
+        assert worst < tol_slice, f"{name}: worst {self.what} slice {idx}: rel L2 {worst:.3e} >= {tol_slice:.1e} " \
+                                  f"(global {glob:.3e})"
+        return glob, worst
