@@ -51,7 +51,7 @@ class SphericalFourierNeuralOperatorNet(nn.Module):
         time_scale_shift_before_filter: bool = True,
         data_grid: str = "equiangular",
         seed: int = 0,
-        gemm_mode: Optional[str] = None,   # "f32" (fp32 MFMA) | "h3" (split-fp16 3-pass MFMA); default $SDY_GEMM_MODE or "f32"
+        gemm_mode: Optional[str] = None,   # "f32" (fp32 MFMA) | "h3" (split-fp16 3-pass MFMA); default $SDY_GEMM_MODE or "h3"
         **other,
     ):
         super().__init__()

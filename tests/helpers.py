@@ -2,11 +2,13 @@
 import torch
 
 from oracle.philox import drop_path_keep, element_keep_mask, element_keep_mask_torch
+from oracle.dyffusion import OracleDYffusion
 from oracle.sfno import OracleSFNO, SFNOConfig, make_state_dict
 
 
-def make_pair(cfg: SFNOConfig, n_in: int, n_cond: int, seed: int = 4321, net_seed: int = 99):
-    """(product net on cuda, oracle net) sharing a 'trained-like' state_dict."""
+def make_pair(cfg: SFNOConfig, n_in: int, n_cond: int, seed: int = 4321, net_seed: int = 99, gemm_mode=None):
+    """(product net on cuda, oracle net) sharing a 'trained-like' state_dict.  `gemm_mode`: the product network's kernel
+    family ("h3" | "f32"); None keeps the network's own default ($SDY_GEMM_MODE or "h3")."""
     import sdy_amd
 
     assert n_in + n_cond == cfg.in_chans
@@ -16,7 +18,7 @@ def make_pair(cfg: SFNOConfig, n_in: int, n_cond: int, seed: int = 4321, net_see
         spatial_shape_in=(cfg.nlat, cfg.nlon), embed_dim=cfg.embed_dim, num_layers=cfg.num_layers,
         mlp_ratio=cfg.mlp_ratio, dropout_mlp=cfg.dropout_mlp, drop_path_rate=cfg.drop_path_rate,
         with_time_emb=cfg.with_time_emb, data_grid=cfg.data_grid, big_skip=cfg.big_skip, pos_embed=cfg.pos_embed,
-        seed=net_seed, time_dim_mult=cfg.time_dim_mult,
+        seed=net_seed, time_dim_mult=cfg.time_dim_mult, gemm_mode=gemm_mode,
     )
     net.load_state_dict(sd, strict=True)
     if cfg.with_time_emb:
@@ -85,3 +87,26 @@ class SliceErrors:
         assert worst < tol_slice, f"{name}: worst {self.what} slice {idx}: rel L2 {worst:.3e} >= {tol_slice:.1e} " \
                                   f"(global {glob:.3e})"
         return glob, worst
+
+
+def oracle_sampling_chain(fcfg: SFNOConfig, fsd, icfg: SFNOConfig, isd, dropout_seed: int, x0, forc, dtype, horizon: int):
+    """One DYffusion sampling pass of the oracle's op sequence in `dtype`, evaluated by torch on the GPU
+    (OracleSFNO(device="cuda")): forecaster weights `fsd`, interpolator weights `isd` replaying the Philox dropout stream of
+    `dropout_seed` (call number = interpolator call index), initial condition `x0` and static forcing `forc`.  float64 is the
+    yardstick of the chain-error tests.  Returns {"t<k>_preds": CPU tensor}."""
+    fora, iora = OracleSFNO(fcfg, fsd, dtype=dtype, device="cuda"), OracleSFNO(icfg, isd, dtype=dtype, device="cuda")
+    masks = PhiloxMasks(icfg, seed=dropout_seed)
+    masks.device = "cuda"
+    n = {"i": 0}
+
+    def ora_i(x, time, condition=None, static_condition=None):
+        masks.call = n["i"]
+        n["i"] += 1
+        return iora(x, time=time, condition=condition, static_condition=static_condition, mask_fn=masks)
+
+    o = OracleDYffusion(lambda x, time, condition=None, static_condition=None: fora(
+        x, time=time, condition=condition, static_condition=static_condition), ora_i, timesteps=horizon)
+    out = {k: v.cpu() for k, v in o.sample(x0.cuda().to(dtype), static_condition=forc.cuda()).items()}
+    del fora, iora
+    torch.cuda.empty_cache()
+    return out

@@ -157,7 +157,7 @@ def test_c2_full_size_interpolator_forward():
     got = net(x.cuda(), time=t.cuda(), condition=cond.cuda())
     err = rel_l2(got, ref)
     assert err < TOL_NET, f"C2 full-size rel L2 {err:.3e} (bound 1e-4)"
-    assert err < TOL_TIGHT, f"C2 full-size rel L2 {err:.3e} (fp32-MFMA expectation)"
+    assert err < TOL_TIGHT, f"C2 full-size rel L2 {err:.3e} (bound of a single full-size forward, 2e-5)"
     # linearity-free, size-independent sanity at full size: batch consistency (B=2 rows equal B=1 results)
     x2 = torch.cat([x, x.flip(0)], 0).cuda()
     got2 = net(x2, time=torch.tensor([3.0, 3.0]).cuda(), condition=torch.cat([cond, cond], 0).cuda())
@@ -193,7 +193,7 @@ def test_c2_full_size_interpolator_forward_with_dropout():
     assert torch.isfinite(got).all()
     err = rel_l2(got, ref)
     assert err < TOL_NET, f"C2 full-size, dropout on: rel L2 {err:.3e} (bound 1e-4)"
-    assert err < TOL_TIGHT, f"C2 full-size, dropout on: rel L2 {err:.3e} (fp32-MFMA expectation)"
+    assert err < TOL_TIGHT, f"C2 full-size, dropout on: rel L2 {err:.3e} (bound of a single full-size forward, 2e-5)"
     # the masks matter at this depth: the next call of the stream gives a visibly different field
     again = net(x.cuda(), time=t.cuda(), condition=cond.cuda())
     assert rel_l2(again, ref) > 1e-3

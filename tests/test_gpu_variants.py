@@ -15,7 +15,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 #  they selected remain what other shapes take and are held to the oracle there, tests/test_gpu_sfno.py, test_gpu_golden.py)
 # SDY_NO_SKIP_FOLD: the first / last block's inner skip as the reference computes it (a convolution of the residual) instead of
 # folded into the dhconv weights -- the two agree to rounding, which this test holds them to
-VARIANTS = ["SDY_NO_DH_FRAG", "SDY_NO_FFT360", "SDY_NO_FUSED_MLP", "SDY_NO_LEG_FRAG", "SDY_NO_LEG_PAR", "SDY_NO_SKIP_FOLD"]
+# SDY_GEMM_MODE=f32: the fp32-MFMA network (the escape hatch from SDY_FLAG_F16_RANGE) -- every stage on
+# the fp32 GEMM, none of the split-fp16 kernels; tests/test_gpu_f32_path.py holds it to float64 in detail
+VARIANTS = {"SDY_NO_DH_FRAG": "1", "SDY_NO_FFT360": "1", "SDY_NO_FUSED_MLP": "1", "SDY_NO_LEG_FRAG": "1", "SDY_NO_LEG_PAR": "1",
+            "SDY_NO_SKIP_FOLD": "1", "SDY_GEMM_MODE": "f32"}
 TOL = 2e-5
 
 
@@ -34,10 +37,11 @@ def _run(tmp_path, tag, env_extra):
 def test_kernel_selection_switches_agree(tmp_path):
     ref = _run(tmp_path, "default", {})
     assert torch.isfinite(ref).all()
-    for v in VARIANTS:
-        got = _run(tmp_path, v, {v: "1"})
+    for v, val in VARIANTS.items():
+        got = _run(tmp_path, v, {v: val})
         err = (torch.linalg.vector_norm(got.double() - ref.double()) / torch.linalg.vector_norm(ref.double())).item()
-        assert err < TOL, f"{v}=1 differs from the default path: rel L2 {err:.3e}"
+        print(f"[variants] {v}={val}: rel L2 {err:.3e} vs the default path")
+        assert err < TOL, f"{v}={val} differs from the default path: rel L2 {err:.3e}"
 
 
 @pytest.mark.gpu

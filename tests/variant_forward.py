@@ -15,6 +15,7 @@ def main(out_path: str) -> None:
     cfg = SFNOConfig(in_chans=70, out_chans=34, nlat=180, nlon=360, embed_dim=256, num_layers=2, with_time_emb=True,
                      dropout_mlp=0.1, drop_path_rate=0.1, min_time=1.0, max_time=5.0)
     net, _, _ = make_pair(cfg, 68, 2)
+    assert net.gemm_mode == os.environ.get("SDY_GEMM_MODE", "h3")     # (SDY_GEMM_MODE=f32 reaches the network)
     g = torch.Generator(device="cpu").manual_seed(77)
     x = torch.randn(3, 68, cfg.nlat, cfg.nlon, generator=g).cuda()
     cond = torch.randn(3, 2, cfg.nlat, cfg.nlon, generator=g).cuda()
