@@ -493,6 +493,57 @@ int sdy_derived_water(const sdy_derived_args* args, void* stream);
 int sdy_time_mean_accumulate(const float* x, int n0, long stride0, int n1, long stride1, int t0, int T, int HW, float scale,
                              float* acc, void* stream);
 
+/* Value histograms of the inference loop's data writer (HistogramDataWriter,
+ * src/ace_inference/inference/data_writer/histograms.py; DynamicHistogram, src/ace_inference/core/histogram.py): per variable
+ * and lead time, n_bins constant-width bins whose range doubles until it holds every value seen.  One call adds ONE dict (all
+ * variables of the targets, or of the predictions) of one window, in three launches: min / max of every variable; the
+ * reference's range rules, one workgroup per variable; counting.  Nothing is read back: range, counts and bookkeeping stay on
+ * the device until the caller copies them.
+ *   data[v]: dev float, element (i0, i1, t, p) of variable v at data[v] + i0*s0[v] + i1*s1[v] + t*HW + p; every (i0, i1) is a
+ *            sample of lead time t_start + t (the window driver's member-stacked view, or flat rows with n0 = 1).  16-byte
+ *            loads when HW, every stride and every pointer allow them, scalar loads otherwise.
+ *   counts:  dev uint64 (nvars, n_times, n_bins), zeroed by the caller before the first call
+ *   state:   dev, sdy_hist_state_bytes(nvars) bytes, zeroed by the caller before the first call (private layout; a host copy
+ *            is read with sdy_hist_state_unpack_host)
+ * Edges are never stored: edge(i) = fl32(fl32(i * step) + start), step = fl32(fl32(stop - start) / n_bins), edge(n_bins) =
+ * stop -- numpy's float32 linspace, no FMA.  Bin k holds [edge(k), edge(k+1)), the last bin is closed on the right
+ * (np.histogram with explicit edges).  Range rules per variable with (vmin, vmax) of THIS call: vmin == vmax widens both by
+ * 1e-6 (fp32); the first call takes (vmin, vmax) as (start, stop); later, while vmin < start: start = fl32(stop - 2 *
+ * fl32(stop - start)) and every time row's counts become c[2j] + c[2j+1] in the upper half; then, while vmax > stop, the
+ * mirror image.  Where the reference would not terminate or would produce NaN edges -- a non-finite vmin / vmax, a zero-width
+ * fp32 range (also the first range of a constant field too large for +-1e-6 to change it), a range whose step is not a
+ * positive finite fp32 -- the variable's range and counts stay as they were, SDY_HIST_FLAG_RANGE is set in its sticky flags
+ * word, and its values are counted as "outside".  A value outside [start, stop] or a NaN is never counted; it adds one to the
+ * variable's "outside" counter (0 unless the flag is set).
+ * SDY_ERR_ARG, before anything is launched: NULL args / data[v] / state / counts, nvars outside 1..SDY_MAX_VARS, a
+ * non-positive n0 / n1 / T / HW / n_times, a negative stride, t_start < 0, t_start + T > n_times, n_bins odd or outside
+ * 2..SDY_HIST_MAX_BINS (the counting kernel keeps 4 x n_bins words in LDS).  SDY_ERR_UNSUPPORTED: T*HW > 2^30, T > 65535. */
+#define SDY_HIST_MAX_BINS 2048
+#define SDY_HIST_FLAG_RANGE 1u
+typedef struct sdy_hist_args {
+  int nvars;
+  const float* data[SDY_MAX_VARS];
+  long s0[SDY_MAX_VARS], s1[SDY_MAX_VARS];
+  int n0, n1, T, HW;
+  int t_start, n_times, n_bins;
+  void* state;
+  unsigned long long* counts;
+} sdy_hist_args;
+int sdy_hist_add(const sdy_hist_args* args, void* stream);
+size_t sdy_hist_args_bytes(void);         /* sizeof(sdy_hist_args) of the library (the bindings compare their layout) */
+size_t sdy_hist_state_bytes(int nvars);   /* 0 for nvars < 1 */
+/* Variable v of a HOST copy of `state`: range, whether a first range has been taken, the sticky flags, the outside counter
+ * (any output may be NULL). */
+int sdy_hist_state_unpack_host(const void* state_host, int v, float* start, float* stop, int* initialised, unsigned* flags,
+                               unsigned long long* outside);
+/* The same arithmetic on the host (the kernels and these entry points compile one header): the range rules for one
+ * (vmin, vmax) -> new range, doublings to the left and to the right, flags (SDY_HIST_FLAG_RANGE: range unchanged, 0
+ * doublings); the n_bins + 1 edges of a range; the bin of each of n values (-1: outside or NaN).  Host pointers, no device. */
+int sdy_hist_plan_host(float start, float stop, int initialised, float vmin, float vmax, int n_bins, float* new_start,
+                       float* new_stop, int* n_left, int* n_right, unsigned* flags);
+int sdy_hist_edges_host(float start, float stop, int n_bins, float* edges);
+int sdy_hist_bins_host(const float* x, long n, float start, float stop, int n_bins, int* bins);
+
 /* ---------------------------------------------------------------------------------------------------------
  * Sticky status word of the CURRENT device.  Kernels only ever set bits; the host reads (and optionally clears) it once per
  * window, not per launch (MultiStepStepper.run_on_batch does, after the window's single loss read-back).

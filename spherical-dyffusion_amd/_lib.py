@@ -153,6 +153,20 @@ class SdyDerivedArgs(C.Structure):
     ]
 
 
+SDY_HIST_MAX_BINS = 2048
+SDY_HIST_FLAG_RANGE = 1
+
+
+class SdyHistArgs(C.Structure):
+    _fields_ = [
+        ("nvars", C.c_int), ("data", C.c_void_p * SDY_MAX_VARS),
+        ("s0", C.c_long * SDY_MAX_VARS), ("s1", C.c_long * SDY_MAX_VARS),
+        ("n0", C.c_int), ("n1", C.c_int), ("T", C.c_int), ("HW", C.c_int),
+        ("t_start", C.c_int), ("n_times", C.c_int), ("n_bins", C.c_int),
+        ("state", C.c_void_p), ("counts", C.c_void_p),
+    ]
+
+
 # name -> (restype, argtypes); every symbol include/sdy_amd.h declares
 SIGNATURES = {
     "sdy_version": (C.c_int, []),
@@ -238,6 +252,15 @@ SIGNATURES = {
     "sdy_ensemble_series_grad": (C.c_int, [C.c_void_p, C.c_int, C.c_long, C.c_long, C.c_void_p, C.c_long, C.c_void_p,
                                           C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "sdy_derived_water": (C.c_int, [C.POINTER(SdyDerivedArgs), C.c_void_p]),
+    "sdy_hist_add": (C.c_int, [C.POINTER(SdyHistArgs), C.c_void_p]),
+    "sdy_hist_args_bytes": (C.c_size_t, []),
+    "sdy_hist_state_bytes": (C.c_size_t, [C.c_int]),
+    "sdy_hist_state_unpack_host": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                             C.POINTER(C.c_int), C.POINTER(C.c_uint), C.POINTER(C.c_ulonglong)]),
+    "sdy_hist_plan_host": (C.c_int, [C.c_float, C.c_float, C.c_int, C.c_float, C.c_float, C.c_int, C.POINTER(C.c_float),
+                                     C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint)]),
+    "sdy_hist_edges_host": (C.c_int, [C.c_float, C.c_float, C.c_int, C.c_void_p]),
+    "sdy_hist_bins_host": (C.c_int, [C.c_void_p, C.c_long, C.c_float, C.c_float, C.c_int, C.c_void_p]),
     "sdy_profile_enable": (C.c_int, [C.c_int]),
     "sdy_profile_stage_count": (C.c_int, []),
     "sdy_profile_stage_name": (C.c_char_p, [C.c_int]),
@@ -274,6 +297,9 @@ def _load():
     if lib.sdy_abi_check(sizes, len(structs)) != 0:
         raise ImportError(f"{LIB_PATH}: argument structures of the bindings and of the library differ in size "
                           f"({[C.sizeof(t) for t in structs]}): rebuild the library (make -C spherical-dyffusion_amd/csrc)")
+    if lib.sdy_hist_args_bytes() != C.sizeof(SdyHistArgs):
+        raise ImportError(f"{LIB_PATH}: sdy_hist_args of the bindings ({C.sizeof(SdyHistArgs)} bytes) and of the library "
+                          f"({lib.sdy_hist_args_bytes()}) differ: rebuild the library (make -C spherical-dyffusion_amd/csrc)")
     return lib
 
 

@@ -931,6 +931,91 @@ def gen_derived(tag="fx_derived"):
           "saved")
 
 
+def gen_histogram(tag="fx_histogram"):
+    """The reference's own `DynamicHistogram` (src/ace_inference/core/histogram.py; numpy only) fed the way
+    `_HistogramAggregator.record_batch` feeds it (data_writer/histograms.py:32-45: `transpose(1, 0, 2, 3).reshape(n_times,
+    -1)` of a (samples, time, lat, lon) array).  That class itself cannot be imported here (its module imports xarray), so the
+    two lines are restated below.  Per case and n_bins (300 and 8) a sequence of adds on a 12 x 24 grid:
+      grow      a first narrow window, one that exceeds the range on the right, one that exceeds it on the left by more
+                than 4x (several doublings in one add);
+      edges     a second add whose values sit exactly on interior edges and on the last edge;
+      constant  a constant field (range +-1e-6: a step below float32's spacing, runs of equal edges), then a wide one;
+      stacked   member-stacked 5-D predictions (members, samples, time, lat, lon); expected counts from the pooled reshape.
+    Stored: inputs, i_time_start, the (min, max) fed at each add, the edges after each add, the doublings each add made,
+    the final counts, numpy's version."""
+    from src.ace_inference.core.histogram import DynamicHistogram
+
+    class Counting(DynamicHistogram):
+        n_left = n_right = 0
+
+        def _double_size_left(self):
+            self.n_left += 1
+            super()._double_size_left()
+
+        def _double_size_right(self):
+            self.n_right += 1
+            super()._double_size_right()
+
+    def pooled(x):          # (..., samples, time, lat, lon) -> (time, everything else): record_batch's reshape, members pooled
+        x = x.reshape(-1, *x.shape[-3:])
+        return x.transpose(1, 0, 2, 3).reshape(x.shape[1], -1)
+
+    rng = np.random.default_rng(20240607)
+    H, W, S, n_times = 12, 24, 2, 6
+    f32 = lambda a: np.ascontiguousarray(a, dtype=np.float32)  # noqa: E731
+    out = dict(numpy_version=np.__version__, n_times=n_times)
+    cases = []
+    for n_bins in (300, 8):
+        def run(case, adds):
+            """adds: list of (array or callable(histogram) -> array, i_time_start)"""
+            key = f"{case}_b{n_bins}"
+            cases.append(key)
+            h = Counting(n_times=n_times, n_bins=n_bins)
+            for i, (x, t0) in enumerate(adds):
+                x = f32(x(h) if callable(x) else x)
+                left, right = h.n_left, h.n_right
+                v = pooled(x)
+                h.add(v, i_time_start=t0)
+                assert h.bin_edges.dtype == np.float32
+                out[f"{key}::in{i}"] = x
+                out[f"{key}::i_time_start{i}"] = t0
+                out[f"{key}::minmax{i}"] = np.array([v.min(), v.max()], dtype=np.float32)
+                out[f"{key}::edges{i}"] = h.bin_edges.copy()
+                out[f"{key}::doublings{i}"] = np.array([h.n_left - left, h.n_right - right])
+            out[f"{key}::n_adds"] = len(adds)
+            out[f"{key}::n_bins"] = n_bins
+            out[f"{key}::counts"] = h.counts.copy()
+            assert h.counts.sum() == sum(out[f"{key}::in{i}"].size for i in range(len(adds)))
+            return h
+
+        h = run("grow", [(280.0 + 2.0 * rng.standard_normal((S, 3, H, W)), 0),
+                         (283.0 + 4.0 * rng.standard_normal((S, 2, H, W)), 3),
+                         (250.0 + 25.0 * rng.standard_normal((S, 3, H, W)), 1)])
+        assert h.n_left >= 2 and h.n_right >= 1
+
+        def on_edges(h):
+            e = h.bin_edges
+            x = rng.uniform(e[0], e[-1], size=(S, 2, H, W)).astype(np.float32).clip(e[0], e[-1])
+            flat = x.reshape(-1)
+            picks = rng.integers(1, n_bins, size=200)
+            flat[:200] = e[picks]                 # exactly on interior edges: the bin to the right owns them
+            flat[200:260] = e[-1]                 # exactly on the last edge: the last bin is closed
+            flat[260:300] = e[0]
+            return rng.permutation(flat).reshape(x.shape)
+
+        run("edges", [(rng.uniform(-1.0, 1.0, size=(S, 3, H, W)), 0), (on_edges, 2), (on_edges, 4)])
+        h = run("constant", [(np.full((S, 2, H, W), 2.5), 0), (np.full((S, 1, H, W), 2.5), 4),
+                             (2.5 + 3.0 * rng.standard_normal((S, 3, H, W)), 2)])
+        assert h.n_left + h.n_right >= 20
+        E = 3
+        run("stacked", [(1.0e5 + 2.5e3 * rng.standard_normal((E, S, 4, H, W)), 0),
+                        (1.0e5 + 4.0e3 * rng.standard_normal((E, S, 2, H, W)), 4)])
+    out["cases"] = json.dumps(cases)
+    path = os.path.join(OUT, f"{tag}.npz")
+    np.savez_compressed(path, **out)
+    print(f"{tag}: {len(cases)} cases, {os.path.getsize(path)} bytes, saved")
+
+
 if __name__ == "__main__":
     torch.set_num_threads(8)
     if len(sys.argv) > 1:      # regenerate selected fixtures only: python tools/gen_golden.py gen_time_mean
@@ -963,6 +1048,7 @@ if __name__ == "__main__":
     gen_mean_series()
     gen_mean_series_grad()
     gen_derived()
+    gen_histogram()
     gen_sfno_wide_masks()
     gen_sfno_full()
     sizes = {n: os.path.getsize(os.path.join(OUT, n)) for n in sorted(os.listdir(OUT))}
