@@ -544,6 +544,34 @@ int sdy_hist_plan_host(float start, float stop, int initialised, float vmin, flo
 int sdy_hist_edges_host(float start, float stop, int n_bins, float* edges);
 int sdy_hist_bins_host(const float* x, long n, float start, float stop, int n_bins, int* bins);
 
+/* Time coarsening of the inference loop's data writer (TimeCoarsen,
+ * src/ace_inference/inference/data_writer/time_coarsen.py:65-134): one launch for all variables of ONE dict.
+ *   data[v]: dev float, element (i0, i1, t, p) of variable v at data[v] + i0*s0[v] + i1*s1[v] + t*HW + p, the in-place views
+ *            sdy_hist_add takes (member-stacked (members, samples, time, lat, lon), or flat rows with n0 = 1)
+ *   out[v]:  dev float, contiguous (n0, n1, T_out, HW), T_out = t_first + (T - t_first) / factor (integer division); the
+ *            pointers may point into one staging buffer
+ * Times t < t_first are copied unchanged (the initial condition of the first window); output time t_first + g is the mean of
+ * input times t_first + g*factor .. t_first + (g+1)*factor - 1; trailing times that do not fill a group are dropped (the
+ * reference's unfold(dimension=time, size=factor, step=factor).mean(-1)).  A mean is the fp32 sum of the group in time order
+ * divided by factor (a true division: torch's mean is sum / count); factor == 1 is a plain gather, bit for bit.  16-byte loads
+ * and stores when HW, every stride and every pointer allow them, scalar accesses otherwise.
+ * SDY_ERR_ARG, before anything is launched: NULL args / data[v] / out[v], nvars outside 1..SDY_MAX_VARS, a non-positive n0 /
+ * n1 / T / HW, a negative stride, factor < 1, t_first outside 0..T, T_out == 0.  SDY_ERR_UNSUPPORTED: T*HW > 2^30, n0*n1 >=
+ * 2^31 (the flat work index is 64-bit: n0*n1 has no grid-dimension limit).
+ * sdy_time_coarsen_host: the same structure with HOST pointers and the same checks; the arithmetic is the header the kernel
+ * compiles (csrc/coarsen_mean.h), so the semantics can be pinned without a device. */
+typedef struct sdy_coarsen_args {
+  int nvars;
+  const float* data[SDY_MAX_VARS];
+  long s0[SDY_MAX_VARS], s1[SDY_MAX_VARS];
+  float* out[SDY_MAX_VARS];
+  int n0, n1, T, HW;
+  int t_first, factor;
+} sdy_coarsen_args;
+int sdy_time_coarsen(const sdy_coarsen_args* args, void* stream);
+int sdy_time_coarsen_host(const sdy_coarsen_args* args);
+size_t sdy_coarsen_args_bytes(void);      /* sizeof(sdy_coarsen_args) of the library (the bindings compare their layout) */
+
 /* ---------------------------------------------------------------------------------------------------------
  * Sticky status word of the CURRENT device.  Kernels only ever set bits; the host reads (and optionally clears) it once per
  * window, not per launch (MultiStepStepper.run_on_batch does, after the window's single loss read-back).

@@ -167,6 +167,16 @@ class SdyHistArgs(C.Structure):
     ]
 
 
+class SdyCoarsenArgs(C.Structure):
+    _fields_ = [
+        ("nvars", C.c_int), ("data", C.c_void_p * SDY_MAX_VARS),
+        ("s0", C.c_long * SDY_MAX_VARS), ("s1", C.c_long * SDY_MAX_VARS),
+        ("out", C.c_void_p * SDY_MAX_VARS),
+        ("n0", C.c_int), ("n1", C.c_int), ("T", C.c_int), ("HW", C.c_int),
+        ("t_first", C.c_int), ("factor", C.c_int),
+    ]
+
+
 # name -> (restype, argtypes); every symbol include/sdy_amd.h declares
 SIGNATURES = {
     "sdy_version": (C.c_int, []),
@@ -261,6 +271,9 @@ SIGNATURES = {
                                      C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint)]),
     "sdy_hist_edges_host": (C.c_int, [C.c_float, C.c_float, C.c_int, C.c_void_p]),
     "sdy_hist_bins_host": (C.c_int, [C.c_void_p, C.c_long, C.c_float, C.c_float, C.c_int, C.c_void_p]),
+    "sdy_time_coarsen": (C.c_int, [C.POINTER(SdyCoarsenArgs), C.c_void_p]),
+    "sdy_time_coarsen_host": (C.c_int, [C.POINTER(SdyCoarsenArgs)]),
+    "sdy_coarsen_args_bytes": (C.c_size_t, []),
     "sdy_profile_enable": (C.c_int, [C.c_int]),
     "sdy_profile_stage_count": (C.c_int, []),
     "sdy_profile_stage_name": (C.c_char_p, [C.c_int]),
@@ -300,6 +313,9 @@ def _load():
     if lib.sdy_hist_args_bytes() != C.sizeof(SdyHistArgs):
         raise ImportError(f"{LIB_PATH}: sdy_hist_args of the bindings ({C.sizeof(SdyHistArgs)} bytes) and of the library "
                           f"({lib.sdy_hist_args_bytes()}) differ: rebuild the library (make -C spherical-dyffusion_amd/csrc)")
+    if lib.sdy_coarsen_args_bytes() != C.sizeof(SdyCoarsenArgs):
+        raise ImportError(f"{LIB_PATH}: sdy_coarsen_args of the bindings ({C.sizeof(SdyCoarsenArgs)} bytes) and of the library "
+                          f"({lib.sdy_coarsen_args_bytes()}) differ: rebuild the library (make -C spherical-dyffusion_amd/csrc)")
     return lib
 
 

@@ -52,6 +52,11 @@ def _layout(v: torch.Tensor) -> Tuple[torch.Tensor, int, int, int, int, int, int
     """-> (tensor to keep alive, n0, n1, s0, s1, T, HW): element (i0, i1, t, p) at data_ptr + i0*s0 + i1*s1 + t*HW + p."""
     if not v.is_cuda:
         raise RuntimeError("sdy_amd histograms run on the GPU only (no CPU fallback)")
+    return _strided_layout(v)
+
+
+def _strided_layout(v: torch.Tensor) -> Tuple[torch.Tensor, int, int, int, int, int, int]:
+    """`_layout` without the device check (shared with `sdy_amd.data_writer`, whose callers check the device themselves)."""
     if v.dim() < 3:
         raise ValueError(f"expected (..., time, lat, lon), got {tuple(v.shape)}")
     v = v.to(torch.float32)

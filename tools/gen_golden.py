@@ -13,6 +13,7 @@ strict=True, which also pins the state_dict contract (names + shapes) of SURVEY.
 import json
 import os
 import sys
+import types
 
 import numpy as np
 import torch
@@ -1016,6 +1017,82 @@ def gen_histogram(tag="fx_histogram"):
     print(f"{tag}: {len(cases)} cases, {os.path.getsize(path)} bytes, saved")
 
 
+def gen_time_coarsen(tag="fx_time_coarsen"):
+    """The reference's own `TimeCoarsen` (src/ace_inference/inference/data_writer/time_coarsen.py) around a recording writer.
+    Per grid -- 6 x 12 (HW = 72) and 5 x 7 (HW = 35) -- two windows of 2 samples as `run_inference` hands them over: 1 + 6
+    times at start_timestep 0, then 6 times at start_timestep 7; targets {a}, predictions {a, b}; unit-scale Gaussians (normal
+    range, no subnormals).  Per factor 1, 2, 3, 4 (six times by 4: one group and a dropped tail) every call the wrapped writer
+    receives is stored: tensors, start_timestep, start_sample, times.  `batch_times` is a stand-in with the two xarray calls
+    the reference makes (`isel`, `coarsen(...).mean()`) on a (sample, time) float64 array; like the tensors' unfold it drops a
+    tail that does not fill a group (xarray's boundary="trim"; its default would refuse the factor 4 case)."""
+    from src.ace_inference.inference.data_writer.time_coarsen import TimeCoarsen
+
+    class Times:
+        def __init__(self, values):
+            self.values = np.asarray(values)
+
+        def isel(self, indexers):
+            return Times(self.values[:, indexers["time"]])
+
+        def coarsen(self, windows):
+            f, v = windows["time"], self.values
+            n = v.shape[1] // f
+            grouped = v[:, :n * f].reshape(v.shape[0], n, f)
+            return types.SimpleNamespace(mean=lambda: Times(grouped.mean(axis=-1)))
+
+    class Recorder:
+        def __init__(self):
+            self.calls = []
+
+        def append_batch(self, target, prediction, start_timestep, start_sample, batch_times):
+            self.calls.append(({k: v.clone().numpy() for k, v in target.items()},
+                               {k: v.clone().numpy() for k, v in prediction.items()}, start_timestep, start_sample,
+                               batch_times.values.copy()))
+
+        def flush(self):
+            pass
+
+    g = torch.Generator(device="cpu").manual_seed(20240917)
+    S, start_sample = 2, 3
+    windows = ((0, 7), (7, 6))            # (start_timestep, times)
+    factors = (1, 2, 3, 4)
+    out = dict(factors=np.array(factors), start_sample=start_sample, window_starts=np.array([w[0] for w in windows]))
+    cases = []
+    for H, W in ((6, 12), (5, 7)):
+        grid = f"g{H}x{W}"
+        data = []
+        for w, (t0, T) in enumerate(windows):
+            target = {"a": torch.randn(S, T, H, W, generator=g)}
+            prediction = {n: torch.randn(S, T, H, W, generator=g) for n in ("a", "b")}
+            times = np.arange(t0, t0 + T, dtype=np.float64)[None, :] * 6.0 + np.array([[0.0], [1000.0]])
+            data.append((target, prediction, t0, times))
+            for src, d in (("target", target), ("prediction", prediction)):
+                for n, v in d.items():
+                    assert np.isfinite(v.numpy()).all() and (np.abs(v.numpy()) >= np.finfo(np.float32).tiny).all()
+                    out[f"{grid}::w{w}::{src}::{n}"] = v.numpy()
+            out[f"{grid}::w{w}::times"] = times
+        for f in factors:
+            case = f"{grid}_f{f}"
+            cases.append(case)
+            rec = Recorder()
+            tc = TimeCoarsen(rec, f)
+            for target, prediction, t0, times in data:
+                tc.append_batch(target, prediction, t0, start_sample, Times(times))
+            out[f"{case}::n_calls"] = len(rec.calls)
+            for j, (tgt, pred, st, ss, bt) in enumerate(rec.calls):
+                for src, d in (("target", tgt), ("prediction", pred)):
+                    for n, v in d.items():
+                        assert v.dtype == np.float32
+                        out[f"{case}::call{j}::{src}::{n}"] = v
+                out[f"{case}::call{j}::start_timestep"] = st
+                out[f"{case}::call{j}::start_sample"] = ss
+                out[f"{case}::call{j}::times"] = bt
+    out["cases"] = json.dumps(cases)
+    path = os.path.join(OUT, f"{tag}.npz")
+    np.savez_compressed(path, **out)
+    print(f"{tag}: {len(cases)} cases, {os.path.getsize(path)} bytes, saved")
+
+
 if __name__ == "__main__":
     torch.set_num_threads(8)
     if len(sys.argv) > 1:      # regenerate selected fixtures only: python tools/gen_golden.py gen_time_mean
@@ -1049,6 +1126,7 @@ if __name__ == "__main__":
     gen_mean_series_grad()
     gen_derived()
     gen_histogram()
+    gen_time_coarsen()
     gen_sfno_wide_masks()
     gen_sfno_full()
     sizes = {n: os.path.getsize(os.path.join(OUT, n)) for n in sorted(os.listdir(OUT))}
