@@ -572,6 +572,67 @@ int sdy_time_coarsen(const sdy_coarsen_args* args, void* stream);
 int sdy_time_coarsen_host(const sdy_coarsen_args* args);
 size_t sdy_coarsen_args_bytes(void);      /* sizeof(sdy_coarsen_args) of the library (the bindings compare their layout) */
 
+/* Per-grid-point video statistics of the inference aggregators (VideoAggregator with its extended statistics,
+ * src/ace_inference/core/aggregator/inference/video.py): one launch adds ONE window of all variables to float64 accumulators
+ * that stay on the device.
+ *   gen[v]:    dev float, element (i0, i1, t, p) of variable v at gen[v] + i0*gs0 + i1*gs1 + t*HW + p: the member-stacked
+ *              (members, samples, time, lat, lon) view of the window driver, or flat rows with n0 = 1.  All n0*n1 rows are
+ *              pooled (the reference's class takes 4-D data only: pooling members is this library's rule)
+ *   target[v]: dev float, element (i1, t, p) at target[v] + i1*ts1 + t*HW + p
+ *   accumulators: dev double, contiguous (nvars, n_timesteps, HW) each -- variable v's (n_timesteps, HW) block at
+ *              base + v*n_timesteps*HW; window time t lands at time t_start + t.  gen_mean and target_mean are required; the
+ *              other five are updated where their pointer is non-NULL (the caller fills err_min / err_max with +inf / -inf and
+ *              the rest with 0 before the first call):
+ *                gen_mean += mean over the generated rows      target_mean += mean over the target rows
+ *                gen_sq, target_sq += mean of the squares
+ *                err_var += UNBIASED variance over the rows of e (one row adds NaN, as torch.var of one sample)
+ *                err_min = min(err_min, min over rows of e)    err_max likewise; a NaN wins, as in torch.minimum
+ *              e of row (i0, i1) = fl32(gen - target row i1), the reference's single fp32 subtraction, widened to double;
+ *              every sum is float64.
+ * Exactly one thread owns an accumulator element (no atomics): calls that touch the same times must be ordered on a stream.
+ * 16-byte loads when HW, every stride and every pointer allow them, scalar loads otherwise.
+ * SDY_ERR_ARG, before anything is launched: NULL args / gen[v] / target[v] / gen_mean / target_mean, nvars outside
+ * 1..SDY_MAX_VARS, a non-positive n0 / n1 / T / HW / n_timesteps, a negative stride, t_start < 0, t_start + T > n_timesteps.
+ * SDY_ERR_UNSUPPORTED: T*HW > 2^30, n0*n1 >= 2^31, n_timesteps*HW >= 2^40 (flat accumulator indices are 64-bit).
+ * The _host twin: the same structure with HOST pointers and the same checks; the arithmetic is the header the kernel compiles
+ * (csrc/field_stats.h), so the semantics can be pinned without a device. */
+typedef struct sdy_video_args {
+  int nvars;
+  const float* gen[SDY_MAX_VARS];
+  const float* target[SDY_MAX_VARS];
+  long gs0, gs1, ts1;
+  int n0, n1, T, HW;
+  int t_start, n_timesteps;
+  double *gen_mean, *target_mean, *gen_sq, *target_sq, *err_var, *err_min, *err_max;
+} sdy_video_args;
+int sdy_video_accumulate(const sdy_video_args* args, void* stream);
+int sdy_video_accumulate_host(const sdy_video_args* args);
+size_t sdy_video_args_bytes(void);        /* sizeof(sdy_video_args) of the library (the bindings compare their layout) */
+
+/* Zonal means of the inference aggregators (ZonalMeanAggregator, .../aggregator/inference/zonal_mean.py): one launch adds ONE
+ * window of all variables.  gen / target / strides as above with HW = H*W.
+ *   gen_acc, target_acc: dev double, contiguous (nvars, n1, n_timesteps, H) each, zeroed by the caller before the first call:
+ *     gen_acc[v, s, t_start + t, lat]    += mean over the n0 members of the mean over the W longitudes of gen[v][., s, t, lat, .]
+ *     target_acc[v, s, t_start + t, lat] += mean over the W longitudes of target[v][s, t, lat, .]
+ *   summed in float64 (the reference sums in fp32).  The member mean is this library's rule: the reference drops the zonal
+ *   mean for ensembles.  One wave per latitude row (several rows per wave when a row has fewer than 64 loads), cross-lane
+ *   reduction, no atomics.
+ * SDY_ERR_ARG, before anything is launched: NULL args / gen[v] / target[v] / gen_acc / target_acc, nvars outside
+ * 1..SDY_MAX_VARS, a non-positive n0 / n1 / T / H / W / n_timesteps, a negative stride, t_start < 0, t_start + T >
+ * n_timesteps.  SDY_ERR_UNSUPPORTED: T*H*W > 2^30, n0*n1 >= 2^31, n_timesteps*H >= 2^40, n1*n_timesteps*H >= 2^50. */
+typedef struct sdy_zonal_args {
+  int nvars;
+  const float* gen[SDY_MAX_VARS];
+  const float* target[SDY_MAX_VARS];
+  long gs0, gs1, ts1;
+  int n0, n1, T, H, W;
+  int t_start, n_timesteps;
+  double *gen_acc, *target_acc;
+} sdy_zonal_args;
+int sdy_zonal_accumulate(const sdy_zonal_args* args, void* stream);
+int sdy_zonal_accumulate_host(const sdy_zonal_args* args);
+size_t sdy_zonal_args_bytes(void);        /* sizeof(sdy_zonal_args) of the library (the bindings compare their layout) */
+
 /* ---------------------------------------------------------------------------------------------------------
  * Sticky status word of the CURRENT device.  Kernels only ever set bits; the host reads (and optionally clears) it once per
  * window, not per launch (MultiStepStepper.run_on_batch does, after the window's single loss read-back).

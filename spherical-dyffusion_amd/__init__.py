@@ -18,6 +18,7 @@ from .loop import NullAggregator, NullDataWriter, WindowStitcher, run_inference 
 from . import checkpoint, data_writer, derived, ensemble, histogram, interface, metrics, normalizer, ops, synthetic  # noqa: F401
 from .derived import compute_derived_quantities  # noqa: F401
 from .histogram import DynamicHistogram, HistogramDataWriter  # noqa: F401
+from .metrics import VideoAggregator, ZonalMeanAggregator  # noqa: F401
 from .data_writer import DataWriter, DataWriterConfig, PredictionDataWriter, TimeCoarsen, TimeCoarsenConfig  # noqa: F401
 
 __version__ = "0.1.0"

@@ -177,6 +177,27 @@ class SdyCoarsenArgs(C.Structure):
     ]
 
 
+class SdyVideoArgs(C.Structure):
+    _fields_ = [
+        ("nvars", C.c_int), ("gen", C.c_void_p * SDY_MAX_VARS), ("target", C.c_void_p * SDY_MAX_VARS),
+        ("gs0", C.c_long), ("gs1", C.c_long), ("ts1", C.c_long),
+        ("n0", C.c_int), ("n1", C.c_int), ("T", C.c_int), ("HW", C.c_int),
+        ("t_start", C.c_int), ("n_timesteps", C.c_int),
+        ("gen_mean", C.c_void_p), ("target_mean", C.c_void_p), ("gen_sq", C.c_void_p), ("target_sq", C.c_void_p),
+        ("err_var", C.c_void_p), ("err_min", C.c_void_p), ("err_max", C.c_void_p),
+    ]
+
+
+class SdyZonalArgs(C.Structure):
+    _fields_ = [
+        ("nvars", C.c_int), ("gen", C.c_void_p * SDY_MAX_VARS), ("target", C.c_void_p * SDY_MAX_VARS),
+        ("gs0", C.c_long), ("gs1", C.c_long), ("ts1", C.c_long),
+        ("n0", C.c_int), ("n1", C.c_int), ("T", C.c_int), ("H", C.c_int), ("W", C.c_int),
+        ("t_start", C.c_int), ("n_timesteps", C.c_int),
+        ("gen_acc", C.c_void_p), ("target_acc", C.c_void_p),
+    ]
+
+
 # name -> (restype, argtypes); every symbol include/sdy_amd.h declares
 SIGNATURES = {
     "sdy_version": (C.c_int, []),
@@ -274,6 +295,12 @@ SIGNATURES = {
     "sdy_time_coarsen": (C.c_int, [C.POINTER(SdyCoarsenArgs), C.c_void_p]),
     "sdy_time_coarsen_host": (C.c_int, [C.POINTER(SdyCoarsenArgs)]),
     "sdy_coarsen_args_bytes": (C.c_size_t, []),
+    "sdy_video_accumulate": (C.c_int, [C.POINTER(SdyVideoArgs), C.c_void_p]),
+    "sdy_video_accumulate_host": (C.c_int, [C.POINTER(SdyVideoArgs)]),
+    "sdy_video_args_bytes": (C.c_size_t, []),
+    "sdy_zonal_accumulate": (C.c_int, [C.POINTER(SdyZonalArgs), C.c_void_p]),
+    "sdy_zonal_accumulate_host": (C.c_int, [C.POINTER(SdyZonalArgs)]),
+    "sdy_zonal_args_bytes": (C.c_size_t, []),
     "sdy_profile_enable": (C.c_int, [C.c_int]),
     "sdy_profile_stage_count": (C.c_int, []),
     "sdy_profile_stage_name": (C.c_char_p, [C.c_int]),
@@ -316,6 +343,11 @@ def _load():
     if lib.sdy_coarsen_args_bytes() != C.sizeof(SdyCoarsenArgs):
         raise ImportError(f"{LIB_PATH}: sdy_coarsen_args of the bindings ({C.sizeof(SdyCoarsenArgs)} bytes) and of the library "
                           f"({lib.sdy_coarsen_args_bytes()}) differ: rebuild the library (make -C spherical-dyffusion_amd/csrc)")
+    for what, theirs, ours in (("sdy_video_args", lib.sdy_video_args_bytes(), C.sizeof(SdyVideoArgs)),
+                               ("sdy_zonal_args", lib.sdy_zonal_args_bytes(), C.sizeof(SdyZonalArgs))):
+        if theirs != ours:
+            raise ImportError(f"{LIB_PATH}: {what} of the bindings ({ours} bytes) and of the library ({theirs}) differ: "
+                              "rebuild the library (make -C spherical-dyffusion_amd/csrc)")
     return lib
 
 

@@ -12,9 +12,11 @@ from __future__ import annotations
 import ctypes as C
 from typing import Dict, List, Mapping, Optional, Sequence
 
+import numpy as np
 import torch
 
-from ._lib import check, current_stream, lib, ptr
+from ._lib import SDY_MAX_VARS, SdyVideoArgs, SdyZonalArgs, check, current_stream, lib, ptr
+from .histogram import _strided_layout
 
 
 def spherical_area_weights(lats, num_lon: int) -> torch.Tensor:
@@ -68,18 +70,21 @@ class TorchDistributed:
         return self._dist.get_world_size() if self._dist is not None else 1
 
     def reduce_sum(self, tensor: torch.Tensor) -> torch.Tensor:
+        return tensor if self._dist is None else self._reduce(tensor, self._dist.ReduceOp.SUM)
+
+    def _reduce(self, tensor: torch.Tensor, op) -> torch.Tensor:
         if self._dist is None:
             return tensor
         if not tensor.is_cuda:
             out = tensor.clone()
-            self._dist.all_reduce(out)
+            self._dist.all_reduce(out, op=op)
             return out
         if self._stream is None:
             self._stream = torch.cuda.Stream(device=tensor.device)
         self._stream.wait_stream(torch.cuda.current_stream(tensor.device))
         with torch.cuda.stream(self._stream):
             out = tensor.clone()
-            self._dist.all_reduce(out)
+            self._dist.all_reduce(out, op=op)
         torch.cuda.current_stream(tensor.device).wait_stream(self._stream)
         return out
 
@@ -87,6 +92,14 @@ class TorchDistributed:
         if self._dist is None:
             return tensor
         return self.reduce_sum(tensor) / self.world_size
+
+    def reduce_min(self, tensor: torch.Tensor) -> torch.Tensor:
+        """What the reference's `VideoAggregator` asks of its `dist` for the error extremes: all_reduce with MIN (`reduce_max`:
+        MAX) on the side stream; identity without a process group."""
+        return tensor if self._dist is None else self._reduce(tensor, self._dist.ReduceOp.MIN)
+
+    def reduce_max(self, tensor: torch.Tensor) -> torch.Tensor:
+        return tensor if self._dist is None else self._reduce(tensor, self._dist.ReduceOp.MAX)
 
 
 class TimeMeanAggregator:
@@ -437,6 +450,276 @@ class OneStepMeanAggregator:
         return {k: float(self._dist.reduce_mean(logs[k].reshape(1))[0]) for k in sorted(logs)}
 
 
+class _FieldAccumulator:
+    """What `VideoAggregator` and `ZonalMeanAggregator` share: the layouts of a window's tensors, the float64 accumulators
+    (one flat device buffer per statistic, the variables' blocks in dict order, so a run of same-shaped variables is one
+    contiguous `(nvars, ...)` block: what one launch takes), the memory limit and the per-time batch counts (host integers)."""
+
+    def __init__(self, n_timesteps: int, dist=None, metadata=None, max_bytes: Optional[int] = None):
+        if n_timesteps < 1:
+            raise ValueError(f"n_timesteps must be positive, got {n_timesteps}")
+        self._n_timesteps = int(n_timesteps)
+        self._dist = TorchDistributed() if dist is None else dist
+        self._metadata = {} if metadata is None else metadata
+        self._max_bytes = max_bytes
+        self._n_batches = [0] * self._n_timesteps
+        self._names: Optional[List[str]] = None
+        self._grids: List[tuple] = []
+        self._acc: Dict[str, torch.Tensor] = {}
+        self._offsets: List[int] = []
+
+    # -- to be provided: statistic name -> fill value, and the accumulator elements of one variable
+    def _statistics(self) -> Dict[str, float]:
+        raise NotImplementedError
+
+    def _block(self, n1: int, H: int, W: int) -> int:
+        raise NotImplementedError
+
+    def _layouts(self, target_data, gen_data, i_time_start: int):
+        """Per generated variable (gen, target, n0, n1, gs0, gs1, ts1, T, H, W), everything checked; nothing is enqueued."""
+        if len(gen_data) == 0:
+            raise ValueError("No data in gen_data")
+        out = []
+        for name, g in gen_data.items():
+            if name not in target_data:
+                raise ValueError(f"no target for generated variable {name!r}")
+            t = target_data[name]
+            if g.dim() not in (4, 5) or t.dim() != 4:
+                raise ValueError(f"{name!r}: generated data are (samples, time, lat, lon) or (members, samples, time, lat, lon)"
+                                 f" and targets (samples, time, lat, lon), got {tuple(g.shape)} and {tuple(t.shape)}")
+            if tuple(g.shape[-4:]) != tuple(t.shape):
+                raise ValueError(f"{name!r}: generated {tuple(g.shape)} against target {tuple(t.shape)}")
+            H, W = g.shape[-2:]
+            gv, n0, n1, gs0, gs1, T, _ = _strided_layout(g)
+            tv, _, tn1, _, ts1, _, _ = _strided_layout(t)
+            if min(n0, n1, T, H, W) < 1:
+                raise ValueError("empty tensor")
+            if (n0, n1) != (1 if g.dim() == 4 else g.shape[0], tn1):   # (a 5-D view that had to be copied came back flat)
+                gv = gv.view(g.shape)
+                n0, n1, gs0, gs1 = g.shape[0], g.shape[1], gv.stride(0), gv.stride(1)
+            out.append((gv, tv, n0, n1, gs0, gs1, ts1, T, H, W))
+        T = out[0][7]
+        if any(l[7] != T for l in out):
+            raise ValueError("the variables of one window differ in their number of times")
+        if i_time_start < 0 or i_time_start + T > self._n_timesteps:
+            raise ValueError(f"times {i_time_start}..{i_time_start + T - 1} outside the aggregator's {self._n_timesteps}")
+        return out
+
+    def _prepare(self, names: List[str], lay) -> torch.device:
+        """First batch: the memory limit, the device check, then the accumulators.  Later batches: the same variables and
+        grids as the first."""
+        on_device = all(l[0].is_cuda and l[1].is_cuda for l in lay)
+        grids = [(l[3], l[8], l[9]) for l in lay]
+        if self._names is None:
+            stats = self._statistics()
+            total = sum(self._block(*g) for g in grids) * self._n_timesteps
+            need = len(stats) * total * 8
+            device = lay[0][0].device
+            limit = self._max_bytes
+            if limit is None and on_device:
+                limit = torch.cuda.get_device_properties(device).total_memory // 4
+            if limit is not None and need > limit:
+                raise ValueError(f"{type(self).__name__}: {len(stats)} statistics x {len(names)} variables x "
+                                 f"{self._n_timesteps} timesteps need {need} bytes of float64 accumulators, more than "
+                                 f"max_bytes = {limit}")
+        elif names != self._names or grids != self._grids:
+            raise ValueError("the variables, sample count or grids of a window differ from the first window's")
+        if not on_device:
+            raise RuntimeError("sdy_amd aggregators run on the GPU only (no CPU fallback)")
+        if self._names is None:
+            self._acc = {k: torch.full((total,), fill, dtype=torch.float64, device=device) for k, fill in stats.items()}
+            self._offsets, at = [], 0
+            for g in grids:
+                self._offsets.append(at)
+                at += self._block(*g) * self._n_timesteps
+            self._names, self._grids = list(names), grids
+        return next(iter(self._acc.values())).device
+
+    def _runs(self, lay):
+        """Runs of consecutive variables that one launch takes: same extents and strides, at most SDY_MAX_VARS."""
+        first = 0
+        while first < len(lay):
+            last = first + 1
+            while last < len(lay) and last - first < SDY_MAX_VARS and lay[last][2:] == lay[first][2:]:
+                last += 1
+            yield first, last
+            first = last
+
+    def _record(self, target_data, gen_data, i_time_start: int) -> None:
+        i_time_start = int(i_time_start)
+        lay = self._layouts(target_data, gen_data, i_time_start)
+        device = self._prepare(list(gen_data), lay)
+        for l in lay:
+            if l[0].device != device or l[1].device != device:
+                raise ValueError(f"tensors on {l[0].device} / {l[1].device}, accumulators on {device}")
+        with torch.cuda.device(device):
+            for first, last in self._runs(lay):
+                self._launch(lay, first, last, i_time_start)
+        for t in range(i_time_start, i_time_start + lay[0][7]):
+            self._n_batches[t] += 1
+
+    def _counts(self) -> torch.Tensor:
+        if self._names is None:
+            raise RuntimeError("No data recorded")
+        return torch.tensor(self._n_batches, dtype=torch.float64, device=next(iter(self._acc.values())).device)
+
+    def _view(self, stat: str, i: int, *shape) -> torch.Tensor:
+        n = 1
+        for d in shape:
+            n *= d
+        return self._acc[stat][self._offsets[i]:self._offsets[i] + n].view(*shape)
+
+    def get_logs(self, label: str) -> Dict[str, object]:
+        """{}: the wandb videos / images of the reference are out of scope, and the log key sets stay what they were."""
+        return {}
+
+
+class VideoAggregator(_FieldAccumulator):
+    """Videos of state evolution: device mirror of `VideoAggregator`
+    (`src/ace_inference/core/aggregator/inference/video.py`) minus the wandb rendering.
+
+    Same constructor keywords (`n_timesteps`, `enable_extended_videos`, `dist`, `metadata`) plus `max_bytes`, same
+    `record_batch`.  A window is never copied to the host (the reference moves every tensor with `.cpu()`): one
+    `sdy_video_accumulate` launch per run of same-shaped variables adds the window to float64 accumulators
+    `(n_timesteps, lat, lon)` on the device -- per variable the mean of gen and target, and with `enable_extended_videos` the
+    mean squares, the unbiased variance of the error over the rows and the error's extremes.  `get_data()` returns the
+    reference's `_get_data(label="")` as float64 device tensors `(n_timesteps, lat, lon)`: `<name>` is a pair
+    `{"gen", "target"}`; extended: `bias/<name>`, `rmse/<name>` = sqrt(err_var / n_batches), `min_err/<name>`,
+    `max_err/<name>`, `gen_var/<name>` = (E[g^2] - E[g]^2) / (E[t^2] - E[t]^2).  `get_dataset()` gives the same as numpy
+    arrays under the reference's dataset keys (`/` -> `_`; the pair stacked `(source, timestep, lat, lon)`, gen first).
+    `get_logs` returns {}.
+
+    The accumulators are allocated on the first batch, after comparing statistics x variables x n_timesteps x lat x lon x 8
+    bytes with `max_bytes` (default: a quarter of the device's memory): videos are a short-run diagnostic.
+
+    Ensembles.  The reference's class cannot take member-stacked data (its buffers come out `(n_timesteps, time, lat, lon)`
+    for 5-D input), so the rule is this library's own: a `(members, samples, time, lat, lon)` gen is POOLED over members x
+    samples, as the histogram writer pools it, and the error of row (member, sample) is taken against target row `sample` --
+    what the reference computes from flat `(members * samples, ...)` gen and the target repeated per member.
+
+    Ranks: the reference's equal-weight `dist.reduce_mean` (`reduce_min` / `reduce_max` for the extremes); ragged shares with
+    `sample_weights` are out of scope."""
+
+    def __init__(self, n_timesteps: int, enable_extended_videos: bool, dist=None, metadata=None,
+                 max_bytes: Optional[int] = None):
+        super().__init__(n_timesteps, dist=dist, metadata=metadata, max_bytes=max_bytes)
+        self._extended = bool(enable_extended_videos)
+
+    def _statistics(self) -> Dict[str, float]:
+        stats = {"gen_mean": 0.0, "target_mean": 0.0}
+        if self._extended:
+            stats.update(gen_sq=0.0, target_sq=0.0, err_var=0.0, err_min=float("inf"), err_max=float("-inf"))
+        return stats
+
+    def _block(self, n1: int, H: int, W: int) -> int:
+        return H * W
+
+    def _launch(self, lay, first: int, last: int, t_start: int) -> None:
+        a = SdyVideoArgs()
+        a.nvars = last - first
+        for j in range(first, last):
+            a.gen[j - first], a.target[j - first] = ptr(lay[j][0]), ptr(lay[j][1])
+        _, _, a.n0, a.n1, a.gs0, a.gs1, a.ts1, a.T, H, W = lay[first]
+        a.HW, a.t_start, a.n_timesteps = H * W, t_start, self._n_timesteps
+        for stat, buf in self._acc.items():
+            setattr(a, stat, buf.data_ptr() + 8 * self._offsets[first])
+        check(lib.sdy_video_accumulate(C.byref(a), current_stream()), "sdy_video_accumulate")
+
+    @torch.no_grad()
+    def record_batch(self, loss, target_data, gen_data, target_data_norm=None, gen_data_norm=None, i_time_start: int = 0):
+        del loss, target_data_norm, gen_data_norm
+        self._record(target_data, gen_data, i_time_start)
+
+    @torch.no_grad()
+    def get_data(self) -> Dict[str, object]:
+        n = self._counts()[:, None, None]
+        red = self._dist.reduce_mean
+        data: Dict[str, object] = {}
+        for i, name in enumerate(self._names):
+            shape = (self._n_timesteps,) + self._grids[i][1:]
+            gen, target = red(self._view("gen_mean", i, *shape) / n), red(self._view("target_mean", i, *shape) / n)
+            data[name] = {"gen": gen, "target": target}
+            if self._extended:
+                data[f"bias/{name}"] = gen - target
+        if self._extended:
+            for stat, label in (("err_var", "rmse"), ("err_min", "min_err"), ("err_max", "max_err")):
+                for i, name in enumerate(self._names):
+                    x = self._view(stat, i, self._n_timesteps, *self._grids[i][1:])
+                    data[f"{label}/{name}"] = (torch.sqrt(red(x / n)) if stat == "err_var" else
+                                               self._dist.reduce_min(x) if stat == "err_min" else self._dist.reduce_max(x))
+            for i, name in enumerate(self._names):
+                shape = (self._n_timesteps,) + self._grids[i][1:]
+                var = {}
+                for src in ("gen", "target"):
+                    mean = red(self._view(f"{src}_mean", i, *shape) / n)
+                    var[src] = red(self._view(f"{src}_sq", i, *shape) / n) - mean ** 2
+                data[f"gen_var/{name}"] = var["gen"] / var["target"]
+        return data
+
+    @torch.no_grad()
+    def get_dataset(self) -> Dict[str, np.ndarray]:
+        out = {}
+        for label, d in self.get_data().items():
+            key = label.replace("/", "_")
+            if isinstance(d, Mapping):
+                out[key] = np.stack([d["gen"].cpu().numpy(), d["target"].cpu().numpy()], axis=0)
+            else:
+                out[key] = d.cpu().numpy()
+        return out
+
+
+class ZonalMeanAggregator(_FieldAccumulator):
+    """Zonal means as a function of latitude and time (hovmollers): device mirror of `ZonalMeanAggregator`
+    (`src/ace_inference/core/aggregator/inference/zonal_mean.py`) minus the wandb images.
+
+    Same constructor keywords plus `max_bytes`, same `record_batch`; one `sdy_zonal_accumulate` launch per run of same-shaped
+    variables adds a window's longitude means to float64 accumulators `(samples, n_timesteps, lat)` (the reference sums in
+    fp32).  `get_data()` returns `{"gen/<name>", "error/<name>"}`, each a float64 device tensor `(n_timesteps, lat)`: the
+    sample mean of `acc / n_batches`, error = gen - target.  These are the arrays the reference turns into images; its
+    transpose-and-flip for the picture (`data.t().flip(dims=[0])`) is NOT applied.  `get_logs` returns {}.
+
+    Ensembles: the reference drops this aggregator for ensembles, so the rule is this library's own -- the zonal mean of a
+    `(members, samples, time, lat, lon)` gen is the member mean, per sample.  Ranks: the reference's equal-weight
+    `dist.reduce_mean`; ragged shares with `sample_weights` are out of scope."""
+
+    def __init__(self, n_timesteps: int, dist=None, metadata=None, max_bytes: Optional[int] = None):
+        super().__init__(n_timesteps, dist=dist, metadata=metadata, max_bytes=max_bytes)
+
+    def _statistics(self) -> Dict[str, float]:
+        return {"gen_acc": 0.0, "target_acc": 0.0}
+
+    def _block(self, n1: int, H: int, W: int) -> int:
+        return n1 * H
+
+    def _launch(self, lay, first: int, last: int, t_start: int) -> None:
+        a = SdyZonalArgs()
+        a.nvars = last - first
+        for j in range(first, last):
+            a.gen[j - first], a.target[j - first] = ptr(lay[j][0]), ptr(lay[j][1])
+        _, _, a.n0, a.n1, a.gs0, a.gs1, a.ts1, a.T, a.H, a.W = lay[first]
+        a.t_start, a.n_timesteps = t_start, self._n_timesteps
+        for stat, buf in self._acc.items():
+            setattr(a, stat, buf.data_ptr() + 8 * self._offsets[first])
+        check(lib.sdy_zonal_accumulate(C.byref(a), current_stream()), "sdy_zonal_accumulate")
+
+    @torch.no_grad()
+    def record_batch(self, loss, target_data, gen_data, target_data_norm=None, gen_data_norm=None, i_time_start: int = 0):
+        del loss, target_data_norm, gen_data_norm
+        self._record(target_data, gen_data, i_time_start)
+
+    @torch.no_grad()
+    def get_data(self) -> Dict[str, torch.Tensor]:
+        n = self._counts()[None, :, None]
+        data = {}
+        for i, name in enumerate(self._names):
+            n1, H, _ = self._grids[i]
+            gen = self._view("gen_acc", i, n1, self._n_timesteps, H)
+            target = self._view("target_acc", i, n1, self._n_timesteps, H)
+            data[f"gen/{name}"] = self._dist.reduce_mean(gen / n).mean(dim=0)
+            data[f"error/{name}"] = self._dist.reduce_mean((gen - target) / n).mean(dim=0)
+        return data
+
+
 class InferenceAggregator:
     """The aggregator `run_inference` is handed by the reference's entry point (`inference/inference.py:247-262`): `mean`
     (per-step series, denormalised), `mean_norm` (normalised), `time_mean`, and `mean_step_20` when asked for, behind ONE
@@ -448,14 +731,20 @@ class InferenceAggregator:
 
     `grad_mag_percent_diff=True` adds the reference's `weighted_grad_mag_percent_diff/<var>` to `mean`, `mean_norm` and
     `mean_step_20`.  It is off by default: the default key set of the logs stays what existing callers rely on, and a
-    drop-in caller of the reference passes `grad_mag_percent_diff=True` to get the reference's full key set."""
+    drop-in caller of the reference passes `grad_mag_percent_diff=True` to get the reference's full key set.
+
+    `video_data=True` (`extended_video_data=True` for the extended statistics too) and `zonal_mean_data=True` add the
+    `video` / `zonal_mean` aggregators (`VideoAggregator`, `ZonalMeanAggregator`): the numbers behind the reference's videos
+    and hovmollers, accumulated on the device and read with `get_video_data()` / `get_zonal_mean_data()`.  They add no log
+    keys, and `log_video` / `enable_extended_videos` / `log_zonal_mean_images` (the rendered products) keep raising."""
 
     accepts_sample_weights = True
 
     def __init__(self, area_weights: torch.Tensor, sigma_coordinates=None, n_timesteps: Optional[int] = None,
                  n_ensemble_members: int = 1, record_step_20: bool = False, log_video: bool = False,
                  enable_extended_videos: bool = False, log_zonal_mean_images: bool = False, dist=None, metadata=None,
-                 device=None, grad_mag_percent_diff: bool = False):
+                 device=None, grad_mag_percent_diff: bool = False, video_data: bool = False,
+                 extended_video_data: bool = False, zonal_mean_data: bool = False):
         if log_video or enable_extended_videos or log_zonal_mean_images:
             raise NotImplementedError("video / zonal-mean image logging is out of scope of sdy_amd (DESIGN.md section 8)")
         if n_timesteps is None:
@@ -472,6 +761,11 @@ class InferenceAggregator:
         }
         if record_step_20:
             self._aggregators["mean_step_20"] = OneStepMeanAggregator(target_time=20, **kw)
+        if video_data or extended_video_data:
+            self._aggregators["video"] = VideoAggregator(n_timesteps=n_timesteps, enable_extended_videos=extended_video_data,
+                                                         dist=dist, metadata=metadata)
+        if zonal_mean_data:
+            self._aggregators["zonal_mean"] = ZonalMeanAggregator(n_timesteps=n_timesteps, dist=dist, metadata=metadata)
 
     @torch.no_grad()
     def record_batch(self, loss, target_data, gen_data, target_data_norm, gen_data_norm, i_time_start: int = 0,
@@ -499,3 +793,11 @@ class InferenceAggregator:
 
     def get_time_mean_maps(self):
         return self._aggregators["time_mean"].time_mean_maps()
+
+    def get_video_data(self):
+        """`VideoAggregator.get_data()` of the run (`video_data=True` / `extended_video_data=True`)."""
+        return self._aggregators["video"].get_data()
+
+    def get_zonal_mean_data(self):
+        """`ZonalMeanAggregator.get_data()` of the run (`zonal_mean_data=True`)."""
+        return self._aggregators["zonal_mean"].get_data()

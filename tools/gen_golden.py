@@ -1093,6 +1093,147 @@ def gen_time_coarsen(tag="fx_time_coarsen"):
     print(f"{tag}: {len(cases)} cases, {os.path.getsize(path)} bytes, saved")
 
 
+class NoDist:
+    """One process: the reductions over ranks are identities."""
+
+    def reduce_mean(self, t):
+        return t
+
+    reduce_min = reduce_max = reduce_mean
+
+
+FIELD_T, FIELD_MEMBERS = 3, 3
+
+
+def _field_cases():
+    """The inputs `gen_video` and `gen_zonal_mean` share, from one seed: per case a list of windows
+    (i_time_start, target {name: (S, T, H, W)}, gen {name: (S, T, H, W)}), fed the way `run_inference` feeds an aggregator --
+    the first window holds T + 1 times (the initial condition), later ones T, n_timesteps = 1 + 3T, T = 3 -- followed by a second
+    pass with fresh data over the first two windows' times, so times 0 .. 2T get n_batches = 2 and the rest 1.  S = 1, 2, 3
+    samples on a 16 x 32 grid (one variable) and on an odd 7 x 10 grid (two variables; HW % 4 != 0).  Unit-scale Gaussians with
+    a per-variable offset, so bias, variance and zonal structure are all non-trivial."""
+    g = torch.Generator(device="cpu").manual_seed(20241017)
+    T = FIELD_T
+    starts = ((0, T + 1), (T + 1, T), (2 * T + 1, T), (0, T + 1), (T + 1, T))
+    cases = {}
+    for (H, W), names in (((16, 32), ("a",)), ((7, 10), ("a", "b"))):
+        for S in (1, 2, 3):
+            lat = torch.linspace(-1.0, 1.0, H)[None, None, :, None]
+            windows = []
+            for t0, n in starts:
+                target = {k: torch.randn(S, n, H, W, generator=g) + 3.0 * j + lat for j, k in enumerate(names)}
+                gen = {k: target[k] + 0.5 * torch.randn(S, n, H, W, generator=g) + 0.25 for k in names}
+                windows.append((t0, target, gen))
+            cases[f"g{H}x{W}_s{S}"] = windows
+    return cases, 1 + 3 * T
+
+
+def _field_digest(windows):
+    return sum(float(v.double().abs().sum()) for _, target, gen in windows for d in (target, gen) for v in d.values())
+
+
+def _strip(label):
+    return label.strip("/")
+
+
+def gen_video(tag="fx_video"):
+    """The reference's own `VideoAggregator` (src/ace_inference/core/aggregator/inference/video.py), with and without
+    `enable_extended_videos`, on `_field_cases()` -- whose inputs and i_time_starts fx_zonal_mean.npz holds (the float64
+    videos fill this file; the inputs are not stored twice, a digest of them is) --: every array of `_get_data("")` (labels without
+    the leading slash; the pair as `<name>::gen` / `<name>::target`).  The plain aggregator's pair is checked here to be the
+    extended one's, bit for bit, and stored once.  `min_err` / `max_err` are stored as the float32 they are (checked).
+    Plus one "pooled" case: E = 3 members x S = 2 samples on the 7 x 10 grid, fed to the reference as flat (E * S, T, H, W) gen
+    (member-major) with the target repeated E times -- what a member-stacked (E, S, T, H, W) gen must reproduce."""
+    from src.ace_inference.core.aggregator.inference.video import VideoAggregator
+
+    cases, n_timesteps = _field_cases()
+    out = dict(n_timesteps=n_timesteps, members=FIELD_MEMBERS)
+
+    def run(case, windows):
+        ext = VideoAggregator(n_timesteps, True, dist=NoDist())
+        plain = VideoAggregator(n_timesteps, False, dist=NoDist())
+        for t0, target, gen in windows:
+            for agg in (ext, plain):
+                agg.record_batch(loss=0.0, target_data=target, gen_data=gen, i_time_start=t0)
+        data, pdata = ext._get_data(""), plain._get_data("")
+        assert [k for k in data if k in pdata] == list(pdata)
+        labels = []
+        for label, d in data.items():
+            key = _strip(label)
+            labels.append(key)
+            assert d.gen.dtype == torch.float64
+            if d.target is not None:
+                assert torch.equal(d.gen, pdata[label].gen) and torch.equal(d.target, pdata[label].target)
+                out[f"{case}::out::{key}::gen"] = d.gen.numpy()
+                out[f"{case}::out::{key}::target"] = d.target.numpy()
+            elif key.startswith(("min_err/", "max_err/")):
+                a = d.gen.numpy()
+                assert np.array_equal(a.astype(np.float32).astype(np.float64), a)
+                out[f"{case}::out::{key}"] = a.astype(np.float32)
+            else:
+                out[f"{case}::out::{key}"] = d.gen.numpy()
+        out[f"{case}::labels"] = json.dumps(labels)
+
+    for case, windows in cases.items():
+        out[f"{case}::inputs_digest"] = _field_digest(windows)
+        run(case, windows)
+    # pooled: member-stacked inputs are stored; the reference sees them flat
+    g = torch.Generator(device="cpu").manual_seed(20241018)
+    E, S, H, W = FIELD_MEMBERS, 2, 7, 10
+    case, windows, flat = "pooled", [], []
+    for t0, n in ((0, FIELD_T + 1), (FIELD_T + 1, FIELD_T), (2 * FIELD_T + 1, FIELD_T)):
+        target = {k: torch.randn(S, n, H, W, generator=g) + j for j, k in enumerate(("a", "b"))}
+        gen = {k: target[k][None] + 0.5 * torch.randn(E, S, n, H, W, generator=g) for k in target}
+        windows.append((t0, target, gen))
+        flat.append((t0, {k: v.repeat(E, 1, 1, 1) for k, v in target.items()},
+                     {k: v.reshape(E * S, n, H, W) for k, v in gen.items()}))
+    out[f"{case}::starts"] = np.array([w[0] for w in windows])
+    out[f"{case}::names"] = json.dumps(["a", "b"])
+    for i, (t0, target, gen) in enumerate(windows):
+        for k in target:
+            out[f"{case}::w{i}::target::{k}"] = target[k].numpy()
+            out[f"{case}::w{i}::gen::{k}"] = gen[k].numpy()
+    run(case, flat)
+    out["cases"] = json.dumps(list(cases) + [case])
+    path = os.path.join(OUT, f"{tag}.npz")
+    np.savez_compressed(path, **out)
+    print(f"{tag}: {len(cases) + 1} cases, {os.path.getsize(path)} bytes, saved")
+
+
+def gen_zonal_mean(tag="fx_zonal_mean"):
+    """The reference's own `ZonalMeanAggregator` (src/ace_inference/core/aggregator/inference/zonal_mean.py) on the inputs of
+    `_field_cases()`, stored here for this fixture and for fx_video.npz (windows `<case>::w<i>::<target|gen>::<name>`,
+    `<case>::starts`): per case and variable the two (n_timesteps, lat) arrays `get_logs` hands to `wandb.Image`, with its transpose-and-flip for the picture undone."""
+    from src.ace_inference.core.aggregator.inference import zonal_mean as ref
+
+    class Images:
+        @staticmethod
+        def Image(data, caption=None):
+            return data.flip(dims=[0]).t().contiguous()       # back from the picture's orientation to (time, lat)
+
+    ref.wandb = Images
+    cases, n_timesteps = _field_cases()
+    out = dict(n_timesteps=n_timesteps)
+    for case, windows in cases.items():
+        agg = ref.ZonalMeanAggregator(n_timesteps, dist=NoDist())
+        out[f"{case}::starts"] = np.array([w[0] for w in windows])
+        out[f"{case}::names"] = json.dumps(list(windows[0][1]))
+        out[f"{case}::inputs_digest"] = _field_digest(windows)
+        for i, (t0, target, gen) in enumerate(windows):
+            for k in target:
+                out[f"{case}::w{i}::target::{k}"] = target[k].numpy()
+                out[f"{case}::w{i}::gen::{k}"] = gen[k].numpy()
+            agg.record_batch(loss=0.0, target_data=target, gen_data=gen, target_data_norm=target, gen_data_norm=gen,
+                             i_time_start=t0)
+        for label, a in agg.get_logs("").items():
+            assert a.dtype == torch.float32 and tuple(a.shape) == (n_timesteps, next(iter(windows[0][1].values())).shape[2])
+            out[f"{case}::out::{_strip(label)}"] = a.numpy()
+    out["cases"] = json.dumps(list(cases))
+    path = os.path.join(OUT, f"{tag}.npz")
+    np.savez_compressed(path, **out)
+    print(f"{tag}: {len(cases)} cases, {os.path.getsize(path)} bytes, saved")
+
+
 if __name__ == "__main__":
     torch.set_num_threads(8)
     if len(sys.argv) > 1:      # regenerate selected fixtures only: python tools/gen_golden.py gen_time_mean
@@ -1127,6 +1268,8 @@ if __name__ == "__main__":
     gen_derived()
     gen_histogram()
     gen_time_coarsen()
+    gen_video()
+    gen_zonal_mean()
     gen_sfno_wide_masks()
     gen_sfno_full()
     sizes = {n: os.path.getsize(os.path.join(OUT, n)) for n in sorted(os.listdir(OUT))}
