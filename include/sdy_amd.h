@@ -485,6 +485,66 @@ typedef struct {
 } sdy_derived_args;
 int sdy_derived_water(const sdy_derived_args* args, void* stream);
 
+/* Post-step state corrector of the stepper (Corrector, src/ace_inference/core/corrector.py), applied to the B samples of one
+ * step: gen is the network's output, `in` the state it stepped from.  Per sample, with mean_w the area-weighted global mean
+ * (metrics.weighted_mean) and dp_k / twp / dry as above, the reference's three rules in its order:
+ *   SDY_CORRECTOR_DRY_AIR   err = mean_w(dry(gen)) - mean_w(dry(in));
+ *                           ps  = ((dry(gen) - err) + sum_k (ak[k+1]-ak[k])*q_k) / (1 - sum_k (bk[k+1]-bk[k])*q_k)
+ *   SDY_CORRECTOR_ZERO_ADV  adv -= mean_w(adv)
+ *   budget (with the ps left by the first rule): tend = (twp(gen) - twp(in)) / 21600, evap = lhf / 2.5e6
+ *     1 precipitation   prate *= (mean_w(evap) - mean_w(tend)) / mean_w(prate)
+ *     2 evaporation     lhf    = (evap * (mean_w(tend) + mean_w(prate)) / mean_w(evap)) * 2.5e6
+ *     3 / 4             1 / 2, then adv = tend - (evap - prate) per column with the corrected evap / prate
+ * Elementwise arithmetic is fp32 in the reference's operation order (no FMA contraction, levels summed in order); the global
+ * sums are float64 and deterministic: per-workgroup partials of fixed 1024-column chunks in the workspace, summed in chunk order
+ * by one thread per sample, no atomics -- a sample's result depends neither on B, nor on its place in the batch, nor on the run.
+ * Three launches whatever B, K and the flags: reduce (reads every needed plane once), solve (B threads), apply (re-reads what
+ * the rewritten fields depend on).  mean_w(tend) is taken as affine in err (it is, per column, up to fp32 rounding), so the
+ * apply pass needs no second reduction.  The scalars never leave the device.
+ *   variable: element (b, p) at base + b*stride + channel*HW + p, physical value x*std + mean; the corrected value y is stored as
+ *             (y - mean)/std with the gen variable's mean / std.  Two layouts: the stepper's packed (B, n, HW) tensors (stride =
+ *             n*HW, channel = the variable's index) and plain per-variable tensors (channel 0, mean 0, std 1: exact).
+ *   out_*:    where a rewritten field goes: the gen variable itself (in place) or a plane of its own; nothing else is written.
+ *             out_ps with DRY_AIR, out_adv with ZERO_ADV or budget 3 / 4, out_prate with budget 1 / 3, out_lhf with 2 / 4.
+ *             An out plane may be the gen variable's own plane but must not overlap any other plane that is read.
+ *   area:     dev float (HW), the weights.   ws: dev, 8-byte aligned, at least the workspace bytes of (B, HW); scratch only.
+ *   needed:   gen_q / in_q / gen_ps / in_ps with DRY_AIR or a budget; gen_adv with ZERO_ADV; gen_lhf / gen_prate with a budget.
+ * Any HW >= 1; 16-byte loads when HW, every stride and every plane address allow it, 4-byte loads otherwise (same sums either
+ * way).  A zero mean_w(prate) / mean_w(evap) or 1 - sum (bk[k+1]-bk[k])*q_k = 0 gives inf / nan as in the reference.
+ * SDY_ERR_ARG, before anything is launched: NULL args / area / ws or a needed variable's base / out, B or HW < 1, K outside
+ * 1..SDY_DERIVED_MAX_LEVELS when water is needed, unknown flag bits, budget outside 0..4, a negative channel or stride, with
+ * B > 1 a stride below (channel+1)*HW, std not finite and > 0, mean not finite, ws misaligned or ws_bytes too small.
+ * SDY_ERR_UNSUPPORTED: B > 65535.  The host twin computes the same on host memory (ws may be NULL). */
+#define SDY_CORRECTOR_DRY_AIR 1
+#define SDY_CORRECTOR_ZERO_ADV 2
+typedef struct sdy_corrector_var {
+  const float* base;
+  long stride;
+  int channel;
+  float mean, std;
+} sdy_corrector_var;
+typedef struct sdy_corrector_out {
+  float* base;
+  long stride;
+  int channel;
+} sdy_corrector_out;
+typedef struct sdy_corrector_args {
+  int B, HW, K;
+  int flags;    /* SDY_CORRECTOR_DRY_AIR | SDY_CORRECTOR_ZERO_ADV */
+  int budget;   /* 0 none, 1 precipitation, 2 evaporation, 3 advection_and_precipitation, 4 advection_and_evaporation */
+  float ak[SDY_DERIVED_MAX_LEVELS + 1], bk[SDY_DERIVED_MAX_LEVELS + 1];
+  const float* area;
+  sdy_corrector_var gen_q[SDY_DERIVED_MAX_LEVELS], in_q[SDY_DERIVED_MAX_LEVELS];
+  sdy_corrector_var gen_ps, in_ps, gen_lhf, gen_prate, gen_adv;
+  sdy_corrector_out out_ps, out_lhf, out_prate, out_adv;
+  void* ws;
+  size_t ws_bytes;
+} sdy_corrector_args;
+int sdy_corrector(const sdy_corrector_args* args, void* stream);
+int sdy_corrector_host(const sdy_corrector_args* args);
+size_t sdy_corrector_workspace_bytes(int B, int HW);
+size_t sdy_corrector_args_bytes(void);    /* sizeof(sdy_corrector_args) of the library (the bindings compare their layout) */
+
 /* Time-mean accumulation of the inference aggregator (src/ace_inference/core/aggregator/inference/time_mean.py:97-117,
  * _add_or_initialize_time_mean): acc[p] += scale * sum over rows (r0, r1) and times t0 <= t < T of
  * x[r0*stride0 + r1*stride1 + t*HW + p].  x: dev, one variable of a window, (n0, n1, T, HW) with float strides for the

@@ -153,6 +153,34 @@ class SdyDerivedArgs(C.Structure):
     ]
 
 
+SDY_CORRECTOR_DRY_AIR = 1
+SDY_CORRECTOR_ZERO_ADV = 2
+SDY_CORRECTOR_BUDGET = {None: 0, "precipitation": 1, "evaporation": 2, "advection_and_precipitation": 3,
+                        "advection_and_evaporation": 4}
+
+
+class SdyCorrectorVar(C.Structure):
+    _fields_ = [("base", C.c_void_p), ("stride", C.c_long), ("channel", C.c_int), ("mean", C.c_float), ("std", C.c_float)]
+
+
+class SdyCorrectorOut(C.Structure):
+    _fields_ = [("base", C.c_void_p), ("stride", C.c_long), ("channel", C.c_int)]
+
+
+class SdyCorrectorArgs(C.Structure):
+    _fields_ = [
+        ("B", C.c_int), ("HW", C.c_int), ("K", C.c_int), ("flags", C.c_int), ("budget", C.c_int),
+        ("ak", C.c_float * (SDY_DERIVED_MAX_LEVELS + 1)), ("bk", C.c_float * (SDY_DERIVED_MAX_LEVELS + 1)),
+        ("area", C.c_void_p),
+        ("gen_q", SdyCorrectorVar * SDY_DERIVED_MAX_LEVELS), ("in_q", SdyCorrectorVar * SDY_DERIVED_MAX_LEVELS),
+        ("gen_ps", SdyCorrectorVar), ("in_ps", SdyCorrectorVar), ("gen_lhf", SdyCorrectorVar),
+        ("gen_prate", SdyCorrectorVar), ("gen_adv", SdyCorrectorVar),
+        ("out_ps", SdyCorrectorOut), ("out_lhf", SdyCorrectorOut), ("out_prate", SdyCorrectorOut),
+        ("out_adv", SdyCorrectorOut),
+        ("ws", C.c_void_p), ("ws_bytes", C.c_size_t),
+    ]
+
+
 SDY_HIST_MAX_BINS = 2048
 SDY_HIST_FLAG_RANGE = 1
 
@@ -283,6 +311,10 @@ SIGNATURES = {
     "sdy_ensemble_series_grad": (C.c_int, [C.c_void_p, C.c_int, C.c_long, C.c_long, C.c_void_p, C.c_long, C.c_void_p,
                                           C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "sdy_derived_water": (C.c_int, [C.POINTER(SdyDerivedArgs), C.c_void_p]),
+    "sdy_corrector": (C.c_int, [C.POINTER(SdyCorrectorArgs), C.c_void_p]),
+    "sdy_corrector_host": (C.c_int, [C.POINTER(SdyCorrectorArgs)]),
+    "sdy_corrector_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "sdy_corrector_args_bytes": (C.c_size_t, []),
     "sdy_hist_add": (C.c_int, [C.POINTER(SdyHistArgs), C.c_void_p]),
     "sdy_hist_args_bytes": (C.c_size_t, []),
     "sdy_hist_state_bytes": (C.c_size_t, [C.c_int]),
@@ -343,7 +375,8 @@ def _load():
     if lib.sdy_coarsen_args_bytes() != C.sizeof(SdyCoarsenArgs):
         raise ImportError(f"{LIB_PATH}: sdy_coarsen_args of the bindings ({C.sizeof(SdyCoarsenArgs)} bytes) and of the library "
                           f"({lib.sdy_coarsen_args_bytes()}) differ: rebuild the library (make -C spherical-dyffusion_amd/csrc)")
-    for what, theirs, ours in (("sdy_video_args", lib.sdy_video_args_bytes(), C.sizeof(SdyVideoArgs)),
+    for what, theirs, ours in (("sdy_corrector_args", lib.sdy_corrector_args_bytes(), C.sizeof(SdyCorrectorArgs)),
+                               ("sdy_video_args", lib.sdy_video_args_bytes(), C.sizeof(SdyVideoArgs)),
                                ("sdy_zonal_args", lib.sdy_zonal_args_bytes(), C.sizeof(SdyZonalArgs))):
         if theirs != ours:
             raise ImportError(f"{LIB_PATH}: {what} of the bindings ({ours} bytes) and of the library ({theirs}) differ: "

@@ -92,7 +92,12 @@ class SteppedData:
 
 class MultiStepStepper:
     def __init__(self, module, in_names: List[str], out_names: List[str], forcing_names: List[str],
-                 means: Dict[str, float], stds: Dict[str, float], prescriber: Optional[Prescriber] = None):
+                 means: Dict[str, float], stds: Dict[str, float], prescriber: Optional[Prescriber] = None,
+                 corrector=None):
+        """`corrector` (not in the reference's multi-step stepper; `sdy_amd.Corrector`, the reference's `core/corrector.py`
+        as its single-module `core/stepper.py:542-543` applies it): every step's prediction is corrected against the state
+        it stepped from, on the device, before the loss terms, the prescriber, the timelines and the autoregressive
+        feedback see it.  None (the default): nothing changes and no launch is added."""
         self.module = module
         # init_packers (stepper_multistep.py:219-223): the in packer excludes the forcings
         self.in_names = [n for n in in_names if n not in forcing_names]
@@ -111,10 +116,15 @@ class MultiStepStepper:
             raise ValueError(f"more than {SDY_MAX_VARS} variables")
         # one entry per distinct variable of (in packer) U (out packer)
         self._entries = list(dict.fromkeys(self.in_names + self.out_names))
+        self.corrector = corrector
+        # raises ValueError unless every variable the corrector reads or rewrites is in both packers
+        self._correct = corrector.bind(self.in_names, self.out_names, self.means, self.stds) \
+            if corrector is not None and corrector.enabled else None
 
     @classmethod
     def from_statistics(cls, module, in_names: List[str], out_names: List[str], forcing_names: Optional[List[str]] = None,
-                        data_dir_stats=None, data_dir=None, prescriber: Optional[Prescriber] = None) -> "MultiStepStepper":
+                        data_dir_stats=None, data_dir=None, prescriber: Optional[Prescriber] = None,
+                        corrector=None) -> "MultiStepStepper":
         """The reference's constructor path (`stepper_multistep.py:103-131`): forcings default to the input-only names,
         the scalars of `normalize_names` = in U out come from `centering` / `scaling` found in `data_dir_stats`, `data_dir`
         or the packaged statistics (`normalizer.find_statistics`)."""
@@ -123,7 +133,7 @@ class MultiStepStepper:
             forcing_names = [n for n in in_names if n not in out_names]
         path_mean, path_std = find_statistics(data_dir_stats, data_dir)
         norm = get_normalizer(path_mean, path_std, list(dict.fromkeys(list(in_names) + list(out_names))))
-        return cls(module, in_names, out_names, forcing_names, norm.means, norm.stds, prescriber)
+        return cls(module, in_names, out_names, forcing_names, norm.means, norm.stds, prescriber, corrector)
 
     # ---- helpers ------------------------------------------------------------------------------------------------
     def _table(self, names: List[str], data: Dict[str, torch.Tensor]) -> SdyVarTable:
@@ -167,6 +177,7 @@ class MultiStepStepper:
             state = torch.empty(B, n_in, H, W, dtype=torch.float32, device=dev)
             check(lib.sdy_norm_pack(C.byref(in_tab), 0, T1, B, HW, ptr(state), stream()), "sdy_norm_pack")
             loss_terms = torch.zeros(n_forward_steps, B, 2, dtype=torch.float64, device=dev)
+            corr_ws = self._correct.workspace(B, HW, dev) if self._correct is not None else None     # once per window
 
             fa = SdyStepFinishArgs()
             fa.B, fa.HW, fa.T1 = B, HW, T1
@@ -205,11 +216,17 @@ class MultiStepStepper:
                                                        is_autoregressive=th > horizon, prepare_inputs=False,
                                                        num_predictions=1)
                 g = res[f"t{h}_preds_normed"].contiguous()
-                check(lib.sdy_lp_rel_terms(ptr(g), C.byref(out_tab), th, T1, B, HW, ptr(loss_terms[th - 1]), stream()),
-                      "sdy_lp_rel_terms")
                 ar = None
                 if "preds_autoregressive_init_normed" in res:   # the state handed to the next window differs from the
                     ar = res["preds_autoregressive_init_normed"].contiguous()   # prediction (stepper_multistep.py:412-418)
+                if self._correct is not None:       # in a copy, in the normalised space, against the state stepped from
+                    g = g.clone()
+                    self._correct(state, g, corr_ws)
+                    if ar is not None:
+                        ar = ar.clone()
+                        self._correct(state, ar, corr_ws)
+                check(lib.sdy_lp_rel_terms(ptr(g), C.byref(out_tab), th, T1, B, HW, ptr(loss_terms[th - 1]), stream()),
+                      "sdy_lp_rel_terms")
                 nxt = torch.empty_like(state)
                 fa.t, fa.gen, fa.prev_in, fa.next_in = th, ptr(g), ptr(state), ptr(nxt)
                 fa.ar_init = ptr(ar)

@@ -932,6 +932,94 @@ def gen_derived(tag="fx_derived"):
           "saved")
 
 
+def gen_corrector(tag="fx_corrector"):
+    """The reference's own `Corrector` (core/corrector.py) on CPU, per sample set and configuration.
+
+    Three sample sets (inputs stored once each): `b3k2` B = 3, K = 2 on 6 x 12; `b2k8` B = 2, K = 8 on 19 x 36; `b2k3` B = 2,
+    K = 3 on 7 x 9 (HW = 63: no multiple of 4).  Plausible fields, so that no global mean is near zero: ps 1e5 +- 3e3, q from
+    1e-6 aloft to 2e-2 at the surface, prate > 0 with mean 3e-5, lhf of order 80, adv of order 1e-5 with a non-zero mean; gen
+    is the input plus a step-sized change (a 15 Pa mean pressure drift), so the water-path tendency is the small difference
+    of large numbers it is in a rollout.  Configurations: each option alone (a budget mode alone is what the reference's class
+    accepts, its docstring notwithstanding), conserve_dry_air + zero advection + each of the four budget modes, all on every
+    set; and the full `advection_and_precipitation` combination once on `b3k2` under the alias names.  Recorded per case: the
+    rewritten variables as the reference returns them in float32 (`ref32`) and from float64 inputs (`ref64`)."""
+    from src.ace_inference.core.corrector import CorrectorConfig
+    from src.ace_inference.core.data_loading.data_typing import SigmaCoordinates
+
+    g = torch.Generator(device="cpu").manual_seed(90210)
+    ak8 = [3.0, 5238.4, 11815.8, 17263.1, 19929.5, 17023.4, 8970.5, 1537.5, 0.0]
+    bk8 = [0.0, 0.0, 0.0115, 0.0781, 0.2034, 0.4004, 0.6513, 0.9065, 1.0]
+    levels = {2: (ak8[::4], bk8[::4]), 3: ([ak8[i] for i in (0, 3, 6, 8)], [bk8[i] for i in (0, 3, 6, 8)]), 8: (ak8, bk8)}
+    adv_name = "tendency_of_total_water_path_due_to_advection"
+    plain = dict(ps="PRESsfc", lhf="LHTFLsfc", prate="PRATEsfc")
+    alias = dict(ps="PS", lhf="LHFLX", prate="surface_precipitation_rate")
+
+    def fields(B, K, H, W, names):
+        q_scale = torch.logspace(-6, -2, K) if K > 1 else torch.tensor([1e-2])
+        d_in, d_gen = {}, {}
+        for k in range(K):
+            d_in[f"specific_total_water_{k}"] = q_scale[k] * (1.0 + torch.rand(B, H, W, generator=g))
+            d_gen[f"specific_total_water_{k}"] = d_in[f"specific_total_water_{k}"] * (1.0 + 0.05 * torch.randn(B, H, W, generator=g))
+        d_in[names["ps"]] = 1.0e5 + 3.0e3 * torch.randn(B, H, W, generator=g)
+        d_gen[names["ps"]] = d_in[names["ps"]] + 15.0 + 200.0 * torch.randn(B, H, W, generator=g)
+        for d in (d_in, d_gen):
+            d[names["lhf"]] = 80.0 + 30.0 * torch.randn(B, H, W, generator=g)
+            d[names["prate"]] = 6.0e-5 * torch.rand(B, H, W, generator=g)
+            d[adv_name] = 3.0e-6 + 1.0e-5 * torch.randn(B, H, W, generator=g)
+            d["TMP2m"] = 280.0 + torch.randn(B, H, W, generator=g)              # an unrelated variable passes through
+        return d_in, d_gen
+
+    out = {}
+    sets = {}
+    for sname, (B, K, H, W) in (("b3k2", (3, 2, 6, 12)), ("b2k8", (2, 8, 19, 36)), ("b2k3", (2, 3, 7, 9))):
+        lat = (torch.arange(H, dtype=torch.float64) + 0.5) / H * np.pi - np.pi / 2
+        area = (torch.cos(lat)[:, None] * (1.0 + 0.1 * torch.rand(H, W, generator=g, dtype=torch.float64))).float()
+        d_in, d_gen = fields(B, K, H, W, plain)
+        sets[sname] = (K, area, d_in, d_gen)
+        ak, bk = levels[K]
+        out[f"{sname}::ak"], out[f"{sname}::bk"] = np.asarray(ak, np.float32), np.asarray(bk, np.float32)
+        out[f"{sname}::area"] = area.numpy()
+        out[f"{sname}::names"] = json.dumps(list(d_gen))
+        out.update({f"{sname}::in::{k}": v.numpy() for k, v in d_in.items()})
+        out.update({f"{sname}::gen::{k}": v.numpy() for k, v in d_gen.items()})
+    modes = ["precipitation", "evaporation", "advection_and_precipitation", "advection_and_evaporation"]
+    configs = [("dry", dict(conserve_dry_air=True)), ("zero_adv", dict(zero_global_mean_moisture_advection=True))]
+    configs += [(f"only_{m}", dict(moisture_budget_correction=m)) for m in modes]
+    configs += [(f"all_{m}", dict(conserve_dry_air=True, zero_global_mean_moisture_advection=True,
+                                  moisture_budget_correction=m)) for m in modes]
+    cases = []
+
+    def run(case, sname, cfg, rename):
+        K, area, d_in, d_gen = sets[sname]
+        rn = lambda n: rename.get(n, n)  # noqa: E731
+        ak, bk = out[f"{sname}::ak"], out[f"{sname}::bk"]
+        res = {}
+        for tagp, dt in (("ref32", torch.float32), ("ref64", torch.float64)):
+            sigma = SigmaCoordinates(ak=torch.tensor(ak).to(dt), bk=torch.tensor(bk).to(dt))
+            corr = CorrectorConfig(**cfg).build(area.to(dt), sigma)
+            i = {rn(k): v.to(dt) for k, v in d_in.items()}
+            o = {rn(k): v.to(dt) for k, v in d_gen.items()}
+            r = corr(i, o)
+            assert list(r) == list(o)
+            res[tagp] = {k: v for k, v in r.items() if v is not o[k]}
+            assert all(v.dtype == dt for v in res[tagp].values())
+        assert list(res["ref32"]) == list(res["ref64"]) and res["ref32"], case
+        cases.append(dict(name=case, set=sname, config=cfg, rename=rename, written=list(res["ref32"])))
+        for tagp, vals in res.items():
+            out.update({f"{case}::{tagp}::{k}": v.numpy() for k, v in vals.items()})
+
+    for sname in sets:
+        for cname, cfg in configs:
+            run(f"{sname}_{cname}", sname, cfg, {})
+    run("b3k2_alias", "b3k2", dict(conserve_dry_air=True, zero_global_mean_moisture_advection=True,
+                                   moisture_budget_correction="advection_and_precipitation"),
+        {plain[k]: alias[k] for k in plain})
+    out["cases"] = json.dumps(cases)
+    path = os.path.join(OUT, f"{tag}.npz")
+    np.savez_compressed(path, **out)
+    assert os.path.getsize(path) < (1 << 20), os.path.getsize(path)
+
+
 def gen_histogram(tag="fx_histogram"):
     """The reference's own `DynamicHistogram` (src/ace_inference/core/histogram.py; numpy only) fed the way
     `_HistogramAggregator.record_batch` feeds it (data_writer/histograms.py:32-45: `transpose(1, 0, 2, 3).reshape(n_times,
@@ -1266,6 +1354,7 @@ if __name__ == "__main__":
     gen_mean_series()
     gen_mean_series_grad()
     gen_derived()
+    gen_corrector()
     gen_histogram()
     gen_time_coarsen()
     gen_video()
