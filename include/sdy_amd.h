@@ -57,7 +57,8 @@ extern "C" {
 #define SDY_OK 0
 #define SDY_ERR_ARG (-1)         /* null pointer / non-positive extent */
 #define SDY_ERR_UNSUPPORTED (-2) /* size the kernels do not cover (e.g. nlon with a prime factor > 5) */
-#define SDY_ERR_ALIGN (-3)       /* extent along a contiguous dimension not a multiple of 4 */
+#define SDY_ERR_ALIGN (-3)       /* extent along a contiguous dimension not a multiple of 4, or a pointer that a kernel reads
+                                    or writes as float4 not 16-byte aligned (stated at the prototypes concerned) */
 #define SDY_ERR_WORKSPACE (-4)   /* workspace too small */
 #define SDY_ERR_NAME (-5)        /* unknown parameter name */
 #define SDY_ERR_SHAPE (-6)       /* parameter has the wrong number of elements */
@@ -367,10 +368,14 @@ int sdy_sfno_time_embed(sdy_sfno* net, const float* time, int B, float* t_repr, 
 
 /* ---------------------------------------------------------------------------------------------------------
  * Sampler arithmetic of BaseDYffusion.sample_loop (src/diffusion/dyffusion.py:517-519, :655-661). */
-/* out = x_s + (x_ip_next - x_ip_s); any of the three may alias out.  x_ip_s NULL means "x_ip_s == x_s" (s = 0). */
+/* out = x_s + (x_ip_next - x_ip_s); any of the three may alias out.  x_ip_s NULL means "x_ip_s == x_s" (s = 0).
+ * 16-byte aligned pointers are read and written as float4; if any of the four is not aligned, the whole range goes through
+ * 4-byte accesses instead (same values, bit for bit). */
 int sdy_cold_update(const float* x_s, const float* x_ip_next, const float* x_ip_s, float* out, size_t n,
                     void* stream);
-/* channel concat of up to 4 NCHW tensors (torch.cat(dim=1)) */
+/* channel concat of up to 4 NCHW tensors (torch.cat(dim=1)).  HW % 4 == 0 and every src[i] and out 16-byte aligned (float4
+ * copies), else SDY_ERR_ALIGN before anything is launched; the same holds for the inputs of sdy_sfno_forward, which are
+ * concatenated by the same kernels. */
 int sdy_concat_channels(const float* const* src, const int* chans, int nsrc, float* out, int B, int HW,
                         void* stream);
 
@@ -379,7 +384,12 @@ int sdy_concat_channels(const float* const* src, const int* chans, int nsrc, flo
  * run_on_batch_multistep (src/ace_inference/core/stepper_multistep.py:298-466): StandardNormalizer
  * (src/ace_inference/core/normalizer.py:96-110), Packer (src/utilities/packer.py:70-77), Prescriber
  * (src/ace_inference/core/prescriber.py:68-92), relative LpLoss (src/ace_inference/training/utils/darcy_loss.py:214-228).
- * Variables are separate dev tensors (B, T1, nlat*nlon) as in the reference's data dict. */
+ * Variables are separate dev tensors (B, T1, nlat*nlon) as in the reference's data dict.
+ * Alignment: these kernels move float4.  HW % 4 == 0, and EVERY device pointer of float data handed to sdy_norm_pack,
+ * sdy_init_timeline, sdy_step_finish and sdy_lp_rel_terms -- the per-variable data[] of a table, out, the per-entry timelines,
+ * gen, prev_in, next_in, ar_init, presc_target, presc_mask -- must be 16-byte aligned; otherwise SDY_ERR_ALIGN is returned
+ * before anything is launched and nothing is written.  (A freshly allocated tensor is aligned; a contiguous VIEW that starts
+ * at an odd element of a larger buffer is not: copy it first.) */
 #define SDY_MAX_VARS 96
 typedef struct sdy_var_table {
   int nvars;
@@ -549,7 +559,9 @@ size_t sdy_corrector_args_bytes(void);    /* sizeof(sdy_corrector_args) of the l
  * _add_or_initialize_time_mean): acc[p] += scale * sum over rows (r0, r1) and times t0 <= t < T of
  * x[r0*stride0 + r1*stride1 + t*HW + p].  x: dev, one variable of a window, (n0, n1, T, HW) with float strides for the
  * two leading axes (members, samples; a transposed view needs no copy); acc: dev (HW) running map.  scale = 1 / (n0 * n1 *
- * (T - t0)) gives the reference's mean over members, samples and time (t0 = 1 skips a window's initial condition). */
+ * (T - t0)) gives the reference's mean over members, samples and time (t0 = 1 skips a window's initial condition).
+ * HW and both strides multiples of 4, x and acc 16-byte aligned (float4 loads and stores), else SDY_ERR_ALIGN before anything
+ * is launched. */
 int sdy_time_mean_accumulate(const float* x, int n0, long stride0, int n1, long stride1, int t0, int T, int HW, float scale,
                              float* acc, void* stream);
 
@@ -731,7 +743,7 @@ int sdy_dropout_stream_words(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
                              uint32_t* out4);
 /* The forward-conditioning noise stream (above) written out: out dev (B, C, HW) receives eps of row b = trajectory
  * batch_offset + b % n, call + b / n (n = rows_per_call, 0 means B), channel c, pixel p -- what sdy_sfno_forward draws for a
- * generated group of C channels.  HW % 4 == 0. */
+ * generated group of C channels.  HW % 4 == 0 and out 16-byte aligned (float4 stores), else SDY_ERR_ALIGN. */
 int sdy_cond_noise_fill(uint64_t seed, uint32_t call, uint32_t batch_offset, int rows_per_call, int B, int C, int HW, float* out,
                         void* stream);
 

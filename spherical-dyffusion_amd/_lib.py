@@ -406,6 +406,13 @@ def ptr(t) -> int:
     return 0 if t is None else t.data_ptr()
 
 
+def aligned(t):
+    """`t`, or a copy of it when its first element is not on a 16-byte boundary (None stays None).  `.contiguous()` returns a
+    contiguous VIEW as it is, whatever its storage offset; the float4 kernels refuse such a pointer (SDY_ERR_ALIGN,
+    include/sdy_amd.h).  A fresh allocation is aligned; a copy keeps the order of the axes."""
+    return t if t is None or t.data_ptr() % 16 == 0 else t.clone()
+
+
 def current_stream() -> int:
     import torch
 

@@ -50,7 +50,7 @@ extern "C" const char* sdy_error_string(int code) {
     case SDY_OK: return "ok";
     case SDY_ERR_ARG: return "bad argument (null pointer or non-positive extent)";
     case SDY_ERR_UNSUPPORTED: return "unsupported size/configuration";
-    case SDY_ERR_ALIGN: return "extent along a contiguous dimension is not a multiple of 4";
+    case SDY_ERR_ALIGN: return "extent along a contiguous dimension is not a multiple of 4, or a pointer read as float4 is not 16-byte aligned";
     case SDY_ERR_WORKSPACE: return "workspace too small";
     case SDY_ERR_NAME: return "unknown parameter name";
     case SDY_ERR_SHAPE: return "parameter has the wrong number of elements";

@@ -8,6 +8,11 @@
 
 namespace {
 
+// The kernels of the stepper, the sampler glue and the time-mean map read and write float4: their launchers refuse (or, for the
+// cold update, fall back to 4-byte accesses on) a pointer that is not on a 16-byte boundary -- a contiguous tensor VIEW at an
+// odd storage offset is one -- before anything is enqueued.
+inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
 // ---- InstanceNorm statistics -> per-(b,c) affine coefficients ------------------------------------------
 // nn.InstanceNorm2d(eps=1e-6, affine=True, track_running_stats=False): biased variance over H*W per (b,c)
 // (src/models/sfno/sfnonet.py:641-648), folded with the block's time scale/shift (sfnonet.py:280-287).
@@ -324,8 +329,8 @@ __global__ __launch_bounds__(256) void cond_noise_kernel(float* __restrict__ out
 // ---- cold-sampling update: out = x_s + (x_ip_next - x_ip_s)   (src/diffusion/dyffusion.py:517-519) -------
 __global__ __launch_bounds__(256) void cold_update_kernel(const float* __restrict__ xs, const float* __restrict__ xn,
                                                            const float* __restrict__ xi, float* __restrict__ out,
-                                                           size_t n) {
-  const size_t n4 = n >> 2;
+                                                           size_t n, int vec) {
+  const size_t n4 = vec ? n >> 2 : 0;   // vec == 0 (a pointer off the 16-byte grid): the scalar loop takes the whole range
   const size_t stride = (size_t)gridDim.x * 256;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
     const f32x4 a = reinterpret_cast<const f32x4*>(xs)[i];
@@ -821,7 +826,7 @@ __global__ __launch_bounds__(256) void time_mean_kernel(const float* __restrict_
 extern "C" int sdy_time_mean_accumulate(const float* x, int n0, long stride0, int n1, long stride1, int t0, int T, int HW,
                                         float scale, float* acc, void* stream) {
   if (!x || !acc || n0 < 1 || n1 < 1 || T < 1 || t0 < 0 || t0 >= T || HW < 1) return SDY_ERR_ARG;
-  if ((HW & 3) || (stride0 & 3) || (stride1 & 3)) return SDY_ERR_ALIGN;
+  if ((HW & 3) || (stride0 & 3) || (stride1 & 3) || !al16(x) || !al16(acc)) return SDY_ERR_ALIGN;
   hipLaunchKernelGGL(time_mean_kernel, dim3((HW / 4 + 255) / 256), dim3(256), 0, (hipStream_t)stream, x, n0, stride0, n1,
                      stride1, t0, T, HW / 4, scale, acc);
   return sdy_launch_status();
@@ -868,9 +873,11 @@ extern "C" int sdy_ensemble_series_grad(const float* pred, int M, long member_st
 
 extern "C" int sdy_norm_pack(const sdy_var_table* vars, int t, int T1, int B, int HW, float* out, void* stream) {
   if (!vars || !out || vars->nvars < 1 || vars->nvars > SDY_MAX_VARS || t < 0 || t >= T1 || B <= 0 || HW <= 0) return SDY_ERR_ARG;
-  if (HW & 3) return SDY_ERR_ALIGN;
+  if ((HW & 3) || !al16(out)) return SDY_ERR_ALIGN;
   for (int i = 0; i < vars->nvars; ++i)
     if (!vars->data[i] || vars->std[i] == 0.0f) return SDY_ERR_ARG;
+  for (int i = 0; i < vars->nvars; ++i)
+    if (!al16(vars->data[i])) return SDY_ERR_ALIGN;
   hipLaunchKernelGGL(norm_pack_kernel, dim3((HW / 4 + 255) / 256, vars->nvars, B), dim3(256), 0, (hipStream_t)stream, *vars,
                      t, T1, HW / 4, out);
   return sdy_launch_status();
@@ -886,6 +893,8 @@ extern "C" int sdy_init_timeline(const sdy_var_table* vars, int T1, int B, int H
     tn.p[i] = tl_norm[i];
     td.p[i] = tl_denorm[i];
   }
+  for (int i = 0; i < vars->nvars; ++i)
+    if (!al16(tl_norm[i]) || !al16(tl_denorm[i]) || !al16(vars->data[i])) return SDY_ERR_ALIGN;
   hipLaunchKernelGGL(init_timeline_kernel, dim3((HW / 4 + 255) / 256, vars->nvars, B), dim3(256), 0, (hipStream_t)stream,
                      *vars, T1, HW / 4, tn, td);
   return sdy_launch_status();
@@ -904,6 +913,10 @@ extern "C" int sdy_step_finish(const sdy_step_finish_args* a, void* stream) {
   if (a->presc_entry >= 0 && (a->presc_entry >= a->n_entries || !a->presc_target || !a->presc_mask ||
                               a->out_idx[a->presc_entry] < 0))
     return SDY_ERR_ARG;
+  if (!al16(a->gen) || !al16(a->next_in) || !al16(a->prev_in) || !al16(a->ar_init)) return SDY_ERR_ALIGN;   // (NULL is aligned)
+  for (int e = 0; e < a->n_entries; ++e)
+    if (a->out_idx[e] >= 0 && (!al16(a->gen_norm_tl[e]) || !al16(a->gen_tl[e]))) return SDY_ERR_ALIGN;
+  if (a->presc_entry >= 0 && (!al16(a->presc_target) || !al16(a->presc_mask))) return SDY_ERR_ALIGN;
   hipLaunchKernelGGL(step_finish_kernel, dim3((a->HW / 4 + 255) / 256, a->n_entries, a->B), dim3(256), 0,
                      (hipStream_t)stream, *a);
   return sdy_launch_status();
@@ -911,9 +924,13 @@ extern "C" int sdy_step_finish(const sdy_step_finish_args* a, void* stream) {
 
 extern "C" int sdy_lp_rel_terms(const float* gen, const sdy_var_table* targets, int t, int T1, int B, int HW,
                                 double* terms, void* stream) {
-  if (!gen || !targets || !terms || targets->nvars < 1 || targets->nvars > SDY_MAX_VARS || t < 0 || t >= T1 || B <= 0)
+  if (!gen || !targets || !terms || targets->nvars < 1 || targets->nvars > SDY_MAX_VARS || t < 0 || t >= T1 || B <= 0 || HW <= 0)
     return SDY_ERR_ARG;
-  if (HW & 3) return SDY_ERR_ALIGN;
+  if ((HW & 3) || !al16(gen)) return SDY_ERR_ALIGN;
+  for (int i = 0; i < targets->nvars; ++i)
+    if (!targets->data[i] || targets->std[i] == 0.0f) return SDY_ERR_ARG;
+  for (int i = 0; i < targets->nvars; ++i)
+    if (!al16(targets->data[i])) return SDY_ERR_ALIGN;
   int gx = (HW / 4 + 255) / 256;
   if (gx > 16) gx = 16;
   hipLaunchKernelGGL(lp_terms_kernel, dim3(gx, targets->nvars, B), dim3(256), 0, (hipStream_t)stream, gen, *targets, t, T1,
@@ -1071,7 +1088,7 @@ int sdy_affine_copy_stats_launch(const float* x, long x_bs, const float* a, cons
 int sdy_concat_launch(const float* const* src, const int* chans, int nsrc, float* out, long out_bstride, int B, int HW,
                       hipStream_t stream, int src_rows) {
   if (!src || !chans || !out || nsrc < 1 || nsrc > 4 || B <= 0 || HW <= 0) return SDY_ERR_ARG;
-  if (HW & 3) return SDY_ERR_ALIGN;
+  if ((HW & 3) || (out_bstride & 3) || !al16(out)) return SDY_ERR_ALIGN;
   ConcatArgs a;
   int total = 0;
   for (int i = 0; i < 4; ++i) {
@@ -1082,6 +1099,8 @@ int sdy_concat_launch(const float* const* src, const int* chans, int nsrc, float
       total += chans[i];
     }
   }
+  for (int i = 0; i < nsrc; ++i)
+    if (!al16(src[i])) return SDY_ERR_ALIGN;
   a.nsrc = nsrc;
   const int HW4 = HW / 4;
   hipLaunchKernelGGL(concat_kernel, dim3((HW4 + 255) / 256, total, B), dim3(256), 0, stream, a, out, out_bstride, HW4, src_rows);
@@ -1092,7 +1111,7 @@ int sdy_concat_gen_launch(const float* const* src, const int* chans, int nsrc, c
                           long out_bstride, int B, int HW, hipStream_t stream) {
   if (!src || !chans || !out || nsrc < 1 || nsrc > 4 || B <= 0 || HW <= 0) return SDY_ERR_ARG;
   if (gen.gen < 0 || gen.gen >= nsrc || !gen.coef || gen.rows_per_call <= 0 || B % gen.rows_per_call) return SDY_ERR_ARG;
-  if (HW & 3) return SDY_ERR_ALIGN;
+  if ((HW & 3) || (out_bstride & 3) || !al16(out) || !al16(gen.noise)) return SDY_ERR_ALIGN;
   ConcatGenArgs g;
   int total = 0;
   for (int i = 0; i < 4; ++i) {
@@ -1103,6 +1122,8 @@ int sdy_concat_gen_launch(const float* const* src, const int* chans, int nsrc, c
       total += chans[i];
     }
   }
+  for (int i = 0; i < nsrc; ++i)
+    if (!al16(src[i])) return SDY_ERR_ALIGN;
   if ((long)gen.batch_offset + gen.rows_per_call > 0xFFFFFFFFL / chans[gen.gen])
     return SDY_ERR_ARG;   // counter word c1 = trajectory * C + c must not wrap
   g.cat.nsrc = nsrc;
@@ -1117,7 +1138,7 @@ int sdy_concat_gen_launch(const float* const* src, const int* chans, int nsrc, c
 int sdy_cond_noise_launch(uint64_t seed, uint32_t call, uint32_t batch_offset, int rows_per_call, int B, int C, int HW, float* out,
                           hipStream_t stream) {
   if (!out || B <= 0 || C <= 0 || HW <= 0 || rows_per_call < 0 || (rows_per_call > 0 && B % rows_per_call)) return SDY_ERR_ARG;
-  if (HW & 3) return SDY_ERR_ALIGN;
+  if ((HW & 3) || !al16(out)) return SDY_ERR_ALIGN;
   const int rpc = rows_per_call > 0 ? rows_per_call : B;
   if ((long)batch_offset + rpc > 0xFFFFFFFFL / C) return SDY_ERR_ARG;
   if (C > 65535 || B > 65535) return SDY_ERR_ARG;   // grid y / z extents
@@ -1130,10 +1151,11 @@ int sdy_cond_noise_launch(uint64_t seed, uint32_t call, uint32_t batch_offset, i
 int sdy_cold_update_launch(const float* xs, const float* xn, const float* xi, float* out, size_t n,
                            hipStream_t stream) {
   if (!xs || !xn || !out || n == 0) return SDY_ERR_ARG;
-  size_t blocks = ((n >> 2) + 255) / 256;
+  const int vec = al16(xs) && al16(xn) && al16(xi) && al16(out);
+  size_t blocks = ((vec ? n >> 2 : n) + 255) / 256;
   if (blocks < 1) blocks = 1;
   if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(cold_update_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, xs, xn, xi, out, n);
+  hipLaunchKernelGGL(cold_update_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, xs, xn, xi, out, n, vec);
   return sdy_launch_status();
 }
 

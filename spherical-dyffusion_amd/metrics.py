@@ -15,7 +15,7 @@ from typing import Dict, List, Mapping, Optional, Sequence
 import numpy as np
 import torch
 
-from ._lib import SDY_MAX_VARS, SdyVideoArgs, SdyZonalArgs, check, current_stream, lib, ptr
+from ._lib import SDY_MAX_VARS, SdyVideoArgs, SdyZonalArgs, aligned, check, current_stream, lib, ptr
 from .histogram import _strided_layout
 
 
@@ -155,6 +155,7 @@ class TimeMeanAggregator:
                 (n1, T, H, W), n0 = v.shape, 1
             if v.stride(-1) != 1 or v.stride(-2) != W or v.stride(-3) != H * W:
                 v = v.contiguous()
+            v = aligned(v)                                  # float4 loads (sdy_time_mean_accumulate)
             s0, s1 = (v.stride(0), v.stride(1)) if v.dim() == 5 else (0, v.stride(0))
             if name not in maps:
                 maps[name] = torch.zeros(H, W, dtype=torch.float32, device=v.device)

@@ -11,13 +11,13 @@ from typing import Optional
 
 import torch
 
-from ._lib import SdyConvArgs, SdyMlpArgs, SdyPairArgs, check, current_stream, lib, ptr
+from ._lib import SdyConvArgs, SdyMlpArgs, SdyPairArgs, aligned, check, current_stream, lib, ptr
 
 
 def _f32c(t: torch.Tensor) -> torch.Tensor:
     if not t.is_cuda:
         raise RuntimeError("sdy_amd ops run on the GPU only (no CPU fallback)")
-    return t.to(torch.float32).contiguous()
+    return aligned(t.to(torch.float32).contiguous())     # the kernels read float4: no view at an odd storage offset
 
 
 def _aux(t: torch.Tensor, dev) -> torch.Tensor:

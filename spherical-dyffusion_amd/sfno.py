@@ -17,7 +17,7 @@ import torch
 from torch import nn
 
 from . import _lib
-from ._lib import SdySfnoConfig, SdySfnoFwdArgs, check, current_stream, lib, ptr
+from ._lib import SdySfnoConfig, SdySfnoFwdArgs, aligned, check, current_stream, lib, ptr
 
 
 class SphericalFourierNeuralOperatorNet(nn.Module):
@@ -365,7 +365,7 @@ class SphericalFourierNeuralOperatorNet(nn.Module):
         else:
             assert condition is None and gen is None, "condition is not None but num_conditional_channels is 0"
             assert static_condition is None, "static_condition is not None but num_conditional_channels is 0"
-        pieces = [t.to(torch.float32).contiguous() for t in (inputs, condition, static_condition) if t is not None]
+        pieces = [aligned(t.to(torch.float32).contiguous()) for t in (inputs, condition, static_condition) if t is not None]
         B = B_in = inputs.shape[0]
         if shared_inputs:
             assert rows_per_call == B_in and self.with_time_emb and torch.is_tensor(time) and time.numel() % B_in == 0 \
@@ -427,7 +427,7 @@ class SphericalFourierNeuralOperatorNet(nn.Module):
             assert n_calls == 1, "injected noise addresses one call per forward"
             eps = self.noise_injector(self._call)
             if eps is not None:
-                eps = eps.to(dev, torch.float32).contiguous()
+                eps = aligned(eps.to(dev, torch.float32).contiguous())
                 assert eps.shape == gen[0].shape, f"injected noise {tuple(eps.shape)} != {tuple(gen[0].shape)}"
             gen = (gen[0], gen[1], eps)
         self._native_call(h, dev, pieces, tt, out, self._call, self.batch_offset, rows_per_call, keep_masks, drop_path_keep,
@@ -438,7 +438,7 @@ class SphericalFourierNeuralOperatorNet(nn.Module):
     def _forward_condition(self, fc, B: int, dev):
         """(x0, a, s) -> (x0 as fp32 contiguous, coef (B, 2) on the device, no injected noise)."""
         x0, a, s = fc
-        x0 = x0.to(torch.float32).contiguous()
+        x0 = aligned(x0.to(torch.float32).contiguous())     # the input concat copies float4
         nlat, nlon = self.img_shape
         assert x0.shape[0] == B and tuple(x0.shape[-2:]) == (nlat, nlon), f"bad forward_condition shape {tuple(x0.shape)}"
 

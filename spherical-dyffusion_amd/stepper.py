@@ -23,7 +23,7 @@ from typing import Dict, List, Optional
 
 import torch
 
-from ._lib import SDY_MAX_VARS, SdyStepFinishArgs, SdyVarTable, check, current_stream, lib, ptr
+from ._lib import SDY_MAX_VARS, SdyStepFinishArgs, SdyVarTable, aligned, check, current_stream, lib, ptr
 
 
 @dataclass
@@ -158,7 +158,7 @@ class MultiStepStepper:
             raise RuntimeError("sdy_amd stepper runs on the GPU only (no CPU fallback); move the window to cuda")
         dev = any_t.device
         HW = H * W
-        data = {k: v.to(dev, torch.float32).contiguous() for k, v in data.items()}
+        data = {k: aligned(v.to(dev, torch.float32).contiguous()) for k, v in data.items()}   # (the kernels read float4)
         mod = self.module
         horizon = mod.true_horizon
         hack = bool(getattr(getattr(mod.model, "hparams", None), "hack_for_imprecise_interpolation", False))
@@ -215,10 +215,10 @@ class MultiStepStepper:
                     res = mod.get_preds_at_t_for_batch(batch, horizon=h, split="predict", ensemble=False,
                                                        is_autoregressive=th > horizon, prepare_inputs=False,
                                                        num_predictions=1)
-                g = res[f"t{h}_preds_normed"].contiguous()
+                g = aligned(res[f"t{h}_preds_normed"].contiguous())
                 ar = None
                 if "preds_autoregressive_init_normed" in res:   # the state handed to the next window differs from the
-                    ar = res["preds_autoregressive_init_normed"].contiguous()   # prediction (stepper_multistep.py:412-418)
+                    ar = aligned(res["preds_autoregressive_init_normed"].contiguous())   # prediction (:412-418)
                 if self._correct is not None:       # in a copy, in the normalised space, against the state stepped from
                     g = g.clone()
                     self._correct(state, g, corr_ws)
