@@ -16,7 +16,7 @@
  *
  * Internal spectral layouts (fp32):
  *   grid-frequency  Xf[m][k][b][ri][c]   m < mtr = min(mmax, lmax), k < nlat, ri in {re, im}
- *   coefficients    Cs[l][m][b][ri][c]   l < lmax, m < mtr; entries with m > l are never read or written
+ *   coefficients    Cs[l][m][b][ri][c]   l < lmax, m < mtr; entries with m > l are never read (sdy_legendre_fwd zeroes them)
  * (These are the layouts of the stage-level entry points below.  sdy_sfno_forward keeps its own spectral workspace in a
  *  private variant: the 2C axis ordered [c/16][ri][16], and (order, latitude) pairs whose Legendre table entries are below
  *  1e-12 of the order's maximum omitted altogether -- DESIGN.md section 3.)
@@ -96,6 +96,10 @@ int sdy_sht_plan_create_ex(int nlat, int nlon, int lmax, int mmax, int grid, int
 void sdy_sht_plan_destroy(sdy_sht_plan* plan);
 /* dims[0..5] = nlat, nlon, lmax, mmax, mtr, grid */
 int sdy_sht_plan_dims(const sdy_sht_plan* plan, int dims[6]);
+/* Which kernels the plan resolved to (read-only): out[0] = Legendre back end of both directions -- 0 folded fragment stream
+ * (leg_par.hip), 1 fragment stream (leg_h3.hip), 2 split-fp16 batched GEMM (gemm_h3.hip), 3 fp32 batched GEMM (gemm.hip);
+ * out[1] = 1 when the longitude FFTs of C % 16 == 0 fields run in the 360-point kernels of fft360.hip, else 0. */
+int sdy_sht_plan_kernels(const sdy_sht_plan* plan, int out[2]);
 /* floats needed by sdy_sht_forward / sdy_sht_inverse for B*C fields */
 size_t sdy_sht_workspace_floats(const sdy_sht_plan* plan, int B, int C);
 
@@ -110,14 +114,17 @@ int sdy_sht_inverse(const sdy_sht_plan* plan, const float* in_c64, float* y, int
 
 /* Stage-level entry points on the internal layouts (what the fused network path launches). */
 /* longitude real FFT x (2*pi/nlon) fused with the per-(b,c) affine a*x+d of InstanceNorm + time scale/shift
- * (src/models/sfno/sfnonet.py:292,298-299).  a, d: dev [B*C] or NULL.  xn_out: dev (B,C,nlat,nlon) or NULL. */
+ * (src/models/sfno/sfnonet.py:292,298-299).  a, d: dev [B*C], both or neither (else SDY_ERR_ARG).  xn_out: dev
+ * (B,C,nlat,nlon) or NULL.  Xf: dev [mtr][nlat][B][2][C].  The kernels move four channels at a time as 16-byte words:
+ * C % 4 == 0 and x, xn_out, Xf 16-byte aligned, else SDY_ERR_ALIGN before anything is launched. */
 int sdy_rfft_lon(const sdy_sht_plan* plan, const float* x, const float* a, const float* d, float* xn_out,
                  float* Xf, int B, int C, void* stream);
-/* Legendre analysis: Cs[l][m][n] = sum_k Wq[m][l][k] Xf[m][k][n]  (einsum '...km,mlk->...lm') */
+/* Legendre analysis: Cs[l][m][n] = sum_k Wq[m][l][k] Xf[m][k][n]  (einsum '...km,mlk->...lm'); exact zeros where m > l */
 int sdy_legendre_fwd(const sdy_sht_plan* plan, const float* Xf, float* Cs, int B, int C, void* stream);
 /* Legendre synthesis: Yf[m][k][n] = sum_l P[m][l][k] Cs[l][m][n]  (einsum '...lm,mlk->...km') */
 int sdy_legendre_inv(const sdy_sht_plan* plan, const float* Cs, float* Yf, int B, int C, void* stream);
-/* inverse longitude FFT (irfft n=nlon, norm="forward") + optional per-channel bias (s2convolutions.py:188-189) */
+/* inverse longitude FFT (irfft n=nlon, norm="forward") + optional per-channel bias (s2convolutions.py:188-189).
+ * C % 4 == 0 and Yf, y 16-byte aligned, else SDY_ERR_ALIGN before anything is launched (see sdy_rfft_lon). */
 int sdy_irfft_lon(const sdy_sht_plan* plan, const float* Yf, const float* bias, float* y, int B, int C,
                   void* stream);
 

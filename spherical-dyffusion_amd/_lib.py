@@ -236,6 +236,7 @@ SIGNATURES = {
     "sdy_sht_plan_create_ex": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "sdy_sht_plan_destroy": (None, [C.c_void_p]),
     "sdy_sht_plan_dims": (C.c_int, [C.c_void_p, C.POINTER(C.c_int * 6)]),
+    "sdy_sht_plan_kernels": (C.c_int, [C.c_void_p, C.POINTER(C.c_int * 2)]),
     "sdy_sht_workspace_floats": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
     "sdy_sht_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "sdy_sht_inverse": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),

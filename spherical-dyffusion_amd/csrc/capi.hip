@@ -277,6 +277,13 @@ extern "C" int sdy_sht_plan_dims(const sdy_sht_plan* p, int dims[6]) {
   return SDY_OK;
 }
 
+extern "C" int sdy_sht_plan_kernels(const sdy_sht_plan* p, int out[2]) {
+  if (!p || !out) return SDY_ERR_ARG;
+  out[0] = (int)p->leg;
+  out[1] = (p->fft.fft360 && p->fft.n == 180) ? 1 : 0;
+  return SDY_OK;
+}
+
 static inline size_t xf_floats(const sdy_sht_plan* p, int B, int C) { return (size_t)p->mtr * p->nlat * B * 2 * C; }
 static inline size_t cs_floats(const sdy_sht_plan* p, int B, int C) { return (size_t)p->lmax * p->mtr * B * 2 * C; }
 
@@ -285,16 +292,21 @@ extern "C" size_t sdy_sht_workspace_floats(const sdy_sht_plan* p, int B, int C) 
   return round_up_sz(xf_floats(p, B, C), 64) + round_up_sz(cs_floats(p, B, C), 64);
 }
 
+static inline bool fft_aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }   // NULL passes
+
 extern "C" int sdy_rfft_lon(const sdy_sht_plan* p, const float* x, const float* a, const float* d, float* xn_out,
                             float* Xf, int B, int C, void* stream) {
   if (!p || !x || !Xf || B <= 0 || C <= 0) return SDY_ERR_ARG;
   if ((a == nullptr) != (d == nullptr)) return SDY_ERR_ARG;
+  // the kernels move runs of four channels of Xf, and rows of x / xn_out, as 16-byte words
+  if (C % 4 != 0 || !fft_aligned16(x) || !fft_aligned16(xn_out) || !fft_aligned16(Xf)) return SDY_ERR_ALIGN;
   return sdy_fft_launch_fwd(p->fft, x, a, d, xn_out, Xf, B, C, p->nlat, p->mtr, 0, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int sdy_irfft_lon(const sdy_sht_plan* p, const float* Yf, const float* bias, float* y, int B, int C,
                              void* stream) {
   if (!p || !Yf || !y || B <= 0 || C <= 0) return SDY_ERR_ARG;
+  if (C % 4 != 0 || !fft_aligned16(Yf) || !fft_aligned16(y)) return SDY_ERR_ALIGN;
   return sdy_fft_launch_inv(p->fft, Yf, bias, y, B, C, p->nlat, p->mtr, 0, nullptr, (hipStream_t)stream);
 }
 
@@ -331,7 +343,12 @@ static int legendre_fwd_impl(const sdy_sht_plan* p, const float* Xf, float* Cs, 
                               (long)p->mtr * p->h3_rows_fwd * p->h3_k_fwd, p->s_wq, 0, (hipStream_t)stream);
   return sdy_gemm_launch(g, (hipStream_t)stream);
 }
+// The stand-alone stage defines the whole of Cs: the back ends never store a coefficient with m > l (nothing downstream reads
+// one), so those are zeroed here first.  The fused network and sdy_sht_forward go through legendre_fwd_impl and skip this.
 extern "C" int sdy_legendre_fwd(const sdy_sht_plan* p, const float* Xf, float* Cs, int B, int C, void* stream) {
+  if (!p || !Xf || !Cs || B <= 0 || C <= 0) return SDY_ERR_ARG;
+  if (C & 1) return SDY_ERR_ALIGN;
+  SDY_TRY(sdy_spec_zero_upper_launch(Cs, p->lmax, p->mtr, 2 * B * C, (hipStream_t)stream));
   return legendre_fwd_impl(p, Xf, Cs, B, C, false, stream, false, false);
 }
 
@@ -371,7 +388,7 @@ extern "C" int sdy_sht_forward(const sdy_sht_plan* p, const float* x, float* out
   float* Xf = ws;
   float* Cs = ws + round_up_sz(xf_floats(p, B, C), 64);
   SDY_TRY(sdy_rfft_lon(p, x, nullptr, nullptr, nullptr, Xf, B, C, stream));
-  SDY_TRY(sdy_legendre_fwd(p, Xf, Cs, B, C, stream));
+  SDY_TRY(legendre_fwd_impl(p, Xf, Cs, B, C, false, stream, false, false));   // spec_to_torch zeroes m > l itself
   return sdy_spec_to_torch_launch(Cs, out_c64, B, C, p->lmax, p->mtr, p->mmax, (hipStream_t)stream);
 }
 

@@ -44,6 +44,8 @@ int sdy_time_mlp_launch(const SdyTimeMlp& t, const float* time, int B, float* tr
                         const float* dp_keep_in, int enable_dropout, uint64_t seed, uint32_t call,
                         uint32_t batch_offset, int rows_per_call, hipStream_t stream, float* scratch);
 int sdy_spec_to_torch_launch(const float* Cs, float* out, int B, int C, int L, int mtr, int Mfull, hipStream_t stream);
+// Cs[l][m][n] = 0 for m > l (l < L, m < mtr, n < N)
+int sdy_spec_zero_upper_launch(float* Cs, int L, int mtr, int N, hipStream_t stream);
 int sdy_torch_to_spec_launch(const float* in, float* Cs, int B, int C, int L, int mtr, int Mfull, hipStream_t stream);
 // InstanceNorm coefficients (no time scale / shift) from per-ring partial statistics part[b][k][c][2] (fft360.hip's act epilogue)
 int sdy_instnorm_from_partials_launch(const double* part, int K, int B, int C, int HW, const float* gamma, const float* beta,

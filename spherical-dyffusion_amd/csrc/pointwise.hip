@@ -530,6 +530,15 @@ __global__ __launch_bounds__(256) void torch_to_spec_kernel(const float* __restr
   }
 }
 
+// Cs[l][m][n], n < N: zero where m > l.  For degree l these are the (mtr - 1 - l) * N contiguous floats after order l; the
+// Legendre analysis kernels never store them (the stand-alone sdy_legendre_fwd defines them, the fused path does not).
+__global__ __launch_bounds__(256) void spec_zero_upper_kernel(float* __restrict__ Cs, int mtr, int N) {
+  const int l = blockIdx.x;   // l < mtr - 1
+  float* run = Cs + ((long)l * mtr + l + 1) * N;
+  const long len = (long)(mtr - 1 - l) * N;
+  for (long i = (long)blockIdx.y * 256 + threadIdx.x; i < len; i += (long)gridDim.y * 256) run[i] = 0.0f;
+}
+
 // ---- stepper glue (src/ace_inference/core/stepper_multistep.py:298-466) -----------------------------------------
 __global__ __launch_bounds__(256) void norm_pack_kernel(const sdy_var_table v, int t, int T1, int HW4,
                                                          float* __restrict__ out) {
@@ -1187,6 +1196,12 @@ int sdy_time_mlp_launch(const SdyTimeMlp& t, const float* time, int B, float* tr
 
 int sdy_spec_to_torch_launch(const float* Cs, float* out, int B, int C, int L, int mtr, int Mfull, hipStream_t stream) {
   hipLaunchKernelGGL(spec_to_torch_kernel, dim3(1024), dim3(256), 0, stream, Cs, out, B, C, L, mtr, Mfull);
+  return sdy_launch_status();
+}
+int sdy_spec_zero_upper_launch(float* Cs, int L, int mtr, int N, hipStream_t stream) {
+  const int rows = L < mtr - 1 ? L : mtr - 1;   // degrees that have an order above them
+  if (rows <= 0) return SDY_OK;
+  hipLaunchKernelGGL(spec_zero_upper_kernel, dim3(rows, 8), dim3(256), 0, stream, Cs, mtr, N);
   return sdy_launch_status();
 }
 int sdy_torch_to_spec_launch(const float* in, float* Cs, int B, int C, int L, int mtr, int Mfull, hipStream_t stream) {

@@ -83,7 +83,7 @@ class RealSHT(_ShtBase):
         self._require_gpu(x)
         assert x.shape[-2] == self.nlat and x.shape[-1] == self.nlon, f"bad grid {tuple(x.shape[-2:])}"
         lead = x.shape[:-2]
-        xf = x.reshape(-1, self.nlat, self.nlon).to(torch.float32).contiguous()
+        xf = _lib.aligned(x.reshape(-1, self.nlat, self.nlon).to(torch.float32).contiguous())   # float4 loads (SDY_ERR_ALIGN)
         n = xf.shape[0]
         pad = (-n) % 4  # channel count seen by the kernels must be a multiple of 4
         if pad:

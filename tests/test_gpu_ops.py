@@ -492,7 +492,7 @@ def test_conv_cin_to_256_persistent_kernel(sdy, Cin):
     (180, 360, 180, 181, 16, 2),    # nlon = 360 FFT specialisation (C % 16 == 0) + folded Legendre kernel
     (180, 360, 120, 100, 32, 1),    # truncated lmax / mmax
     (90, 360, 90, 181, 16, 1),      # fewer rings, mmax > lmax
-    (33, 64, 33, 33, 4, 2),         # odd nlat: the unfolded Legendre kernel, generic FFT
+    (33, 64, 33, 33, 4, 2),         # odd nlat: the unfolded Legendre kernel; the compile-time <32,4> FFT (nlon = 64)
     (32, 64, 20, 17, 12, 2),        # truncated small grid
 ])
 def test_sht_shapes_both_directions(sdy, nlat, nlon, L, M, C, B, grid):

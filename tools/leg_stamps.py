@@ -21,6 +21,7 @@ names = ["issue loads", "loads arrive", "split + barrier", "MFMA", "stores issue
 for fwd in (1, 0):
     for _ in range(3):
         if fwd:
+            # (the stand-alone entry zeroes m > l first; the stamps are taken inside the Legendre kernel only)
             check(lib.sdy_legendre_fwd(plan.handle, ptr(Xf), ptr(Cs), B, E, current_stream()))
         else:
             check(lib.sdy_legendre_inv(plan.handle, ptr(Cs), ptr(Xf), B, E, current_stream()))

@@ -41,6 +41,7 @@ bench("instnorm_coeffs", lambda: check(lib.sdy_instnorm_coeffs(ptr(x), B, E, H*W
 a = torch.rand(B, E, device=dev) + 0.5
 bench("rfft (affine, store xn)", lambda: check(lib.sdy_rfft_lon(plan.handle, ptr(x), ptr(a), ptr(d), ptr(xn), ptr(Xf), B, E, st())), 3 * T)
 bench("rfft (no xn store)", lambda: check(lib.sdy_rfft_lon(plan.handle, ptr(x), ptr(a), ptr(d), None, ptr(Xf), B, E, st())), 2 * T)
+# (the stand-alone entry also zeroes the m > l coefficients first, a small launch the fused network does not make)
 bench("legendre_fwd", lambda: check(lib.sdy_legendre_fwd(plan.handle, ptr(Xf), ptr(Cs), B, E, st())), 1.5 * T, 3.0e9 * B)
 bench("dhconv", lambda: check(lib.sdy_dhconv(ptr(Cs), ptr(wp), ptr(Cs2), L, mtr, B, E, E, st())), T + 94.4e6, 8.54e9 * B)
 wf = torch.empty(lib.sdy_dhconv_frag_pack_bytes(L), dtype=torch.uint8, device=dev)
