@@ -562,6 +562,55 @@ int sdy_corrector_host(const sdy_corrector_args* args);
 size_t sdy_corrector_workspace_bytes(int B, int HW);
 size_t sdy_corrector_args_bytes(void);    /* sizeof(sdy_corrector_args) of the library (the bindings compare their layout) */
 
+/* Dry-air conservation diagnostics (compute_dry_air_absolute_differences, src/ace_inference/core/aggregator/climate_data.py:
+ * 199-233; get_dry_air_nonconservation / ConservationLoss, core/loss.py; DryAir, core/aggregator/one_step/derived.py).  For B
+ * samples and T times, with dry = ps - g*twp per column as above (the fp32 chain of csrc/corrector_math.h):
+ *   gm[b][t]      = sum_p area[p]*dry(b,t,p) / sum_p area[p]                 (metrics.weighted_mean over the grid)
+ *   absdiff[t]    = (1/B) * sum_b |gm[b][t+1] - gm[b][t]|,  t = 0 .. T-2      (.diff(dim=-1).abs().mean(dim=0))
+ *   mean_absdiff  = (1/(T-1)) * sum_t absdiff[t]                             (.mean()); with B equal rows per time this is also
+ *                                                                              DryAir's mean over samples and times at once
+ * all float64.  Two launches whatever B, T and K: a reduce pass that reads the K water levels, the pressure and the weights
+ * once and writes one float64 partial pair per (sample, time, 1024-column chunk) to the workspace, and one small block that
+ * adds the partials in chunk order, the samples in sample order and the times in time order.  No atomics: gm[b][t] depends
+ * neither on B, nor on the row's place in the batch, nor on the run, and the host twin (same arithmetic, same tree inside a
+ * chunk, same orders) gives the same bits.
+ *   variable: element (b, t, p) at base + b*stride_b + t*stride_t + channel*HW + p, physical value x*std + mean: (B, T, H, W)
+ *             dict tensors, their [:, 0:2] views and the stepper's packed (B, C, H, W) tensors (T = 1, channel = the index) all
+ *             pass without a copy.
+ *   area:     dev float (HW).   ak, bk: K + 1 values.
+ *   gm:       dev double (B*T), always written.   absdiff: dev double (T-1).   mean_absdiff: dev double (1); with
+ *             accumulate != 0 the value is ADDED to what is there (a running total over batches, in stream order).  With
+ *             T = 1 neither absdiff nor mean_absdiff is touched (both may be NULL).
+ *   ws:       dev, 8-byte aligned, at least sdy_dry_air_workspace_bytes(B, T, HW); scratch only.
+ * SDY_ERR_ARG, before anything is launched: NULL args / area / gm / ws, with T > 1 a NULL absdiff / mean_absdiff, a NULL base
+ * of ps or of one of the K levels, B, T or HW < 1, HW not a multiple of 4, K outside 1..SDY_DERIVED_MAX_LEVELS, a negative
+ * channel, a negative stride or one that is not a multiple of 4, a plane address (or area) not 16-byte aligned, an output not
+ * 8-byte aligned, std not finite and > 0, mean not finite, ws misaligned or ws_bytes too small.  SDY_ERR_UNSUPPORTED: B*T >
+ * 65535.  The host twin computes the same on host memory (ws may be NULL). */
+typedef struct sdy_dry_air_var {
+  const float* base;
+  long stride_b, stride_t;
+  int channel;
+  float mean, std;
+} sdy_dry_air_var;
+typedef struct sdy_dry_air_args {
+  int B, T, HW, K;
+  int accumulate;
+  float ak[SDY_DERIVED_MAX_LEVELS + 1], bk[SDY_DERIVED_MAX_LEVELS + 1];
+  const float* area;
+  sdy_dry_air_var q[SDY_DERIVED_MAX_LEVELS];
+  sdy_dry_air_var ps;
+  double* gm;
+  double* absdiff;
+  double* mean_absdiff;
+  void* ws;
+  size_t ws_bytes;
+} sdy_dry_air_args;
+int sdy_dry_air_series(const sdy_dry_air_args* args, void* stream);
+int sdy_dry_air_series_host(const sdy_dry_air_args* args);
+size_t sdy_dry_air_workspace_bytes(int B, int T, int HW);
+size_t sdy_dry_air_args_bytes(void);      /* sizeof(sdy_dry_air_args) of the library (the bindings compare their layout) */
+
 /* Time-mean accumulation of the inference aggregator (src/ace_inference/core/aggregator/inference/time_mean.py:97-117,
  * _add_or_initialize_time_mean): acc[p] += scale * sum over rows (r0, r1) and times t0 <= t < T of
  * x[r0*stride0 + r1*stride1 + t*HW + p].  x: dev, one variable of a window, (n0, n1, T, HW) with float strides for the

@@ -181,6 +181,22 @@ class SdyCorrectorArgs(C.Structure):
     ]
 
 
+class SdyDryAirVar(C.Structure):
+    _fields_ = [("base", C.c_void_p), ("stride_b", C.c_long), ("stride_t", C.c_long), ("channel", C.c_int),
+                ("mean", C.c_float), ("std", C.c_float)]
+
+
+class SdyDryAirArgs(C.Structure):
+    _fields_ = [
+        ("B", C.c_int), ("T", C.c_int), ("HW", C.c_int), ("K", C.c_int), ("accumulate", C.c_int),
+        ("ak", C.c_float * (SDY_DERIVED_MAX_LEVELS + 1)), ("bk", C.c_float * (SDY_DERIVED_MAX_LEVELS + 1)),
+        ("area", C.c_void_p),
+        ("q", SdyDryAirVar * SDY_DERIVED_MAX_LEVELS), ("ps", SdyDryAirVar),
+        ("gm", C.c_void_p), ("absdiff", C.c_void_p), ("mean_absdiff", C.c_void_p),
+        ("ws", C.c_void_p), ("ws_bytes", C.c_size_t),
+    ]
+
+
 SDY_HIST_MAX_BINS = 2048
 SDY_HIST_FLAG_RANGE = 1
 
@@ -316,6 +332,10 @@ SIGNATURES = {
     "sdy_corrector_host": (C.c_int, [C.POINTER(SdyCorrectorArgs)]),
     "sdy_corrector_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "sdy_corrector_args_bytes": (C.c_size_t, []),
+    "sdy_dry_air_series": (C.c_int, [C.POINTER(SdyDryAirArgs), C.c_void_p]),
+    "sdy_dry_air_series_host": (C.c_int, [C.POINTER(SdyDryAirArgs)]),
+    "sdy_dry_air_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "sdy_dry_air_args_bytes": (C.c_size_t, []),
     "sdy_hist_add": (C.c_int, [C.POINTER(SdyHistArgs), C.c_void_p]),
     "sdy_hist_args_bytes": (C.c_size_t, []),
     "sdy_hist_state_bytes": (C.c_size_t, [C.c_int]),
@@ -377,6 +397,7 @@ def _load():
         raise ImportError(f"{LIB_PATH}: sdy_coarsen_args of the bindings ({C.sizeof(SdyCoarsenArgs)} bytes) and of the library "
                           f"({lib.sdy_coarsen_args_bytes()}) differ: rebuild the library (make -C spherical-dyffusion_amd/csrc)")
     for what, theirs, ours in (("sdy_corrector_args", lib.sdy_corrector_args_bytes(), C.sizeof(SdyCorrectorArgs)),
+                               ("sdy_dry_air_args", lib.sdy_dry_air_args_bytes(), C.sizeof(SdyDryAirArgs)),
                                ("sdy_video_args", lib.sdy_video_args_bytes(), C.sizeof(SdyVideoArgs)),
                                ("sdy_zonal_args", lib.sdy_zonal_args_bytes(), C.sizeof(SdyZonalArgs))):
         if theirs != ours:

@@ -45,8 +45,13 @@ class WindowMetrics(Mapping):
     copy's event on first access, then raises if a kernel of the window flagged an fp16-range overflow / non-finite
     statistics (include/sdy_amd.h, `sdy_status_flags`)."""
 
-    def __init__(self, terms_host: torch.Tensor, flags_host: Optional[torch.Tensor], event, where: str):
+    def __init__(self, terms_host: torch.Tensor, flags_host: Optional[torch.Tensor], event, where: str,
+                 dry_air_host: Optional[torch.Tensor] = None, dry_air_penalty: Optional[float] = None):
+        """`dry_air_host` (one float64 element behind the terms in the same pinned buffer) and `dry_air_penalty`: the window's
+        mean dry-air non-conservation; the mapping then has `dry_air_loss` = penalty * that, and `loss` includes it
+        (`src/ace_inference/core/stepper.py:570-574`; a NaN there makes `loss` NaN, as the reference's `loss +=` does)."""
         self._terms, self._flags, self._event, self._where = terms_host, flags_host, event, where
+        self._dry_air, self._penalty = dry_air_host, dry_air_penalty
         self._values: Optional[Dict[str, torch.Tensor]] = None
 
     def ready(self) -> bool:
@@ -66,7 +71,12 @@ class WindowMetrics(Mapping):
             terms = self._terms
             per_step = (terms[..., 0].sqrt() / terms[..., 1].sqrt()).mean(dim=1)
             vals = {f"loss_step_{i}": per_step[i].to(torch.float32) for i in range(per_step.shape[0])}
-            vals["loss"] = per_step.sum().to(torch.float32)
+            loss = per_step.sum()
+            if self._dry_air is not None:
+                dry_air_loss = self._penalty * self._dry_air.reshape(())
+                vals["dry_air_loss"] = dry_air_loss.to(torch.float32)
+                loss = loss + dry_air_loss
+            vals["loss"] = loss.to(torch.float32)
             self._values = vals
         return self._values
 
@@ -93,8 +103,14 @@ class SteppedData:
 class MultiStepStepper:
     def __init__(self, module, in_names: List[str], out_names: List[str], forcing_names: List[str],
                  means: Dict[str, float], stds: Dict[str, float], prescriber: Optional[Prescriber] = None,
-                 corrector=None):
-        """`corrector` (not in the reference's multi-step stepper; `sdy_amd.Corrector`, the reference's `core/corrector.py`
+                 corrector=None, conservation_loss=None):
+        """`conservation_loss` (not in the reference's multi-step stepper; `sdy_amd.ConservationLoss`, the reference's
+        `core/loss.py` as its single-module `core/stepper.py:570-574` uses it): with a `dry_air_penalty` set, the window's
+        generated timelines (denormalised, slot 0 the initial condition, corrected if a corrector is set) go through one
+        `sdy_dry_air_series` call behind the last step; `metrics` gains `dry_air_loss` and `loss` includes it.  The value
+        travels to the host with the loss terms, in the same copy.  None, or no penalty: nothing changes, no launch is added.
+
+        `corrector` (not in the reference's multi-step stepper; `sdy_amd.Corrector`, the reference's `core/corrector.py`
         as its single-module `core/stepper.py:542-543` applies it): every step's prediction is corrected against the state
         it stepped from, on the device, before the loss terms, the prescriber, the timelines and the autoregressive
         feedback see it.  None (the default): nothing changes and no launch is added."""
@@ -120,11 +136,14 @@ class MultiStepStepper:
         # raises ValueError unless every variable the corrector reads or rewrites is in both packers
         self._correct = corrector.bind(self.in_names, self.out_names, self.means, self.stds) \
             if corrector is not None and corrector.enabled else None
+        self.conservation_loss = conservation_loss
+        self._conserve = conservation_loss if conservation_loss is not None and \
+            conservation_loss.dry_air_penalty is not None else None
 
     @classmethod
     def from_statistics(cls, module, in_names: List[str], out_names: List[str], forcing_names: Optional[List[str]] = None,
                         data_dir_stats=None, data_dir=None, prescriber: Optional[Prescriber] = None,
-                        corrector=None) -> "MultiStepStepper":
+                        corrector=None, conservation_loss=None) -> "MultiStepStepper":
         """The reference's constructor path (`stepper_multistep.py:103-131`): forcings default to the input-only names,
         the scalars of `normalize_names` = in U out come from `centering` / `scaling` found in `data_dir_stats`, `data_dir`
         or the packaged statistics (`normalizer.find_statistics`)."""
@@ -133,7 +152,8 @@ class MultiStepStepper:
             forcing_names = [n for n in in_names if n not in out_names]
         path_mean, path_std = find_statistics(data_dir_stats, data_dir)
         norm = get_normalizer(path_mean, path_std, list(dict.fromkeys(list(in_names) + list(out_names))))
-        return cls(module, in_names, out_names, forcing_names, norm.means, norm.stds, prescriber, corrector)
+        return cls(module, in_names, out_names, forcing_names, norm.means, norm.stds, prescriber, corrector,
+                   conservation_loss)
 
     # ---- helpers ------------------------------------------------------------------------------------------------
     def _table(self, names: List[str], data: Dict[str, torch.Tensor]) -> SdyVarTable:
@@ -176,7 +196,10 @@ class MultiStepStepper:
             check(lib.sdy_init_timeline(C.byref(out_tab), T1, B, HW, tln, tld, stream()), "sdy_init_timeline")
             state = torch.empty(B, n_in, H, W, dtype=torch.float32, device=dev)
             check(lib.sdy_norm_pack(C.byref(in_tab), 0, T1, B, HW, ptr(state), stream()), "sdy_norm_pack")
-            loss_terms = torch.zeros(n_forward_steps, B, 2, dtype=torch.float64, device=dev)
+            # the loss terms and, with a conservation loss, one more element behind them for the dry-air non-conservation
+            n_terms = n_forward_steps * B * 2
+            window_sums = torch.zeros(n_terms + (1 if self._conserve is not None else 0), dtype=torch.float64, device=dev)
+            loss_terms = window_sums[:n_terms].view(n_forward_steps, B, 2)
             corr_ws = self._correct.workspace(B, HW, dev) if self._correct is not None else None     # once per window
 
             fa = SdyStepFinishArgs()
@@ -238,15 +261,20 @@ class MultiStepStepper:
 
             # metrics (LpLoss.rel, darcy_loss.py:214-228): one device->host copy for the whole window, into pinned memory
             # behind the window's last launch, with the sticky status word (4 bytes) right behind it
-            terms_host = torch.empty(loss_terms.shape, dtype=torch.float64, pin_memory=True)
-            terms_host.copy_(loss_terms, non_blocking=True)
+            if self._conserve is not None:
+                self._conserve.window(gen, window_sums[n_terms:])
+            sums_host = torch.empty(window_sums.shape, dtype=torch.float64, pin_memory=True)
+            sums_host.copy_(window_sums, non_blocking=True)
+            terms_host = sums_host[:n_terms].view(n_forward_steps, B, 2)
+            dry_air_host = sums_host[n_terms:] if self._conserve is not None else None
             flags_host = None
             if self.check_status:
                 flags_host = torch.zeros(1, dtype=torch.int32, pin_memory=True)
                 check(lib.sdy_status_flags_async(ptr(flags_host), 1, stream()), "sdy_status_flags_async")
             done = torch.cuda.Event()
             done.record(torch.cuda.current_stream(dev))
-        metrics = WindowMetrics(terms_host, flags_host, done, "MultiStepStepper.run_on_batch")
+        metrics = WindowMetrics(terms_host, flags_host, done, "MultiStepStepper.run_on_batch", dry_air_host,
+                                self._conserve.dry_air_penalty if self._conserve is not None else None)
         # normalised targets for the caller (full_data_norm of the reference): one launch per variable, the (B, T1) axes
         # flattened into the batch axis of the same kernel
         target_norm = {}
