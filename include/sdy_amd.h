@@ -761,6 +761,57 @@ int sdy_zonal_accumulate(const sdy_zonal_args* args, void* stream);
 int sdy_zonal_accumulate_host(const sdy_zonal_args* args);
 size_t sdy_zonal_args_bytes(void);        /* sizeof(sdy_zonal_args) of the library (the bindings compare their layout) */
 
+/* Per-degree power spectra of generated, target and error fields (no counterpart in the reference, whose only measure of
+ * blurring is weighted_grad_mag_percent_diff): one launch adds ONE window of all listed variables to float64 accumulators that
+ * stay on the device.  For the coefficients a[l][m] of one field (RealSHT: norm "ortho", csphase, m <= l)
+ *   P(l) = |a[l,0]|^2 + 2 * sum_{m = 1 .. min(l, mtr - 1)} |a[l,m]|^2,   l < lmax
+ * so that sum_l P(l) is the integral of the squared field over the sphere for a band-limited field on the Legendre-Gauss grid.
+ *   gen, target: dev float, coefficients in the internal layout above as sdy_legendre_fwd writes them for ONE image (B = 1):
+ *              Cs[l][m][ri][field], m < mtr, gen_fields / target_fields fields per plane (the C of the transform, padding
+ *              included).  Entries with m > l and fields that the decoding below does not name are never read.
+ *              gen field of (variable v, member i0, sample i1, window time t) = v*gen_var_stride + t*gen_time_stride + i0*n1 + i1
+ *              target field of (v, i1, t)                                     = v*target_var_stride + t*target_time_stride + i1
+ *              (the rows of one (variable, time) are consecutive fields: a run of 4 x rows bytes per plane)
+ *   gen_scale, target_scale: dev float [gen_fields] / [target_fields], or NULL for 1: what a field's stored coefficients are
+ *              to be multiplied with, in float64 before anything else (exact for a power of two).  The split-fp16 Legendre
+ *              analysis stages SDY_ACT_SX x |Xf| as fp16, so a field in physical units (a pressure in Pa) has to be handed to
+ *              sdy_rfft_lon scaled down (its per-field a, with d = 0) and its scale undone here.
+ *   accumulators: dev double, contiguous (nvars, n_timesteps, lmax) each, zeroed by the caller before the first call; window
+ *              time t lands at time t_start + t.  gen_power and target_power are required, err_power may be NULL:
+ *                gen_power    += mean over the n0*n1 generated rows of P of the row
+ *                target_power += mean over the n1 target rows of P of the row
+ *                err_power    += mean over the n0*n1 rows of P of (gen row (i0, i1) - target row i1), from the coefficient
+ *                                differences (the transform is linear), the two fp32 coefficients subtracted in float64
+ *              The cross spectrum sum_m w_m Re(gen conj(target)), pooled likewise, is (gen_power + target_power - err_power)/2.
+ * Every sum is float64 in a fixed order (csrc/spectrum.h): a row's orders in ascending m; the rows of an element in 256 slots
+ * (row r in slot r % 256, ascending r) that meet in a butterfly.  One wave owns an accumulator element: no atomics, no LDS;
+ * calls that touch the same times must be ordered on a stream.  A row's P(l) depends on its own coefficients only, whatever
+ * else the call holds; device and host twin give the same bits.  16-byte loads of a buffer whose pointer is 16-byte aligned
+ * and whose field count and two strides are multiples of 4; 4-byte loads otherwise (same values).
+ * SDY_ERR_ARG, before anything is launched: NULL args / gen / target / gen_power / target_power; a non-positive lmax, mtr,
+ * field count, nvars, n0, n1, T or n_timesteps; mtr > lmax; a negative stride; t_start < 0; t_start + T > n_timesteps; a
+ * buffer whose field count does not reach the last row of the last time of the last variable.
+ * SDY_ERR_UNSUPPORTED: n0*n1 >= 2^31 - 256 (row numbers are 32-bit), T or nvars > 65535 (grid extents), lmax*mtr*2*fields >=
+ * 2^40 for either buffer, nvars*n_timesteps*lmax >= 2^40 (flat indices are 64-bit).
+ * The _host twin: the same structure with HOST pointers and the same checks; the arithmetic is the header the kernel compiles
+ * (csrc/spectrum.h), so the semantics can be pinned without a device. */
+typedef struct sdy_spectrum_args {
+  const float* gen;
+  const float* target;
+  const float* gen_scale;
+  const float* target_scale;
+  int lmax, mtr;
+  int gen_fields, target_fields;
+  int gen_var_stride, gen_time_stride;
+  int target_var_stride, target_time_stride;
+  int nvars, n0, n1, T;
+  int t_start, n_timesteps;
+  double *gen_power, *target_power, *err_power;
+} sdy_spectrum_args;
+int sdy_degree_power(const sdy_spectrum_args* args, void* stream);
+int sdy_degree_power_host(const sdy_spectrum_args* args);
+size_t sdy_spectrum_args_bytes(void);     /* sizeof(sdy_spectrum_args) of the library (the bindings compare their layout) */
+
 /* ---------------------------------------------------------------------------------------------------------
  * Sticky status word of the CURRENT device.  Kernels only ever set bits; the host reads (and optionally clears) it once per
  * window, not per launch (MultiStepStepper.run_on_batch does, after the window's single loss read-back).

@@ -242,6 +242,19 @@ class SdyZonalArgs(C.Structure):
     ]
 
 
+class SdySpectrumArgs(C.Structure):
+    _fields_ = [
+        ("gen", C.c_void_p), ("target", C.c_void_p), ("gen_scale", C.c_void_p), ("target_scale", C.c_void_p),
+        ("lmax", C.c_int), ("mtr", C.c_int),
+        ("gen_fields", C.c_int), ("target_fields", C.c_int),
+        ("gen_var_stride", C.c_int), ("gen_time_stride", C.c_int),
+        ("target_var_stride", C.c_int), ("target_time_stride", C.c_int),
+        ("nvars", C.c_int), ("n0", C.c_int), ("n1", C.c_int), ("T", C.c_int),
+        ("t_start", C.c_int), ("n_timesteps", C.c_int),
+        ("gen_power", C.c_void_p), ("target_power", C.c_void_p), ("err_power", C.c_void_p),
+    ]
+
+
 # name -> (restype, argtypes); every symbol include/sdy_amd.h declares
 SIGNATURES = {
     "sdy_version": (C.c_int, []),
@@ -354,6 +367,9 @@ SIGNATURES = {
     "sdy_zonal_accumulate": (C.c_int, [C.POINTER(SdyZonalArgs), C.c_void_p]),
     "sdy_zonal_accumulate_host": (C.c_int, [C.POINTER(SdyZonalArgs)]),
     "sdy_zonal_args_bytes": (C.c_size_t, []),
+    "sdy_degree_power": (C.c_int, [C.POINTER(SdySpectrumArgs), C.c_void_p]),
+    "sdy_degree_power_host": (C.c_int, [C.POINTER(SdySpectrumArgs)]),
+    "sdy_spectrum_args_bytes": (C.c_size_t, []),
     "sdy_profile_enable": (C.c_int, [C.c_int]),
     "sdy_profile_stage_count": (C.c_int, []),
     "sdy_profile_stage_name": (C.c_char_p, [C.c_int]),
@@ -399,7 +415,8 @@ def _load():
     for what, theirs, ours in (("sdy_corrector_args", lib.sdy_corrector_args_bytes(), C.sizeof(SdyCorrectorArgs)),
                                ("sdy_dry_air_args", lib.sdy_dry_air_args_bytes(), C.sizeof(SdyDryAirArgs)),
                                ("sdy_video_args", lib.sdy_video_args_bytes(), C.sizeof(SdyVideoArgs)),
-                               ("sdy_zonal_args", lib.sdy_zonal_args_bytes(), C.sizeof(SdyZonalArgs))):
+                               ("sdy_zonal_args", lib.sdy_zonal_args_bytes(), C.sizeof(SdyZonalArgs)),
+                               ("sdy_spectrum_args", lib.sdy_spectrum_args_bytes(), C.sizeof(SdySpectrumArgs))):
         if theirs != ours:
             raise ImportError(f"{LIB_PATH}: {what} of the bindings ({ours} bytes) and of the library ({theirs}) differ: "
                               "rebuild the library (make -C spherical-dyffusion_amd/csrc)")

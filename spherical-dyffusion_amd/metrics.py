@@ -737,7 +737,10 @@ class InferenceAggregator:
     `video_data=True` (`extended_video_data=True` for the extended statistics too) and `zonal_mean_data=True` add the
     `video` / `zonal_mean` aggregators (`VideoAggregator`, `ZonalMeanAggregator`): the numbers behind the reference's videos
     and hovmollers, accumulated on the device and read with `get_video_data()` / `get_zonal_mean_data()`.  They add no log
-    keys, and `log_video` / `enable_extended_videos` / `log_zonal_mean_images` (the rendered products) keep raising."""
+    keys, and `log_video` / `enable_extended_videos` / `log_zonal_mean_images` (the rendered products) keep raising.
+
+    `power_spectrum_data=True` adds `power_spectrum` (`sdy_amd.spectrum.PowerSpectrumAggregator` on the grid `spectrum_grid`):
+    per-degree power of gen, target and error per lead time, read with `get_power_spectrum_data()`; no log keys either."""
 
     accepts_sample_weights = True
 
@@ -745,7 +748,8 @@ class InferenceAggregator:
                  n_ensemble_members: int = 1, record_step_20: bool = False, log_video: bool = False,
                  enable_extended_videos: bool = False, log_zonal_mean_images: bool = False, dist=None, metadata=None,
                  device=None, grad_mag_percent_diff: bool = False, video_data: bool = False,
-                 extended_video_data: bool = False, zonal_mean_data: bool = False):
+                 extended_video_data: bool = False, zonal_mean_data: bool = False, power_spectrum_data: bool = False,
+                 spectrum_grid: str = "equiangular"):
         if log_video or enable_extended_videos or log_zonal_mean_images:
             raise NotImplementedError("video / zonal-mean image logging is out of scope of sdy_amd (DESIGN.md section 8)")
         if n_timesteps is None:
@@ -767,6 +771,11 @@ class InferenceAggregator:
                                                          dist=dist, metadata=metadata)
         if zonal_mean_data:
             self._aggregators["zonal_mean"] = ZonalMeanAggregator(n_timesteps=n_timesteps, dist=dist, metadata=metadata)
+        if power_spectrum_data:
+            from .spectrum import PowerSpectrumAggregator      # (spectrum.py builds on this module)
+
+            self._aggregators["power_spectrum"] = PowerSpectrumAggregator(n_timesteps=n_timesteps, grid=spectrum_grid,
+                                                                          dist=dist, metadata=metadata)
 
     @torch.no_grad()
     def record_batch(self, loss, target_data, gen_data, target_data_norm, gen_data_norm, i_time_start: int = 0,
@@ -802,3 +811,7 @@ class InferenceAggregator:
     def get_zonal_mean_data(self):
         """`ZonalMeanAggregator.get_data()` of the run (`zonal_mean_data=True`)."""
         return self._aggregators["zonal_mean"].get_data()
+
+    def get_power_spectrum_data(self):
+        """`PowerSpectrumAggregator.get_data()` of the run (`power_spectrum_data=True`)."""
+        return self._aggregators["power_spectrum"].get_data()
