@@ -761,6 +761,72 @@ int sdy_zonal_accumulate(const sdy_zonal_args* args, void* stream);
 int sdy_zonal_accumulate_host(const sdy_zonal_args* args);
 size_t sdy_zonal_args_bytes(void);        /* sizeof(sdy_zonal_args) of the library (the bindings compare their layout) */
 
+/* Per-member time sums of an ensemble rollout (the reference's ensemble TimeMeanAggregator,
+ * src/evaluation/aggregators/time_mean.py with is_ensemble=True, keeps one time-mean map per member): one launch adds ONE
+ * window of all variables to float64 accumulators that stay on the device.  gen / target / strides as sdy_video_args.
+ *   gen[v]:     dev float, element (i0, i1, t, p) of variable v at gen[v] + i0*gs0 + i1*gs1 + t*HW + p: n0 members, n1
+ *               samples; the member-stacked transposed view of the window driver is read in place (flat rows: n0 = 1)
+ *   target[v]:  dev float, element (i1, t, p) at target[v] + i1*ts1 + t*HW + p
+ *   t0:         the first counted time of the window: 1 when the window starts a run (its first time is the initial
+ *               condition), else 0
+ *   gen_sum:    dev double, contiguous (nvars, n0, n1, HW), zeroed by the caller before the first call
+ *   target_sum: dev double, contiguous (nvars, n1, HW), likewise
+ *     every element += the float64 sum of its fp32 values over t0 <= t < T, in ascending t
+ * Exactly one thread owns an accumulator element (no atomics, no LDS): calls on the same accumulators must be ordered on a
+ * stream.  The order of every sum is fixed, so an element's value is bit-identical to the _host twin's, in any batch and in
+ * any run.  16-byte loads when HW, every stride and every input pointer allow them, scalar loads otherwise (same values).
+ * SDY_ERR_ARG, before anything is launched: NULL args / gen[v] / target[v] / gen_sum / target_sum, an accumulator not 8-byte
+ * aligned, nvars outside 1..SDY_MAX_VARS, a non-positive n0 / n1 / T / HW, a negative stride, t0 outside 0..T-1.
+ * SDY_ERR_UNSUPPORTED: T*HW > 2^30, n0*n1 >= 2^31, nvars*n0*n1*HW >= 2^50 (flat accumulator indices are 64-bit).
+ * The _host twin: the same structure with HOST pointers and the same checks; the arithmetic is the header the kernel compiles
+ * (csrc/member_mean.h), so the semantics can be pinned without a device. */
+typedef struct sdy_member_sum_args {
+  int nvars;
+  const float* gen[SDY_MAX_VARS];
+  const float* target[SDY_MAX_VARS];
+  long gs0, gs1, ts1;
+  int n0, n1, T, HW;
+  int t0;
+  double *gen_sum, *target_sum;
+} sdy_member_sum_args;
+int sdy_member_time_sum(const sdy_member_sum_args* args, void* stream);
+int sdy_member_time_sum_host(const sdy_member_sum_args* args);
+size_t sdy_member_sum_args_bytes(void);   /* sizeof(sdy_member_sum_args) of the library (the bindings compare their layout) */
+
+/* Area-weighted statistics of the per-member time means, all variables of one grid in one call (two launches: per-block
+ * partials into ws, then the partials of a variable in block order; no atomics, bit-identical from run to run).
+ *   gen_sum, target_sum: dev double, what sdy_member_time_sum accumulated: (nvars, M, n1, HW) and (nvars, n1, HW)
+ *   n_times:  the number of times behind the sums; g_m = gen_sum / n_times, t = target_sum / n_times
+ *   weights:  dev float (HW), widened to double
+ *   out:      dev double (nvars, 2 M + 4), overwritten.  With sum_w = the sum over the n1 samples and the HW grid points of
+ *             weights[p] * (.), per variable:
+ *               out[m]       = sum_w (g_m - t)^2,  m < M          out[M + m]   = sum_w (g_m - t)
+ *               out[2 M]     = sum_w (mean_m g - t)^2             out[2 M + 1] = sum_w (mean_m g - t)
+ *               out[2 M + 2] = sum_w of the fair CRPS  mean_m |g_m - t| - sum_{i,j} |g_i - g_j| / (2 M (M - 1))
+ *               out[2 M + 3] = sum_w of the unbiased variance over the members
+ *             M == 1: CRPS = |g - t|, variance 0.  The caller divides by n1 * sum(weights) (after adding ranks, if any).
+ *   ws:       dev, 8-byte aligned, at least sdy_member_stats_workspace_bytes(nvars, M, n1, HW); scratch only
+ * Everything is float64.  The _host twin (ws may be NULL) adds the same per-point terms (csrc/member_mean.h) in the same
+ * blocks of 256 points, each block in point order where the device uses a butterfly: equal to rounding, not to the bit.
+ * SDY_ERR_ARG, before anything is launched: NULL args / gen_sum / target_sum / weights / out / ws, a double pointer not 8-byte
+ * aligned, a non-positive nvars / M / n1 / HW, n_times not finite and > 0, ws_bytes too small.
+ * SDY_ERR_UNSUPPORTED: M > SDY_MEMBER_STATS_MAX_MEMBERS, nvars > 65535, n1*HW > 2^30, nvars*M*n1*HW >= 2^50. */
+#define SDY_MEMBER_STATS_MAX_MEMBERS 64
+typedef struct sdy_member_stats_args {
+  int nvars, M, n1, HW;
+  const double* gen_sum;
+  const double* target_sum;
+  const float* weights;
+  double n_times;
+  double* out;
+  void* ws;
+  size_t ws_bytes;
+} sdy_member_stats_args;
+int sdy_member_map_stats(const sdy_member_stats_args* args, void* stream);
+int sdy_member_map_stats_host(const sdy_member_stats_args* args);
+size_t sdy_member_stats_workspace_bytes(int nvars, int M, int n1, int HW);   /* 0 for arguments outside the supported range */
+size_t sdy_member_stats_args_bytes(void); /* sizeof(sdy_member_stats_args) of the library (the bindings compare their layout) */
+
 /* Per-degree power spectra of generated, target and error fields (no counterpart in the reference, whose only measure of
  * blurring is weighted_grad_mag_percent_diff): one launch adds ONE window of all listed variables to float64 accumulators that
  * stay on the device.  For the coefficients a[l][m] of one field (RealSHT: norm "ortho", csphase, m <= l)

@@ -242,6 +242,29 @@ class SdyZonalArgs(C.Structure):
     ]
 
 
+class SdyMemberSumArgs(C.Structure):
+    _fields_ = [
+        ("nvars", C.c_int), ("gen", C.c_void_p * SDY_MAX_VARS), ("target", C.c_void_p * SDY_MAX_VARS),
+        ("gs0", C.c_long), ("gs1", C.c_long), ("ts1", C.c_long),
+        ("n0", C.c_int), ("n1", C.c_int), ("T", C.c_int), ("HW", C.c_int),
+        ("t0", C.c_int),
+        ("gen_sum", C.c_void_p), ("target_sum", C.c_void_p),
+    ]
+
+
+SDY_MEMBER_STATS_MAX_MEMBERS = 64
+
+
+class SdyMemberStatsArgs(C.Structure):
+    _fields_ = [
+        ("nvars", C.c_int), ("M", C.c_int), ("n1", C.c_int), ("HW", C.c_int),
+        ("gen_sum", C.c_void_p), ("target_sum", C.c_void_p), ("weights", C.c_void_p),
+        ("n_times", C.c_double),
+        ("out", C.c_void_p),
+        ("ws", C.c_void_p), ("ws_bytes", C.c_size_t),
+    ]
+
+
 class SdySpectrumArgs(C.Structure):
     _fields_ = [
         ("gen", C.c_void_p), ("target", C.c_void_p), ("gen_scale", C.c_void_p), ("target_scale", C.c_void_p),
@@ -367,6 +390,13 @@ SIGNATURES = {
     "sdy_zonal_accumulate": (C.c_int, [C.POINTER(SdyZonalArgs), C.c_void_p]),
     "sdy_zonal_accumulate_host": (C.c_int, [C.POINTER(SdyZonalArgs)]),
     "sdy_zonal_args_bytes": (C.c_size_t, []),
+    "sdy_member_time_sum": (C.c_int, [C.POINTER(SdyMemberSumArgs), C.c_void_p]),
+    "sdy_member_time_sum_host": (C.c_int, [C.POINTER(SdyMemberSumArgs)]),
+    "sdy_member_sum_args_bytes": (C.c_size_t, []),
+    "sdy_member_map_stats": (C.c_int, [C.POINTER(SdyMemberStatsArgs), C.c_void_p]),
+    "sdy_member_map_stats_host": (C.c_int, [C.POINTER(SdyMemberStatsArgs)]),
+    "sdy_member_stats_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "sdy_member_stats_args_bytes": (C.c_size_t, []),
     "sdy_degree_power": (C.c_int, [C.POINTER(SdySpectrumArgs), C.c_void_p]),
     "sdy_degree_power_host": (C.c_int, [C.POINTER(SdySpectrumArgs)]),
     "sdy_spectrum_args_bytes": (C.c_size_t, []),
@@ -416,6 +446,8 @@ def _load():
                                ("sdy_dry_air_args", lib.sdy_dry_air_args_bytes(), C.sizeof(SdyDryAirArgs)),
                                ("sdy_video_args", lib.sdy_video_args_bytes(), C.sizeof(SdyVideoArgs)),
                                ("sdy_zonal_args", lib.sdy_zonal_args_bytes(), C.sizeof(SdyZonalArgs)),
+                               ("sdy_member_sum_args", lib.sdy_member_sum_args_bytes(), C.sizeof(SdyMemberSumArgs)),
+                               ("sdy_member_stats_args", lib.sdy_member_stats_args_bytes(), C.sizeof(SdyMemberStatsArgs)),
                                ("sdy_spectrum_args", lib.sdy_spectrum_args_bytes(), C.sizeof(SdySpectrumArgs))):
         if theirs != ours:
             raise ImportError(f"{LIB_PATH}: {what} of the bindings ({ours} bytes) and of the library ({theirs}) differ: "

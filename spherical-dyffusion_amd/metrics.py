@@ -262,6 +262,13 @@ def grad_mag_percent_diff(s: torch.Tensor) -> torch.Tensor:
     return 100.0 * (s[..., 9] - s[..., 8]) / s[..., 8]
 
 
+def whole_ics_message(who: str) -> str:
+    """What an ensemble aggregator says to a ragged share (flat rows: an initial condition's members cut by a rank boundary)."""
+    return (f"{who} needs member-stacked (members, samples, time, lat, lon) "
+            "predictions: ensemble-mean RMSE / CRPS / spread of an initial condition need all of its "
+            "members on one rank (shard whole initial conditions, or use TimeMeanAggregator)")
+
+
 class MeanAggregator:
     """Per-timestep series of area-weighted metrics: host mirror of `MeanAggregator` / `AreaWeightedReducedMetric`
     (`src/ace_inference/core/aggregator/inference/reduced.py:105-266`) minus the wandb table / xarray packaging.
@@ -309,9 +316,7 @@ class MeanAggregator:
         for name, gen in gen_data.items():
             if self.is_ensemble:
                 if gen.dim() != 5:
-                    raise ValueError("MeanAggregator(is_ensemble=True) needs member-stacked (members, samples, time, lat, lon) "
-                                     "predictions: ensemble-mean RMSE / CRPS / spread of an initial condition need all of its "
-                                     "members on one rank (shard whole initial conditions, or use TimeMeanAggregator)")
+                    raise ValueError(whole_ics_message("MeanAggregator(is_ensemble=True)"))
                 pred = gen
             else:
                 pred = gen[None]
@@ -451,6 +456,36 @@ class OneStepMeanAggregator:
         return {k: float(self._dist.reduce_mean(logs[k].reshape(1))[0]) for k in sorted(logs)}
 
 
+def window_layouts(target_data, gen_data):
+    """Per generated variable (gen, target, n0, n1, gs0, gs1, ts1, T, H, W) of one window, everything checked but the place of
+    its times in a run; nothing is enqueued."""
+    if len(gen_data) == 0:
+        raise ValueError("No data in gen_data")
+    out = []
+    for name, g in gen_data.items():
+        if name not in target_data:
+            raise ValueError(f"no target for generated variable {name!r}")
+        t = target_data[name]
+        if g.dim() not in (4, 5) or t.dim() != 4:
+            raise ValueError(f"{name!r}: generated data are (samples, time, lat, lon) or (members, samples, time, lat, lon)"
+                             f" and targets (samples, time, lat, lon), got {tuple(g.shape)} and {tuple(t.shape)}")
+        if tuple(g.shape[-4:]) != tuple(t.shape):
+            raise ValueError(f"{name!r}: generated {tuple(g.shape)} against target {tuple(t.shape)}")
+        H, W = g.shape[-2:]
+        gv, n0, n1, gs0, gs1, T, _ = _strided_layout(g)
+        tv, _, tn1, _, ts1, _, _ = _strided_layout(t)
+        if min(n0, n1, T, H, W) < 1:
+            raise ValueError("empty tensor")
+        if (n0, n1) != (1 if g.dim() == 4 else g.shape[0], tn1):   # (a 5-D view that had to be copied came back flat)
+            gv = gv.view(g.shape)
+            n0, n1, gs0, gs1 = g.shape[0], g.shape[1], gv.stride(0), gv.stride(1)
+        out.append((gv, tv, n0, n1, gs0, gs1, ts1, T, H, W))
+    T = out[0][7]
+    if any(l[7] != T for l in out):
+        raise ValueError("the variables of one window differ in their number of times")
+    return out
+
+
 class _FieldAccumulator:
     """What `VideoAggregator` and `ZonalMeanAggregator` share: the layouts of a window's tensors, the float64 accumulators
     (one flat device buffer per statistic, the variables' blocks in dict order, so a run of same-shaped variables is one
@@ -477,31 +512,9 @@ class _FieldAccumulator:
         raise NotImplementedError
 
     def _layouts(self, target_data, gen_data, i_time_start: int):
-        """Per generated variable (gen, target, n0, n1, gs0, gs1, ts1, T, H, W), everything checked; nothing is enqueued."""
-        if len(gen_data) == 0:
-            raise ValueError("No data in gen_data")
-        out = []
-        for name, g in gen_data.items():
-            if name not in target_data:
-                raise ValueError(f"no target for generated variable {name!r}")
-            t = target_data[name]
-            if g.dim() not in (4, 5) or t.dim() != 4:
-                raise ValueError(f"{name!r}: generated data are (samples, time, lat, lon) or (members, samples, time, lat, lon)"
-                                 f" and targets (samples, time, lat, lon), got {tuple(g.shape)} and {tuple(t.shape)}")
-            if tuple(g.shape[-4:]) != tuple(t.shape):
-                raise ValueError(f"{name!r}: generated {tuple(g.shape)} against target {tuple(t.shape)}")
-            H, W = g.shape[-2:]
-            gv, n0, n1, gs0, gs1, T, _ = _strided_layout(g)
-            tv, _, tn1, _, ts1, _, _ = _strided_layout(t)
-            if min(n0, n1, T, H, W) < 1:
-                raise ValueError("empty tensor")
-            if (n0, n1) != (1 if g.dim() == 4 else g.shape[0], tn1):   # (a 5-D view that had to be copied came back flat)
-                gv = gv.view(g.shape)
-                n0, n1, gs0, gs1 = g.shape[0], g.shape[1], gv.stride(0), gv.stride(1)
-            out.append((gv, tv, n0, n1, gs0, gs1, ts1, T, H, W))
+        """`window_layouts` of a window whose times must lie inside the aggregator's."""
+        out = window_layouts(target_data, gen_data)
         T = out[0][7]
-        if any(l[7] != T for l in out):
-            raise ValueError("the variables of one window differ in their number of times")
         if i_time_start < 0 or i_time_start + T > self._n_timesteps:
             raise ValueError(f"times {i_time_start}..{i_time_start + T - 1} outside the aggregator's {self._n_timesteps}")
         return out
@@ -740,7 +753,13 @@ class InferenceAggregator:
     keys, and `log_video` / `enable_extended_videos` / `log_zonal_mean_images` (the rendered products) keep raising.
 
     `power_spectrum_data=True` adds `power_spectrum` (`sdy_amd.spectrum.PowerSpectrumAggregator` on the grid `spectrum_grid`):
-    per-degree power of gen, target and error per lead time, read with `get_power_spectrum_data()`; no log keys either."""
+    per-degree power of gen, target and error per lead time, read with `get_power_spectrum_data()`; no log keys either.
+
+    `ensemble_time_mean_data=True` adds `time_mean_ensemble` (`sdy_amd.EnsembleTimeMeanAggregator`): one time-mean map per
+    member and the statistics the reference's full-rollout evaluation takes of them (`rmse_member_avg`, `bias_member_avg`,
+    `rmse`, `bias`, `crps` per variable; with `ensemble_time_mean_spread=True` also `spread` and `ssr`), under
+    `<label>/time_mean_ensemble/...`; the maps are read with `get_ensemble_time_mean_maps()`.  Off by default: the default
+    key set of the logs does not change."""
 
     accepts_sample_weights = True
 
@@ -749,7 +768,8 @@ class InferenceAggregator:
                  enable_extended_videos: bool = False, log_zonal_mean_images: bool = False, dist=None, metadata=None,
                  device=None, grad_mag_percent_diff: bool = False, video_data: bool = False,
                  extended_video_data: bool = False, zonal_mean_data: bool = False, power_spectrum_data: bool = False,
-                 spectrum_grid: str = "equiangular"):
+                 spectrum_grid: str = "equiangular", ensemble_time_mean_data: bool = False,
+                 ensemble_time_mean_spread: bool = False):
         if log_video or enable_extended_videos or log_zonal_mean_images:
             raise NotImplementedError("video / zonal-mean image logging is out of scope of sdy_amd (DESIGN.md section 8)")
         if n_timesteps is None:
@@ -776,6 +796,11 @@ class InferenceAggregator:
 
             self._aggregators["power_spectrum"] = PowerSpectrumAggregator(n_timesteps=n_timesteps, grid=spectrum_grid,
                                                                           dist=dist, metadata=metadata)
+        if ensemble_time_mean_data or ensemble_time_mean_spread:
+            from .member_mean import EnsembleTimeMeanAggregator      # (member_mean.py builds on this module)
+
+            self._aggregators["time_mean_ensemble"] = EnsembleTimeMeanAggregator(
+                area_weights, dist=dist, metadata=metadata, spread=ensemble_time_mean_spread)
 
     @torch.no_grad()
     def record_batch(self, loss, target_data, gen_data, target_data_norm, gen_data_norm, i_time_start: int = 0,
@@ -811,6 +836,10 @@ class InferenceAggregator:
     def get_zonal_mean_data(self):
         """`ZonalMeanAggregator.get_data()` of the run (`zonal_mean_data=True`)."""
         return self._aggregators["zonal_mean"].get_data()
+
+    def get_ensemble_time_mean_maps(self):
+        """`EnsembleTimeMeanAggregator.time_mean_maps()` of the run (`ensemble_time_mean_data=True`)."""
+        return self._aggregators["time_mean_ensemble"].time_mean_maps()
 
     def get_power_spectrum_data(self):
         """`PowerSpectrumAggregator.get_data()` of the run (`power_spectrum_data=True`)."""
