@@ -127,6 +127,36 @@ int sdy_legendre_inv(const sdy_sht_plan* plan, const float* Cs, float* Yf, int B
  * C % 4 == 0 and Yf, y 16-byte aligned, else SDY_ERR_ALIGN before anything is launched (see sdy_rfft_lon). */
 int sdy_irfft_lon(const sdy_sht_plan* plan, const float* Yf, const float* bias, float* y, int B, int C,
                   void* stream);
+/* The InstanceNorm statistics chain of the fused forward, kernel by kernel (what sdy_sfno_forward launches between its GEMMs;
+ * statistics are dev double [B][C][2] = (sum, sum of squares) over HW of a stored plane, see sdy_conv_args.stats).  None of
+ * these kernels has a scalar tail, so every call is refused before anything is launched when it would need one: HW % 4 != 0, a
+ * batch stride that is not a multiple of 4, or a tensor, statistics or partials pointer off a 16-byte boundary (planes move as
+ * float4, a statistics slot is one pair of doubles) is SDY_ERR_ALIGN; a NULL required pointer, a non-positive extent, n_rows >
+ * 128 or a tile-major stride below ceil(HW / 64) * C * 64 is SDY_ERR_ARG.
+ *
+ * sdy_irfft_lon_act: sdy_irfft_lon with the block's activation on its stores: GELU(ring + bias[c]) (exact erf) goes TILE-MAJOR
+ * to zt ([b][64-pixel tile][C][64], zt_bstride >= ceil(HW / 64) * C * 64 floats per image, the layout sdy_mlp_args.x_tiled reads;
+ * the last tile's pixels past HW are not written) and ring k's (sum, sum of squares) of what was stored to part[b][k][c][2]
+ * (dev double, B * nlat * C * 2, every slot WRITTEN exactly once, not added).  Yf in the channel order of this header,
+ * [m][k][b][ri][c], as for sdy_irfft_lon.  Only the 360-point kernels have this form: SDY_ERR_UNSUPPORTED unless
+ * sdy_sht_plan_kernels reports out[1] == 1 and C % 16 == 0.  zt and part are both required. */
+int sdy_irfft_lon_act(const sdy_sht_plan* plan, const float* Yf, const float* bias, float* zt, long zt_bstride, double* part,
+                      int B, int C, void* stream);
+/* part[b][k][c][2], k < K, summed in the order of k (bit-reproducible) -> a = gamma*rstd, d = beta - mean*a (no time scale /
+ * shift: this is the block's second norm).  `part` is left as it is. */
+int sdy_instnorm_from_partials(const double* part, int K, int B, int C, int HW, const float* gamma, const float* beta,
+                               float eps, float* a, float* d, void* stream);
+/* out = GELU(y) (exact erf) for B images of C channels, y (B, C, HW) with y_bstride floats per image; out NCHW (out_bstride per
+ * image) or, with out_tiled, tile-major as above.  stats (or NULL): the (sum, sum of squares) of what is stored are ADDED to
+ * stats[b][c].  out may be y itself when it is not tiled. */
+int sdy_gelu_stats(const float* y, long y_bstride, float* out, long out_bstride, int out_tiled, double* stats, int B, int C,
+                   int HW, void* stream);
+/* The drop-path skip: out[b] = a[b][c] * x[s] + d[b][c] (one fma; a, d dev [rows of out][C], both NULL = a plain copy) for the
+ * n_rows <= 128 batch rows b = rows[i] (host array); source row s = b, or src_row0 + i when src_row0 >= 0 (x in the launch's own
+ * order).  The (sum, sum of squares) of every stored plane are ADDED to stats[b][c] unless stats is NULL; rows that are not
+ * listed are not touched. */
+int sdy_affine_copy_stats(const float* x, long x_bstride, const float* a, const float* d, float* out, long out_bstride,
+                          double* stats, int C, int HW, const unsigned char* rows, int n_rows, int src_row0, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * _contract_dhconv (src/models/sfno/contractions.py:159-169 via factorizations.py:165-186; called at

@@ -486,6 +486,50 @@ extern "C" int sdy_instnorm_coeffs(const float* x, int B, int C, int HW, const f
   return sdy_instnorm_coeffs_launch(x, B, C, HW, gamma, beta, scale_shift, ss_stride, eps, a, d, (hipStream_t)stream);
 }
 
+// ---- the statistics chain of the fused forward, kernel by kernel (include/sdy_amd.h) ----------------------------------------
+// Thin wrappers over the launchers sdy_sfno_forward uses.  The kernels have no scalar tail and trust their extents, so what
+// they cannot take is refused here, before anything is launched.
+static inline bool tiled_stride_ok(long bs, int C, int HW) { return bs >= (long)((HW + 63) / 64) * C * 64; }
+
+extern "C" int sdy_instnorm_from_partials(const double* part, int K, int B, int C, int HW, const float* gamma,
+                                          const float* beta, float eps, float* a, float* d, void* stream) {
+  if (!part || !gamma || !beta || !a || !d || K <= 0 || B <= 0 || C <= 0 || HW <= 0) return SDY_ERR_ARG;
+  if ((HW & 3) || !fft_aligned16(part)) return SDY_ERR_ALIGN;
+  return sdy_instnorm_from_partials_launch(part, K, B, C, HW, gamma, beta, eps, a, d, (hipStream_t)stream);
+}
+
+extern "C" int sdy_gelu_stats(const float* y, long y_bstride, float* out, long out_bstride, int out_tiled, double* stats,
+                              int B, int C, int HW, void* stream) {
+  if (!y || !out || B <= 0 || C <= 0 || HW <= 0 || y_bstride < 0 || out_bstride < 0) return SDY_ERR_ARG;
+  if ((HW & 3) || (y_bstride & 3) || (out_bstride & 3) || !fft_aligned16(y) || !fft_aligned16(out) || !fft_aligned16(stats))
+    return SDY_ERR_ALIGN;
+  if (out_tiled && (!tiled_stride_ok(out_bstride, C, HW) || out == y)) return SDY_ERR_ARG;
+  return sdy_gelu_stats_launch(y, y_bstride, out, out_bstride, out_tiled ? 1 : 0, stats, B, C, HW, (hipStream_t)stream);
+}
+
+extern "C" int sdy_affine_copy_stats(const float* x, long x_bstride, const float* a, const float* d, float* out,
+                                     long out_bstride, double* stats, int C, int HW, const unsigned char* rows, int n_rows,
+                                     int src_row0, void* stream) {
+  if (!x || !out || !rows || (a == nullptr) != (d == nullptr) || C <= 0 || HW <= 0 || n_rows <= 0 || n_rows > SDY_MAP_MAX ||
+      x_bstride < 0 || out_bstride < 0)
+    return SDY_ERR_ARG;
+  if ((HW & 3) || (x_bstride & 3) || (out_bstride & 3) || !fft_aligned16(x) || !fft_aligned16(out) || !fft_aligned16(stats))
+    return SDY_ERR_ALIGN;
+  return sdy_affine_copy_stats_launch(x, x_bstride, a, d, out, out_bstride, stats, C, HW, rows, n_rows, (hipStream_t)stream,
+                                      src_row0 >= 0 ? src_row0 : -1);
+}
+
+extern "C" int sdy_irfft_lon_act(const sdy_sht_plan* p, const float* Yf, const float* bias, float* zt, long zt_bstride,
+                                 double* part, int B, int C, void* stream) {
+  if (!p || !Yf || !zt || !part || B <= 0 || C <= 0 || zt_bstride < 0) return SDY_ERR_ARG;
+  if (C % 4 != 0 || (zt_bstride & 3) || !fft_aligned16(Yf) || !fft_aligned16(zt) || !fft_aligned16(part)) return SDY_ERR_ALIGN;
+  // only the 360-point kernels carry the activation epilogue (the generic ones have no zt / part form to fall back to)
+  if (!(p->fft.fft360 && p->fft.n == 180) || C % 16 != 0) return SDY_ERR_UNSUPPORTED;
+  if (!tiled_stride_ok(zt_bstride, C, p->nlat * p->nlon)) return SDY_ERR_ARG;
+  return sdy_fft360_launch_inv(p->fft, Yf, bias, nullptr, B, C, p->nlat, p->mtr, 0, nullptr, (hipStream_t)stream, zt, zt_bstride,
+                               part);
+}
+
 static inline int h3_mpad(int Cout) { return Cout > 128 ? round_up(Cout, 256) : 128; }
 static inline int h3_kpad(int Cin) { return round_up(Cin, 64); }
 

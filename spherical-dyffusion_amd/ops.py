@@ -316,6 +316,81 @@ def instnorm_from_stats(stats: torch.Tensor, HW: int, gamma: torch.Tensor, beta:
     return a, d
 
 
+def _stats_ok(stats, B, Cc):
+    assert stats.dtype == torch.float64 and stats.is_cuda and stats.is_contiguous() and stats.numel() == B * Cc * 2
+
+
+def instnorm_from_partials(part: torch.Tensor, HW: int, gamma: torch.Tensor, beta: torch.Tensor, eps: float = 1e-6):
+    """(B, K, C, 2) float64 per-ring (sum, sumsq) partials (`irfft_lon_act`) -> the (a, d) of `instnorm_coeffs` without a time
+    scale / shift; the partials are summed in the order of K (include/sdy_amd.h, sdy_instnorm_from_partials)."""
+    assert part.dtype == torch.float64 and part.is_cuda and part.is_contiguous() and part.dim() == 4 and part.shape[3] == 2
+    B, K, Cc = part.shape[0], part.shape[1], part.shape[2]
+    g, b_ = _aux(gamma, part.device), _aux(beta, part.device)
+    a = torch.empty(B, Cc, dtype=torch.float32, device=part.device)
+    d = torch.empty_like(a)
+    with torch.cuda.device(part.device):
+        check(lib.sdy_instnorm_from_partials(ptr(part), K, B, Cc, HW, ptr(g), ptr(b_), eps, ptr(a), ptr(d), current_stream()),
+              "sdy_instnorm_from_partials")
+    return a, d
+
+
+def gelu_stats(y: torch.Tensor, tiled: bool = False, stats: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """GELU(y) (exact erf) of y (B, C, H, W) with the (sum, sumsq) of the stored planes ADDED to `stats` (B, C, 2) float64
+    (include/sdy_amd.h, sdy_gelu_stats).  Returns (B, C, H, W), or with `tiled` the tile-major (B, ceil(HW / 64), C, 64) tensor
+    `mlp_fused` reads with x_tiled (pixels past HW in the last tile are not written: they hold zeros here)."""
+    y = _f32c(y)
+    B, Cc, H, W = y.shape
+    HW = H * W
+    out = torch.zeros(B, (HW + 63) // 64, Cc, 64, dtype=torch.float32, device=y.device) if tiled else torch.empty_like(y)
+    if stats is not None:
+        _stats_ok(stats, B, Cc)
+    with torch.cuda.device(y.device):
+        check(lib.sdy_gelu_stats(ptr(y), Cc * HW, ptr(out), out[0].numel(), 1 if tiled else 0, ptr(stats), B, Cc, HW,
+                                 current_stream()), "sdy_gelu_stats")
+    return out
+
+
+def affine_copy_stats(x: torch.Tensor, out: torch.Tensor, rows, coeffs=None, stats: Optional[torch.Tensor] = None,
+                      src_row0: int = -1) -> torch.Tensor:
+    """The drop-path skip (include/sdy_amd.h, sdy_affine_copy_stats): out[b] = a[b] * x[s] + d[b] for the batch rows b in `rows`
+    (at most 128), s = b or src_row0 + (index in rows); coeffs = (a, d) of shape (rows of out, C) or None for a copy.  The
+    statistics of the stored planes are ADDED to stats[b]; other rows of `out` and `stats` are left alone."""
+    if not (x.is_cuda and out.is_cuda and x.dtype == out.dtype == torch.float32 and x.is_contiguous() and out.is_contiguous()):
+        raise RuntimeError("sdy_amd ops run on the GPU only (no CPU fallback): contiguous float32 device tensors")
+    Cc, H, W = out.shape[1], out.shape[2], out.shape[3]
+    assert x.shape[1:] == out.shape[1:]
+    rows = [int(r) for r in rows]
+    assert 0 < len(rows) <= 128 and all(0 <= r < out.shape[0] for r in rows)
+    assert all(0 <= s < x.shape[0] for s in (rows if src_row0 < 0 else range(src_row0, src_row0 + len(rows))))
+    rb = (C.c_ubyte * len(rows))(*rows)
+    a = d = None
+    if coeffs is not None:
+        a, d = _aux(coeffs[0], out.device), _aux(coeffs[1], out.device)
+        assert a.numel() == d.numel() == out.shape[0] * Cc
+    if stats is not None:
+        _stats_ok(stats, out.shape[0], Cc)
+    with torch.cuda.device(out.device):
+        check(lib.sdy_affine_copy_stats(ptr(x), Cc * H * W, ptr(a), ptr(d), ptr(out), Cc * H * W, ptr(stats), Cc, H * W, rb,
+                                        len(rows), src_row0, current_stream()), "sdy_affine_copy_stats")
+    return out
+
+
+def irfft_lon_act(plan, Yf: torch.Tensor, bias: Optional[torch.Tensor], B: int, Cc: int):
+    """Inverse longitude FFT of Yf [m][k][b][ri][c] with the block's activation on its stores (include/sdy_amd.h,
+    sdy_irfft_lon_act; `plan` a `sht.ShtPlan` of a 360-point grid, C % 16 == 0): returns (zt, part) = GELU(ring + bias)
+    tile-major (B, ceil(HW / 64), C, 64) and the per-ring float64 (sum, sumsq) (B, nlat, C, 2)."""
+    Yf = _f32c(Yf)
+    assert Yf.numel() == plan.mtr * plan.nlat * B * 2 * Cc
+    HW = plan.nlat * plan.nlon
+    zt = torch.zeros(B, (HW + 63) // 64, Cc, 64, dtype=torch.float32, device=Yf.device)
+    part = torch.empty(B, plan.nlat, Cc, 2, dtype=torch.float64, device=Yf.device)
+    bb = _aux(bias, Yf.device) if bias is not None else None
+    with torch.cuda.device(Yf.device):
+        check(lib.sdy_irfft_lon_act(plan.handle, ptr(Yf), ptr(bb), ptr(zt), zt[0].numel(), ptr(part), B, Cc, current_stream()),
+              "sdy_irfft_lon_act")
+    return zt, part
+
+
 def cold_update(x_s: torch.Tensor, x_ip_next: torch.Tensor, x_ip_s: Optional[torch.Tensor]) -> torch.Tensor:
     """x_s + (x_ip_next - x_ip_s)  (`src/diffusion/dyffusion.py:517-519`); x_ip_s None means x_ip_s == x_s."""
     a, b = _f32c(x_s), _f32c(x_ip_next)

@@ -72,6 +72,85 @@ def test_error_codes_without_gpu(sdy):
         sdy._lib.check(-2, "x")
 
 
+_C_TO_CTYPES = {"int": C.c_int, "long": C.c_long, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t,
+                "uint32_t": C.c_uint32, "uint64_t": C.c_uint64}
+STATS_CHAIN = ("sdy_irfft_lon_act", "sdy_instnorm_from_partials", "sdy_gelu_stats", "sdy_affine_copy_stats")
+
+
+def _prototype_argtypes(hdr, name):
+    """ctypes argument list of `int name(...)` as include/sdy_amd.h declares it: any pointer is a void pointer."""
+    m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", hdr)
+    assert m, f"{name}: no prototype in include/sdy_amd.h"
+    out = []
+    for p in m.group(1).split(","):
+        p = " ".join(p.split())
+        if p == "void":
+            continue
+        if "*" in p:
+            out.append(C.c_void_p)
+        else:
+            out.append(_C_TO_CTYPES[p.replace("const ", "").rsplit(" ", 1)[0]])
+    return out
+
+
+def test_scalar_prototypes_match_the_bindings(sdy):
+    """Every entry point whose binding passes only scalars and untyped pointers -- the stage-level entry points, the four of the
+    InstanceNorm statistics chain among them -- has the header's parameter list, type by type and in order."""
+    from sdy_amd import _lib
+
+    hdr = open(os.path.join(ROOT, "include", "sdy_amd.h")).read()
+    simple = set(_C_TO_CTYPES.values()) | {C.c_void_p}
+    checked = []
+    for name, (res, args) in _lib.SIGNATURES.items():
+        if res is not C.c_int or not set(args) <= simple:
+            continue
+        assert _prototype_argtypes(hdr, name) == list(args), name
+        checked.append(name)
+    assert set(STATS_CHAIN) <= set(checked) and {"sdy_rfft_lon", "sdy_irfft_lon", "sdy_instnorm_from_stats"} <= set(checked)
+
+
+def test_stats_chain_refusals_without_gpu(sdy):
+    """The four stage entry points of the statistics chain refuse what their kernels cannot take by status code BEFORE
+    anything touches the device: on a machine without a GPU a launch attempt would return a positive hipError_t instead."""
+    lib = sdy.lib
+    ARG, UNSUP, ALIGN = -1, -2, -3
+    p, q, odd = 1 << 20, 2 << 20, (1 << 20) + 4          # never dereferenced: two aligned addresses and a misaligned one
+    rows = (C.c_ubyte * 130)()
+    g = lib.sdy_gelu_stats
+    assert g(None, 640, q, 640, 0, None, 1, 2, 320, None) == ARG
+    assert g(p, 640, None, 640, 0, None, 1, 2, 320, None) == ARG
+    assert g(p, 640, q, 640, 0, None, 1, 0, 320, None) == ARG
+    assert g(p, 640, q, 5 * 2 * 64 - 64, 1, None, 1, 2, 320, None) == ARG            # tile-major stride below 5 tiles x C x 64
+    assert g(p, 636, q, 636, 0, None, 1, 2, 318, None) == ALIGN
+    assert g(p, 642, q, 640, 0, None, 1, 2, 320, None) == ALIGN
+    assert g(p, 640, q, 642, 0, None, 1, 2, 320, None) == ALIGN
+    assert g(odd, 640, q, 640, 0, None, 1, 2, 320, None) == ALIGN
+    assert g(p, 640, odd, 640, 0, None, 1, 2, 320, None) == ALIGN
+    assert g(p, 640, q, 640, 0, odd + 4, 1, 2, 320, None) == ALIGN                   # statistics: pairs of doubles
+    f = lib.sdy_affine_copy_stats
+    assert f(None, 640, None, None, q, 640, None, 2, 320, rows, 1, -1, None) == ARG
+    assert f(p, 640, None, None, None, 640, None, 2, 320, rows, 1, -1, None) == ARG
+    assert f(p, 640, None, None, q, 640, None, 2, 320, None, 1, -1, None) == ARG
+    assert f(p, 640, p, None, q, 640, None, 2, 320, rows, 1, -1, None) == ARG          # a without d
+    assert f(p, 640, None, None, q, 640, None, 2, 320, rows, 129, -1, None) == ARG     # more rows than a map holds
+    assert f(p, 640, None, None, q, 640, None, 2, 320, rows, 0, -1, None) == ARG
+    assert f(p, 636, None, None, q, 636, None, 2, 318, rows, 1, -1, None) == ALIGN
+    assert f(p, 641, None, None, q, 640, None, 2, 320, rows, 1, -1, None) == ALIGN
+    assert f(odd, 640, None, None, q, 640, None, 2, 320, rows, 1, -1, None) == ALIGN
+    assert f(p, 640, None, None, odd, 640, None, 2, 320, rows, 1, -1, None) == ALIGN
+    assert f(p, 640, None, None, q, 640, odd + 4, 2, 320, rows, 1, -1, None) == ALIGN
+    h = lib.sdy_instnorm_from_partials
+    assert h(None, 3, 1, 2, 320, p, p, 1e-6, q, q, None) == ARG
+    assert h(p, 3, 1, 2, 320, None, p, 1e-6, q, q, None) == ARG
+    assert h(p, 3, 1, 2, 320, p, p, 1e-6, q, None, None) == ARG
+    assert h(p, 0, 1, 2, 320, p, p, 1e-6, q, q, None) == ARG
+    assert h(p, 3, 1, 2, 318, p, p, 1e-6, q, q, None) == ALIGN
+    assert h(odd + 4, 3, 1, 2, 320, p, p, 1e-6, q, q, None) == ALIGN
+    # sdy_irfft_lon_act: argument checks come before the plan is looked at
+    k = lib.sdy_irfft_lon_act
+    assert k(None, p, None, q, 4096, p, 1, 16, None) == ARG
+
+
 def test_no_cpu_fallback(sdy):
     import torch
 
