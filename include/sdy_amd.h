@@ -71,11 +71,16 @@ int sdy_version(void);
 const char* sdy_error_string(int code);
 /* The argument structures below carry no size field: a caller built against another revision of this header would hand the
  * launchers uninitialised tail bytes (fields are only ever appended).  Contract: zero-initialise every structure with the
- * sizeof of THIS header, and call sdy_abi_check once after loading the library with your own sizeofs, in the order
- * {sdy_conv_args, sdy_mlp_args, sdy_pair_args, sdy_sfno_config, sdy_sfno_fwd_args, sdy_var_table, sdy_step_finish_args}:
- * SDY_OK when all seven equal the library's, SDY_ERR_ARG otherwise (the Python bindings do this at import). */
-#define SDY_ABI_STRUCTS 7
+ * sizeof of THIS header, and call sdy_abi_check once after loading the library with your own sizeofs of every argument
+ * structure below, in header order:
+ *   {sdy_conv_args, sdy_mlp_args, sdy_pair_args, sdy_sfno_config, sdy_sfno_fwd_args, sdy_var_table, sdy_step_finish_args,
+ *    sdy_derived_args, sdy_corrector_args, sdy_dry_air_args, sdy_hist_args, sdy_coarsen_args, sdy_video_args, sdy_zonal_args,
+ *    sdy_member_sum_args, sdy_member_stats_args, sdy_spectrum_args}
+ * SDY_OK when n == SDY_ABI_STRUCTS and every size equals the library's, SDY_ERR_ARG otherwise (the Python bindings do this at
+ * import).  sdy_abi_sizes writes the library's own list, for the message of a failed check (SDY_ERR_ARG: n != SDY_ABI_STRUCTS). */
+#define SDY_ABI_STRUCTS 17
 int sdy_abi_check(const size_t* sizes, int n);
+int sdy_abi_sizes(size_t* sizes, int n);
 
 /* ---------------------------------------------------------------------------------------------------------
  * Spherical-harmonic transform plan.
@@ -590,7 +595,6 @@ typedef struct sdy_corrector_args {
 int sdy_corrector(const sdy_corrector_args* args, void* stream);
 int sdy_corrector_host(const sdy_corrector_args* args);
 size_t sdy_corrector_workspace_bytes(int B, int HW);
-size_t sdy_corrector_args_bytes(void);    /* sizeof(sdy_corrector_args) of the library (the bindings compare their layout) */
 
 /* Dry-air conservation diagnostics (compute_dry_air_absolute_differences, src/ace_inference/core/aggregator/climate_data.py:
  * 199-233; get_dry_air_nonconservation / ConservationLoss, core/loss.py; DryAir, core/aggregator/one_step/derived.py).  For B
@@ -639,7 +643,6 @@ typedef struct sdy_dry_air_args {
 int sdy_dry_air_series(const sdy_dry_air_args* args, void* stream);
 int sdy_dry_air_series_host(const sdy_dry_air_args* args);
 size_t sdy_dry_air_workspace_bytes(int B, int T, int HW);
-size_t sdy_dry_air_args_bytes(void);      /* sizeof(sdy_dry_air_args) of the library (the bindings compare their layout) */
 
 /* Time-mean accumulation of the inference aggregator (src/ace_inference/core/aggregator/inference/time_mean.py:97-117,
  * _add_or_initialize_time_mean): acc[p] += scale * sum over rows (r0, r1) and times t0 <= t < T of
@@ -688,7 +691,6 @@ typedef struct sdy_hist_args {
   unsigned long long* counts;
 } sdy_hist_args;
 int sdy_hist_add(const sdy_hist_args* args, void* stream);
-size_t sdy_hist_args_bytes(void);         /* sizeof(sdy_hist_args) of the library (the bindings compare their layout) */
 size_t sdy_hist_state_bytes(int nvars);   /* 0 for nvars < 1 */
 /* Variable v of a HOST copy of `state`: range, whether a first range has been taken, the sticky flags, the outside counter
  * (any output may be NULL). */
@@ -728,15 +730,30 @@ typedef struct sdy_coarsen_args {
 } sdy_coarsen_args;
 int sdy_time_coarsen(const sdy_coarsen_args* args, void* stream);
 int sdy_time_coarsen_host(const sdy_coarsen_args* args);
-size_t sdy_coarsen_args_bytes(void);      /* sizeof(sdy_coarsen_args) of the library (the bindings compare their layout) */
+
+/* One window of all variables as the field aggregators below read it, in place: what the window driver hands over.
+ *   gen[v]:    dev float, element (i0, i1, t, p) of variable v at gen[v] + i0*gs0 + i1*gs1 + t*plane + p: n0 members (or
+ *              1), n1 samples, T times, plane = the grid points of one time (HW, or H*W; the structure that embeds the window
+ *              says which).  The member-stacked (members, samples, time, lat, lon) view of the window driver is read as it
+ *              is; flat rows are n0 = 1
+ *   target[v]: dev float, element (i1, t, p) at target[v] + i1*ts1 + t*plane + p
+ * 16-byte loads when the plane (for the zonal means: W), every stride and every pointer allow them, scalar loads otherwise
+ * (same values).  Every entry point refuses, before anything is launched, with SDY_ERR_ARG: nvars outside 1..SDY_MAX_VARS, a
+ * non-positive n0 / n1 / T / plane, a negative stride, a NULL gen[v] / target[v]; with SDY_ERR_UNSUPPORTED: T*plane > 2^30,
+ * n0*n1 >= 2^31 (32-bit work items within a variable, 32-bit row numbers). */
+typedef struct sdy_window {
+  int nvars;
+  const float* gen[SDY_MAX_VARS];
+  const float* target[SDY_MAX_VARS];
+  long gs0, gs1, ts1;
+  int n0, n1, T;
+} sdy_window;
 
 /* Per-grid-point video statistics of the inference aggregators (VideoAggregator with its extended statistics,
  * src/ace_inference/core/aggregator/inference/video.py): one launch adds ONE window of all variables to float64 accumulators
  * that stay on the device.
- *   gen[v]:    dev float, element (i0, i1, t, p) of variable v at gen[v] + i0*gs0 + i1*gs1 + t*HW + p: the member-stacked
- *              (members, samples, time, lat, lon) view of the window driver, or flat rows with n0 = 1.  All n0*n1 rows are
- *              pooled (the reference's class takes 4-D data only: pooling members is this library's rule)
- *   target[v]: dev float, element (i1, t, p) at target[v] + i1*ts1 + t*HW + p
+ *   window:    see sdy_window, plane = HW.  All n0*n1 generated rows are pooled (the reference's class takes 4-D data only:
+ *              pooling members is this library's rule)
  *   accumulators: dev double, contiguous (nvars, n_timesteps, HW) each -- variable v's (n_timesteps, HW) block at
  *              base + v*n_timesteps*HW; window time t lands at time t_start + t.  gen_mean and target_mean are required; the
  *              other five are updated where their pointer is non-NULL (the caller fills err_min / err_max with +inf / -inf and
@@ -748,27 +765,22 @@ size_t sdy_coarsen_args_bytes(void);      /* sizeof(sdy_coarsen_args) of the lib
  *              e of row (i0, i1) = fl32(gen - target row i1), the reference's single fp32 subtraction, widened to double;
  *              every sum is float64.
  * Exactly one thread owns an accumulator element (no atomics): calls that touch the same times must be ordered on a stream.
- * 16-byte loads when HW, every stride and every pointer allow them, scalar loads otherwise.
  * SDY_ERR_ARG, before anything is launched: NULL args / gen[v] / target[v] / gen_mean / target_mean, nvars outside
  * 1..SDY_MAX_VARS, a non-positive n0 / n1 / T / HW / n_timesteps, a negative stride, t_start < 0, t_start + T > n_timesteps.
  * SDY_ERR_UNSUPPORTED: T*HW > 2^30, n0*n1 >= 2^31, n_timesteps*HW >= 2^40 (flat accumulator indices are 64-bit).
  * The _host twin: the same structure with HOST pointers and the same checks; the arithmetic is the header the kernel compiles
  * (csrc/field_stats.h), so the semantics can be pinned without a device. */
 typedef struct sdy_video_args {
-  int nvars;
-  const float* gen[SDY_MAX_VARS];
-  const float* target[SDY_MAX_VARS];
-  long gs0, gs1, ts1;
-  int n0, n1, T, HW;
+  sdy_window win;
+  int HW;
   int t_start, n_timesteps;
   double *gen_mean, *target_mean, *gen_sq, *target_sq, *err_var, *err_min, *err_max;
 } sdy_video_args;
 int sdy_video_accumulate(const sdy_video_args* args, void* stream);
 int sdy_video_accumulate_host(const sdy_video_args* args);
-size_t sdy_video_args_bytes(void);        /* sizeof(sdy_video_args) of the library (the bindings compare their layout) */
 
 /* Zonal means of the inference aggregators (ZonalMeanAggregator, .../aggregator/inference/zonal_mean.py): one launch adds ONE
- * window of all variables.  gen / target / strides as above with HW = H*W.
+ * window of all variables.  window: see sdy_window, plane = H*W.
  *   gen_acc, target_acc: dev double, contiguous (nvars, n1, n_timesteps, H) each, zeroed by the caller before the first call:
  *     gen_acc[v, s, t_start + t, lat]    += mean over the n0 members of the mean over the W longitudes of gen[v][., s, t, lat, .]
  *     target_acc[v, s, t_start + t, lat] += mean over the W longitudes of target[v][s, t, lat, .]
@@ -779,24 +791,18 @@ size_t sdy_video_args_bytes(void);        /* sizeof(sdy_video_args) of the libra
  * 1..SDY_MAX_VARS, a non-positive n0 / n1 / T / H / W / n_timesteps, a negative stride, t_start < 0, t_start + T >
  * n_timesteps.  SDY_ERR_UNSUPPORTED: T*H*W > 2^30, n0*n1 >= 2^31, n_timesteps*H >= 2^40, n1*n_timesteps*H >= 2^50. */
 typedef struct sdy_zonal_args {
-  int nvars;
-  const float* gen[SDY_MAX_VARS];
-  const float* target[SDY_MAX_VARS];
-  long gs0, gs1, ts1;
-  int n0, n1, T, H, W;
+  sdy_window win;
+  int H, W;
   int t_start, n_timesteps;
   double *gen_acc, *target_acc;
 } sdy_zonal_args;
 int sdy_zonal_accumulate(const sdy_zonal_args* args, void* stream);
 int sdy_zonal_accumulate_host(const sdy_zonal_args* args);
-size_t sdy_zonal_args_bytes(void);        /* sizeof(sdy_zonal_args) of the library (the bindings compare their layout) */
 
 /* Per-member time sums of an ensemble rollout (the reference's ensemble TimeMeanAggregator,
  * src/evaluation/aggregators/time_mean.py with is_ensemble=True, keeps one time-mean map per member): one launch adds ONE
- * window of all variables to float64 accumulators that stay on the device.  gen / target / strides as sdy_video_args.
- *   gen[v]:     dev float, element (i0, i1, t, p) of variable v at gen[v] + i0*gs0 + i1*gs1 + t*HW + p: n0 members, n1
- *               samples; the member-stacked transposed view of the window driver is read in place (flat rows: n0 = 1)
- *   target[v]:  dev float, element (i1, t, p) at target[v] + i1*ts1 + t*HW + p
+ * window of all variables to float64 accumulators that stay on the device.
+ *   window:     see sdy_window, plane = HW: n0 members, n1 samples
  *   t0:         the first counted time of the window: 1 when the window starts a run (its first time is the initial
  *               condition), else 0
  *   gen_sum:    dev double, contiguous (nvars, n0, n1, HW), zeroed by the caller before the first call
@@ -804,24 +810,20 @@ size_t sdy_zonal_args_bytes(void);        /* sizeof(sdy_zonal_args) of the libra
  *     every element += the float64 sum of its fp32 values over t0 <= t < T, in ascending t
  * Exactly one thread owns an accumulator element (no atomics, no LDS): calls on the same accumulators must be ordered on a
  * stream.  The order of every sum is fixed, so an element's value is bit-identical to the _host twin's, in any batch and in
- * any run.  16-byte loads when HW, every stride and every input pointer allow them, scalar loads otherwise (same values).
+ * any run.
  * SDY_ERR_ARG, before anything is launched: NULL args / gen[v] / target[v] / gen_sum / target_sum, an accumulator not 8-byte
  * aligned, nvars outside 1..SDY_MAX_VARS, a non-positive n0 / n1 / T / HW, a negative stride, t0 outside 0..T-1.
  * SDY_ERR_UNSUPPORTED: T*HW > 2^30, n0*n1 >= 2^31, nvars*n0*n1*HW >= 2^50 (flat accumulator indices are 64-bit).
  * The _host twin: the same structure with HOST pointers and the same checks; the arithmetic is the header the kernel compiles
  * (csrc/member_mean.h), so the semantics can be pinned without a device. */
 typedef struct sdy_member_sum_args {
-  int nvars;
-  const float* gen[SDY_MAX_VARS];
-  const float* target[SDY_MAX_VARS];
-  long gs0, gs1, ts1;
-  int n0, n1, T, HW;
+  sdy_window win;
+  int HW;
   int t0;
   double *gen_sum, *target_sum;
 } sdy_member_sum_args;
 int sdy_member_time_sum(const sdy_member_sum_args* args, void* stream);
 int sdy_member_time_sum_host(const sdy_member_sum_args* args);
-size_t sdy_member_sum_args_bytes(void);   /* sizeof(sdy_member_sum_args) of the library (the bindings compare their layout) */
 
 /* Area-weighted statistics of the per-member time means, all variables of one grid in one call (two launches: per-block
  * partials into ws, then the partials of a variable in block order; no atomics, bit-identical from run to run).
@@ -855,7 +857,6 @@ typedef struct sdy_member_stats_args {
 int sdy_member_map_stats(const sdy_member_stats_args* args, void* stream);
 int sdy_member_map_stats_host(const sdy_member_stats_args* args);
 size_t sdy_member_stats_workspace_bytes(int nvars, int M, int n1, int HW);   /* 0 for arguments outside the supported range */
-size_t sdy_member_stats_args_bytes(void); /* sizeof(sdy_member_stats_args) of the library (the bindings compare their layout) */
 
 /* Per-degree power spectra of generated, target and error fields (no counterpart in the reference, whose only measure of
  * blurring is weighted_grad_mag_percent_diff): one launch adds ONE window of all listed variables to float64 accumulators that
@@ -906,7 +907,6 @@ typedef struct sdy_spectrum_args {
 } sdy_spectrum_args;
 int sdy_degree_power(const sdy_spectrum_args* args, void* stream);
 int sdy_degree_power_host(const sdy_spectrum_args* args);
-size_t sdy_spectrum_args_bytes(void);     /* sizeof(sdy_spectrum_args) of the library (the bindings compare their layout) */
 
 /* ---------------------------------------------------------------------------------------------------------
  * Sticky status word of the CURRENT device.  Kernels only ever set bits; the host reads (and optionally clears) it once per

@@ -221,11 +221,20 @@ class SdyCoarsenArgs(C.Structure):
     ]
 
 
-class SdyVideoArgs(C.Structure):
+class SdyWindow(C.Structure):
+    """sdy_window: embedded as `win` at the head of the three structures below (filled by `windows.fill_window`); its fields
+    also read and write as the embedding structure's own (`a.T` is `a.win.T`)."""
     _fields_ = [
         ("nvars", C.c_int), ("gen", C.c_void_p * SDY_MAX_VARS), ("target", C.c_void_p * SDY_MAX_VARS),
         ("gs0", C.c_long), ("gs1", C.c_long), ("ts1", C.c_long),
-        ("n0", C.c_int), ("n1", C.c_int), ("T", C.c_int), ("HW", C.c_int),
+        ("n0", C.c_int), ("n1", C.c_int), ("T", C.c_int),
+    ]
+
+
+class SdyVideoArgs(C.Structure):
+    _anonymous_ = ("win",)
+    _fields_ = [
+        ("win", SdyWindow), ("HW", C.c_int),
         ("t_start", C.c_int), ("n_timesteps", C.c_int),
         ("gen_mean", C.c_void_p), ("target_mean", C.c_void_p), ("gen_sq", C.c_void_p), ("target_sq", C.c_void_p),
         ("err_var", C.c_void_p), ("err_min", C.c_void_p), ("err_max", C.c_void_p),
@@ -233,20 +242,18 @@ class SdyVideoArgs(C.Structure):
 
 
 class SdyZonalArgs(C.Structure):
+    _anonymous_ = ("win",)
     _fields_ = [
-        ("nvars", C.c_int), ("gen", C.c_void_p * SDY_MAX_VARS), ("target", C.c_void_p * SDY_MAX_VARS),
-        ("gs0", C.c_long), ("gs1", C.c_long), ("ts1", C.c_long),
-        ("n0", C.c_int), ("n1", C.c_int), ("T", C.c_int), ("H", C.c_int), ("W", C.c_int),
+        ("win", SdyWindow), ("H", C.c_int), ("W", C.c_int),
         ("t_start", C.c_int), ("n_timesteps", C.c_int),
         ("gen_acc", C.c_void_p), ("target_acc", C.c_void_p),
     ]
 
 
 class SdyMemberSumArgs(C.Structure):
+    _anonymous_ = ("win",)
     _fields_ = [
-        ("nvars", C.c_int), ("gen", C.c_void_p * SDY_MAX_VARS), ("target", C.c_void_p * SDY_MAX_VARS),
-        ("gs0", C.c_long), ("gs1", C.c_long), ("ts1", C.c_long),
-        ("n0", C.c_int), ("n1", C.c_int), ("T", C.c_int), ("HW", C.c_int),
+        ("win", SdyWindow), ("HW", C.c_int),
         ("t0", C.c_int),
         ("gen_sum", C.c_void_p), ("target_sum", C.c_void_p),
     ]
@@ -278,11 +285,17 @@ class SdySpectrumArgs(C.Structure):
     ]
 
 
+# every argument structure of include/sdy_amd.h, in header order: what sdy_abi_check compares
+ABI_STRUCTS = (SdyConvArgs, SdyMlpArgs, SdyPairArgs, SdySfnoConfig, SdySfnoFwdArgs, SdyVarTable, SdyStepFinishArgs,
+               SdyDerivedArgs, SdyCorrectorArgs, SdyDryAirArgs, SdyHistArgs, SdyCoarsenArgs, SdyVideoArgs, SdyZonalArgs,
+               SdyMemberSumArgs, SdyMemberStatsArgs, SdySpectrumArgs)
+
 # name -> (restype, argtypes); every symbol include/sdy_amd.h declares
 SIGNATURES = {
     "sdy_version": (C.c_int, []),
     "sdy_error_string": (C.c_char_p, [C.c_int]),
     "sdy_abi_check": (C.c_int, [C.POINTER(C.c_size_t), C.c_int]),
+    "sdy_abi_sizes": (C.c_int, [C.POINTER(C.c_size_t), C.c_int]),
     "sdy_sht_tables_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sdy_sht_plan_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "sdy_sht_plan_create_ex": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
@@ -375,13 +388,10 @@ SIGNATURES = {
     "sdy_corrector": (C.c_int, [C.POINTER(SdyCorrectorArgs), C.c_void_p]),
     "sdy_corrector_host": (C.c_int, [C.POINTER(SdyCorrectorArgs)]),
     "sdy_corrector_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
-    "sdy_corrector_args_bytes": (C.c_size_t, []),
     "sdy_dry_air_series": (C.c_int, [C.POINTER(SdyDryAirArgs), C.c_void_p]),
     "sdy_dry_air_series_host": (C.c_int, [C.POINTER(SdyDryAirArgs)]),
     "sdy_dry_air_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
-    "sdy_dry_air_args_bytes": (C.c_size_t, []),
     "sdy_hist_add": (C.c_int, [C.POINTER(SdyHistArgs), C.c_void_p]),
-    "sdy_hist_args_bytes": (C.c_size_t, []),
     "sdy_hist_state_bytes": (C.c_size_t, [C.c_int]),
     "sdy_hist_state_unpack_host": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                              C.POINTER(C.c_int), C.POINTER(C.c_uint), C.POINTER(C.c_ulonglong)]),
@@ -391,23 +401,17 @@ SIGNATURES = {
     "sdy_hist_bins_host": (C.c_int, [C.c_void_p, C.c_long, C.c_float, C.c_float, C.c_int, C.c_void_p]),
     "sdy_time_coarsen": (C.c_int, [C.POINTER(SdyCoarsenArgs), C.c_void_p]),
     "sdy_time_coarsen_host": (C.c_int, [C.POINTER(SdyCoarsenArgs)]),
-    "sdy_coarsen_args_bytes": (C.c_size_t, []),
     "sdy_video_accumulate": (C.c_int, [C.POINTER(SdyVideoArgs), C.c_void_p]),
     "sdy_video_accumulate_host": (C.c_int, [C.POINTER(SdyVideoArgs)]),
-    "sdy_video_args_bytes": (C.c_size_t, []),
     "sdy_zonal_accumulate": (C.c_int, [C.POINTER(SdyZonalArgs), C.c_void_p]),
     "sdy_zonal_accumulate_host": (C.c_int, [C.POINTER(SdyZonalArgs)]),
-    "sdy_zonal_args_bytes": (C.c_size_t, []),
     "sdy_member_time_sum": (C.c_int, [C.POINTER(SdyMemberSumArgs), C.c_void_p]),
     "sdy_member_time_sum_host": (C.c_int, [C.POINTER(SdyMemberSumArgs)]),
-    "sdy_member_sum_args_bytes": (C.c_size_t, []),
     "sdy_member_map_stats": (C.c_int, [C.POINTER(SdyMemberStatsArgs), C.c_void_p]),
     "sdy_member_map_stats_host": (C.c_int, [C.POINTER(SdyMemberStatsArgs)]),
     "sdy_member_stats_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
-    "sdy_member_stats_args_bytes": (C.c_size_t, []),
     "sdy_degree_power": (C.c_int, [C.POINTER(SdySpectrumArgs), C.c_void_p]),
     "sdy_degree_power_host": (C.c_int, [C.POINTER(SdySpectrumArgs)]),
-    "sdy_spectrum_args_bytes": (C.c_size_t, []),
     "sdy_profile_enable": (C.c_int, [C.c_int]),
     "sdy_profile_stage_count": (C.c_int, []),
     "sdy_profile_stage_name": (C.c_char_p, [C.c_int]),
@@ -439,27 +443,13 @@ def _load():
         fn.restype = res
         fn.argtypes = args
     # the argument structures carry no size field: the bindings' layouts must be the library's (include/sdy_amd.h, sdy_abi_check)
-    structs = (SdyConvArgs, SdyMlpArgs, SdyPairArgs, SdySfnoConfig, SdySfnoFwdArgs, SdyVarTable, SdyStepFinishArgs)
-    sizes = (C.c_size_t * len(structs))(*[C.sizeof(t) for t in structs])
-    if lib.sdy_abi_check(sizes, len(structs)) != 0:
-        raise ImportError(f"{LIB_PATH}: argument structures of the bindings and of the library differ in size "
-                          f"({[C.sizeof(t) for t in structs]}): rebuild the library (make -C spherical-dyffusion_amd/csrc)")
-    if lib.sdy_hist_args_bytes() != C.sizeof(SdyHistArgs):
-        raise ImportError(f"{LIB_PATH}: sdy_hist_args of the bindings ({C.sizeof(SdyHistArgs)} bytes) and of the library "
-                          f"({lib.sdy_hist_args_bytes()}) differ: rebuild the library (make -C spherical-dyffusion_amd/csrc)")
-    if lib.sdy_coarsen_args_bytes() != C.sizeof(SdyCoarsenArgs):
-        raise ImportError(f"{LIB_PATH}: sdy_coarsen_args of the bindings ({C.sizeof(SdyCoarsenArgs)} bytes) and of the library "
-                          f"({lib.sdy_coarsen_args_bytes()}) differ: rebuild the library (make -C spherical-dyffusion_amd/csrc)")
-    for what, theirs, ours in (("sdy_corrector_args", lib.sdy_corrector_args_bytes(), C.sizeof(SdyCorrectorArgs)),
-                               ("sdy_dry_air_args", lib.sdy_dry_air_args_bytes(), C.sizeof(SdyDryAirArgs)),
-                               ("sdy_video_args", lib.sdy_video_args_bytes(), C.sizeof(SdyVideoArgs)),
-                               ("sdy_zonal_args", lib.sdy_zonal_args_bytes(), C.sizeof(SdyZonalArgs)),
-                               ("sdy_member_sum_args", lib.sdy_member_sum_args_bytes(), C.sizeof(SdyMemberSumArgs)),
-                               ("sdy_member_stats_args", lib.sdy_member_stats_args_bytes(), C.sizeof(SdyMemberStatsArgs)),
-                               ("sdy_spectrum_args", lib.sdy_spectrum_args_bytes(), C.sizeof(SdySpectrumArgs))):
-        if theirs != ours:
-            raise ImportError(f"{LIB_PATH}: {what} of the bindings ({ours} bytes) and of the library ({theirs}) differ: "
-                              "rebuild the library (make -C spherical-dyffusion_amd/csrc)")
+    ours = (C.c_size_t * len(ABI_STRUCTS))(*[C.sizeof(t) for t in ABI_STRUCTS])
+    if lib.sdy_abi_check(ours, len(ours)) != 0:
+        theirs = (C.c_size_t * len(ours))()
+        theirs = list(theirs) if lib.sdy_abi_sizes(theirs, len(theirs)) == 0 else "another number of structures"
+        raise ImportError(f"{LIB_PATH}: argument structures of the bindings and of the library differ: "
+                          f"{[t.__name__ for t in ABI_STRUCTS]} are {list(ours)} bytes in the bindings and {theirs} in the "
+                          "library: rebuild the library (make -C spherical-dyffusion_amd/csrc)")
     return lib
 
 

@@ -34,12 +34,23 @@ static float h3_pack_host(std::vector<_Float16>& buf, int nb, int rows, int K, i
 }
 
 
-extern "C" int sdy_version(void) { return 101; }
+extern "C" int sdy_version(void) { return 102; }
+
+extern "C" int sdy_abi_sizes(size_t* sizes, int n) {
+  const size_t mine[SDY_ABI_STRUCTS] = {
+      sizeof(sdy_conv_args),      sizeof(sdy_mlp_args),      sizeof(sdy_pair_args),        sizeof(sdy_sfno_config),
+      sizeof(sdy_sfno_fwd_args),  sizeof(sdy_var_table),     sizeof(sdy_step_finish_args), sizeof(sdy_derived_args),
+      sizeof(sdy_corrector_args), sizeof(sdy_dry_air_args),  sizeof(sdy_hist_args),        sizeof(sdy_coarsen_args),
+      sizeof(sdy_video_args),     sizeof(sdy_zonal_args),    sizeof(sdy_member_sum_args),  sizeof(sdy_member_stats_args),
+      sizeof(sdy_spectrum_args)};
+  if (!sizes || n != SDY_ABI_STRUCTS) return SDY_ERR_ARG;
+  for (int i = 0; i < n; ++i) sizes[i] = mine[i];
+  return SDY_OK;
+}
 
 extern "C" int sdy_abi_check(const size_t* sizes, int n) {
-  const size_t mine[SDY_ABI_STRUCTS] = {sizeof(sdy_conv_args), sizeof(sdy_mlp_args), sizeof(sdy_pair_args), sizeof(sdy_sfno_config),
-                                        sizeof(sdy_sfno_fwd_args), sizeof(sdy_var_table), sizeof(sdy_step_finish_args)};
-  if (!sizes || n != SDY_ABI_STRUCTS) return SDY_ERR_ARG;
+  size_t mine[SDY_ABI_STRUCTS];
+  if (!sizes || sdy_abi_sizes(mine, n) != SDY_OK) return SDY_ERR_ARG;
   for (int i = 0; i < n; ++i)
     if (sizes[i] != mine[i]) return SDY_ERR_ARG;
   return SDY_OK;

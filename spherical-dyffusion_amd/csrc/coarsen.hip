@@ -5,6 +5,7 @@
 // a group is coarsen_mean.h.
 #include "common.h"
 #include "coarsen_mean.h"
+#include "window.h"
 
 namespace {
 
@@ -101,8 +102,6 @@ int check_args(const sdy_coarsen_args* a, int* T_out) {
 
 }  // namespace
 
-extern "C" size_t sdy_coarsen_args_bytes(void) { return sizeof(sdy_coarsen_args); }
-
 extern "C" int sdy_time_coarsen_host(const sdy_coarsen_args* a) {
   int T_out = 0;
   SDY_TRY(check_args(a, &T_out));
@@ -131,9 +130,7 @@ extern "C" int sdy_time_coarsen(const sdy_coarsen_args* a, void* stream) {
   for (int v = 0; v < a->nvars; ++v)
     vec = vec && (((uintptr_t)a->data[v] | (uintptr_t)a->out[v]) & 15) == 0 && (a->s0[v] & 3) == 0 && (a->s1[v] & 3) == 0;
   const unsigned long n_items = (unsigned long)a->n0 * a->n1 * T_out * (vec ? a->HW / 4 : a->HW);
-  const unsigned long blocks = (n_items + kItemsPerBlock - 1) / kItemsPerBlock;
-  const unsigned long cap = kBlocksPerLaunch / a->nvars > 32 ? kBlocksPerLaunch / a->nvars : 32;
-  const dim3 grid((unsigned)(blocks < cap ? blocks : cap), a->nvars);
+  const dim3 grid(sdy_grid_cap((n_items + kItemsPerBlock - 1) / kItemsPerBlock, a->nvars, kBlocksPerLaunch, 32), a->nvars);
   if (vec)
     hipLaunchKernelGGL(time_coarsen_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, *a, T_out, n_items);
   else

@@ -163,8 +163,6 @@ int check_args(const sdy_dry_air_args* a, bool need_ws, sdy_dry_air_args* r) {
 
 }  // namespace
 
-extern "C" size_t sdy_dry_air_args_bytes(void) { return sizeof(sdy_dry_air_args); }
-
 extern "C" size_t sdy_dry_air_workspace_bytes(int B, int T, int HW) {
   if (B < 1 || T < 1 || HW < 1) return 0;
   return (size_t)B * T * n_chunks(HW) * 2 * sizeof(double);

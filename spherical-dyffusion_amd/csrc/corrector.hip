@@ -276,8 +276,6 @@ int check_args(const sdy_corrector_args* a, bool need_ws, sdy_corrector_args* r,
 
 }  // namespace
 
-extern "C" size_t sdy_corrector_args_bytes(void) { return sizeof(sdy_corrector_args); }
-
 extern "C" size_t sdy_corrector_workspace_bytes(int B, int HW) {
   if (B < 1 || HW < 1) return 0;
   return partial_doubles(B, HW) * sizeof(double) + (size_t)B * sizeof(sdy_corr_scalars);

@@ -4,18 +4,13 @@
 // there are no atomics and no LDS.  The arithmetic of a grid point is field_stats.h.
 #include "common.h"
 #include "field_stats.h"
+#include "window.h"
 
 namespace {
 
 constexpr int kBlocksPerLaunch = 4096;  // over all variables; a variable with more work strides over its items
+constexpr int kMinBlocksPerVar = 32;
 constexpr int kRowsInFlight = 4;        // independent row loads a thread issues before it consumes the first
-
-template <int W>
-using Vec = std::conditional_t<W == 4, f32x4, float>;
-template <int W>
-__device__ __forceinline__ Vec<W> ld(const float* p) { return *reinterpret_cast<const Vec<W>*>(p); }
-__device__ __forceinline__ float comp(float v, int) { return v; }
-__device__ __forceinline__ float comp(f32x4 v, int c) { return v[c]; }
 
 // Work item idx of variable blockIdx.y: W grid points (4 or 1) at point W * q of window time t, idx = t * (HW / W) + q, so
 // consecutive lanes touch consecutive addresses of every row and of the accumulators.  idx < T * HW <= 2^30 (entry point).
@@ -23,13 +18,13 @@ template <int W, bool EXT>
 __global__ __launch_bounds__(256) void video_kernel(const sdy_video_args a, unsigned n_items) {
   const int v = blockIdx.y;
   const unsigned per_time = (unsigned)(a.HW / W);
-  const long HW = a.HW, gs0 = a.gs0, gs1 = a.gs1, ts1 = a.ts1;
-  const int n0 = a.n0, n1 = a.n1;
+  const long HW = a.HW, gs0 = a.win.gs0, gs1 = a.win.gs1, ts1 = a.win.ts1;
+  const int n0 = a.win.n0, n1 = a.win.n1;
   for (unsigned idx = blockIdx.x * 256u + threadIdx.x; idx < n_items; idx += gridDim.x * 256u) {
     const unsigned t = idx / per_time, q = idx - t * per_time;
     const long in_row = (long)t * HW + (long)q * W;          // < T * HW
-    const float* g = a.gen[v] + in_row;
-    const float* tg = a.target[v] + in_row;
+    const float* g = a.win.gen[v] + in_row;
+    const float* tg = a.win.target[v] + in_row;
     sdy_fs_point<EXT> st[W];
 #pragma unroll
     for (int c = 0; c < W; ++c) sdy_fs_init(st[c]);
@@ -94,9 +89,9 @@ template <int W4>
 __global__ __launch_bounds__(256) void zonal_kernel(const sdy_zonal_args a, int G, unsigned long n_rows) {
   const int v = blockIdx.y;
   const int lig = threadIdx.x & (G - 1), group = threadIdx.x / G, rows_per_block = 256 / G;
-  const int units = a.W / W4, n0 = a.n0;
-  const unsigned long TH = (unsigned long)a.T * a.H;
-  const long gs0 = a.gs0;
+  const int units = a.W / W4, n0 = a.win.n0;
+  const unsigned long TH = (unsigned long)a.win.T * a.H;
+  const long gs0 = a.win.gs0;
   for (unsigned long base = (unsigned long)blockIdx.x * rows_per_block; base < n_rows;
        base += (unsigned long)gridDim.x * rows_per_block) {
     const unsigned long row = base + group;
@@ -106,8 +101,8 @@ __global__ __launch_bounds__(256) void zonal_kernel(const sdy_zonal_args a, int 
     if (active) {
       s = row / TH;                       // < n1
       rem = row - s * TH;                 // t * H + lat < T * H
-      const float* g = a.gen[v] + (long)s * a.gs1 + (long)rem * a.W;
-      const float* tg = a.target[v] + (long)s * a.ts1 + (long)rem * a.W;
+      const float* g = a.win.gen[v] + (long)s * a.win.gs1 + (long)rem * a.W;
+      const float* tg = a.win.target[v] + (long)s * a.win.ts1 + (long)rem * a.W;
       for (int u = lig; u < units; u += G) {
         const Vec<W4> tv = ld<W4>(tg + u * W4);
 #pragma unroll
@@ -137,34 +132,25 @@ __global__ __launch_bounds__(256) void zonal_kernel(const sdy_zonal_args a, int 
     if (active && lig == 0) {
       const unsigned long t = rem / (unsigned)a.H, lat = rem - t * (unsigned)a.H;
       // accumulator element: variable v, sample s < n1, time t_start + t < n_timesteps (entry point), latitude lat < H
-      const long at = (((long)v * a.n1 + (long)s) * a.n_timesteps + (a.t_start + (long)t)) * a.H + (long)lat;
+      const long at = (((long)v * a.win.n1 + (long)s) * a.n_timesteps + (a.t_start + (long)t)) * a.H + (long)lat;
       a.gen_acc[at] += sdy_fs_zonal_mean(gsum, n0, a.W);
       a.target_acc[at] += sdy_fs_zonal_mean(tsum, 1, a.W);
     }
   }
 }
 
-// everything that bounds an address, for the device and the host entry points alike
-int check_common(int nvars, const float* const* gen, const float* const* target, long gs0, long gs1, long ts1, int n0, int n1,
-                 int T, long plane, int t_start, int n_timesteps) {
-  if (nvars < 1 || nvars > SDY_MAX_VARS) return SDY_ERR_ARG;
-  if (n0 < 1 || n1 < 1 || T < 1 || plane < 1 || n_timesteps < 1) return SDY_ERR_ARG;
-  if (gs0 < 0 || gs1 < 0 || ts1 < 0) return SDY_ERR_ARG;
-  // the time offset into the accumulators: window times t_start .. t_start + T - 1 must all exist (in 64 bits: no wrap)
-  if (t_start < 0 || (long)t_start + (long)T > (long)n_timesteps) return SDY_ERR_ARG;
-  for (int v = 0; v < nvars; ++v)
-    if (!gen[v] || !target[v]) return SDY_ERR_ARG;
-  return SDY_OK;
+// the time offset into the accumulators: window times t_start .. t_start + T - 1 must all exist (in 64 bits: no wrap)
+bool times_fit(const sdy_window& w, int t_start, int n_timesteps) {
+  return n_timesteps >= 1 && t_start >= 0 && (long)t_start + (long)w.T <= (long)n_timesteps;
 }
 
+// the window's own checks are sdy_window_check's; here what bounds an accumulator address
 int check_video(const sdy_video_args* a) {
   if (!a) return SDY_ERR_ARG;
-  if (a->HW < 1) return SDY_ERR_ARG;
-  SDY_TRY(check_common(a->nvars, a->gen, a->target, a->gs0, a->gs1, a->ts1, a->n0, a->n1, a->T, a->HW, a->t_start,
-                       a->n_timesteps));
+  if (!times_fit(a->win, a->t_start, a->n_timesteps)) return SDY_ERR_ARG;
   if (!a->gen_mean || !a->target_mean) return SDY_ERR_ARG;
-  // 32-bit work items within a variable, 32-bit row numbers; flat accumulator indices are 64-bit
-  if ((long)a->T * a->HW > (1L << 30) || (long)a->n0 * a->n1 >= (1L << 31)) return SDY_ERR_UNSUPPORTED;
+  SDY_TRY(sdy_window_check(&a->win, a->HW));
+  // flat accumulator indices are 64-bit
   if ((long)a->n_timesteps * a->HW >= (1L << 40)) return SDY_ERR_UNSUPPORTED;
   return SDY_OK;
 }
@@ -172,13 +158,12 @@ int check_video(const sdy_video_args* a) {
 int check_zonal(const sdy_zonal_args* a) {
   if (!a) return SDY_ERR_ARG;
   if (a->H < 1 || a->W < 1) return SDY_ERR_ARG;
-  SDY_TRY(check_common(a->nvars, a->gen, a->target, a->gs0, a->gs1, a->ts1, a->n0, a->n1, a->T, (long)a->H * a->W, a->t_start,
-                       a->n_timesteps));
+  if (!times_fit(a->win, a->t_start, a->n_timesteps)) return SDY_ERR_ARG;
   if (!a->gen_acc || !a->target_acc) return SDY_ERR_ARG;
-  if ((long)a->T * a->H * a->W > (1L << 30) || (long)a->n0 * a->n1 >= (1L << 31)) return SDY_ERR_UNSUPPORTED;
+  SDY_TRY(sdy_window_check(&a->win, (long)a->H * a->W));
   // 64-bit flat accumulator indices: one sample's (n_timesteps, H) and a variable's n1 of them stay far inside the range
   if ((long)a->n_timesteps * a->H >= (1L << 40)) return SDY_ERR_UNSUPPORTED;
-  if ((long)a->n1 * ((long)a->n_timesteps * a->H) >= (1L << 50)) return SDY_ERR_UNSUPPORTED;
+  if ((long)a->win.n1 * ((long)a->n_timesteps * a->H) >= (1L << 50)) return SDY_ERR_UNSUPPORTED;
   return SDY_OK;
 }
 
@@ -186,29 +171,27 @@ bool extended(const sdy_video_args* a) { return a->gen_sq || a->target_sq || a->
 
 template <bool EXT>
 void video_host(const sdy_video_args* a) {
+  const sdy_window& w = a->win;
   const long HW = a->HW;
-  for (int v = 0; v < a->nvars; ++v)
-    for (int t = 0; t < a->T; ++t)
+  for (int v = 0; v < w.nvars; ++v)
+    for (int t = 0; t < w.T; ++t)
       for (long p = 0; p < HW; ++p) {
-        const float* g = a->gen[v] + t * HW + p;
-        const float* tg = a->target[v] + t * HW + p;
+        const float* g = w.gen[v] + t * HW + p;
+        const float* tg = w.target[v] + t * HW + p;
         sdy_fs_point<EXT> st;
         sdy_fs_init(st);
-        for (long i1 = 0; i1 < a->n1; ++i1) {
-          const float tv = tg[i1 * a->ts1];
+        for (long i1 = 0; i1 < w.n1; ++i1) {
+          const float tv = tg[i1 * w.ts1];
           sdy_fs_add_target(st, tv);
-          for (long i0 = 0; i0 < a->n0; ++i0) sdy_fs_add_gen(st, g[i0 * a->gs0 + i1 * a->gs1], tv);
+          for (long i0 = 0; i0 < w.n0; ++i0) sdy_fs_add_gen(st, g[i0 * w.gs0 + i1 * w.gs1], tv);
         }
         const long at = ((long)v * a->n_timesteps + (a->t_start + t)) * HW + p;
-        sdy_fs_store(st, at, a->n0 * a->n1, a->n1, a->gen_mean, a->target_mean, a->gen_sq, a->target_sq, a->err_var,
-                     a->err_min, a->err_max);
+        sdy_fs_store(st, at, w.n0 * w.n1, w.n1, a->gen_mean, a->target_mean, a->gen_sq, a->target_sq, a->err_var, a->err_min,
+                     a->err_max);
       }
 }
 
 }  // namespace
-
-extern "C" size_t sdy_video_args_bytes(void) { return sizeof(sdy_video_args); }
-extern "C" size_t sdy_zonal_args_bytes(void) { return sizeof(sdy_zonal_args); }
 
 extern "C" int sdy_video_accumulate_host(const sdy_video_args* a) {
   SDY_TRY(check_video(a));
@@ -221,12 +204,9 @@ extern "C" int sdy_video_accumulate_host(const sdy_video_args* a) {
 
 extern "C" int sdy_video_accumulate(const sdy_video_args* a, void* stream) {
   SDY_TRY(check_video(a));
-  bool vec = (a->HW & 3) == 0 && ((a->gs0 | a->gs1 | a->ts1) & 3) == 0;
-  for (int v = 0; v < a->nvars; ++v) vec = vec && (((uintptr_t)a->gen[v] | (uintptr_t)a->target[v]) & 15) == 0;
-  const unsigned n_items = (unsigned)((long)a->T * (vec ? a->HW / 4 : a->HW));
-  const unsigned blocks = (n_items + 255u) / 256u;
-  const unsigned cap = kBlocksPerLaunch / a->nvars > 32 ? kBlocksPerLaunch / a->nvars : 32;
-  const dim3 grid(blocks < cap ? blocks : cap, a->nvars);
+  const bool vec = sdy_window_vec4(&a->win, a->HW);
+  const unsigned n_items = (unsigned)((long)a->win.T * (vec ? a->HW / 4 : a->HW));
+  const dim3 grid(sdy_grid_cap((n_items + 255u) / 256u, a->win.nvars, kBlocksPerLaunch, kMinBlocksPerVar), a->win.nvars);
   const hipStream_t s = (hipStream_t)stream;
   if (extended(a)) {
     if (vec)
@@ -244,19 +224,20 @@ extern "C" int sdy_video_accumulate(const sdy_video_args* a, void* stream) {
 
 extern "C" int sdy_zonal_accumulate_host(const sdy_zonal_args* a) {
   SDY_TRY(check_zonal(a));
-  const long W = a->W, TH = (long)a->T * a->H;
-  for (int v = 0; v < a->nvars; ++v)
-    for (long s = 0; s < a->n1; ++s)
+  const sdy_window& w = a->win;
+  const long W = a->W, TH = (long)w.T * a->H;
+  for (int v = 0; v < w.nvars; ++v)
+    for (long s = 0; s < w.n1; ++s)
       for (long rem = 0; rem < TH; ++rem) {
-        const float* g = a->gen[v] + s * a->gs1 + rem * W;
-        const float* tg = a->target[v] + s * a->ts1 + rem * W;
+        const float* g = w.gen[v] + s * w.gs1 + rem * W;
+        const float* tg = w.target[v] + s * w.ts1 + rem * W;
         double gsum = 0.0, tsum = 0.0;
         for (long p = 0; p < W; ++p) tsum += (double)tg[p];
-        for (long i0 = 0; i0 < a->n0; ++i0)
-          for (long p = 0; p < W; ++p) gsum += (double)g[i0 * a->gs0 + p];
+        for (long i0 = 0; i0 < w.n0; ++i0)
+          for (long p = 0; p < W; ++p) gsum += (double)g[i0 * w.gs0 + p];
         const long t = rem / a->H, lat = rem - t * a->H;
-        const long at = (((long)v * a->n1 + s) * a->n_timesteps + (a->t_start + t)) * a->H + lat;
-        a->gen_acc[at] += sdy_fs_zonal_mean(gsum, a->n0, a->W);
+        const long at = (((long)v * w.n1 + s) * a->n_timesteps + (a->t_start + t)) * a->H + lat;
+        a->gen_acc[at] += sdy_fs_zonal_mean(gsum, w.n0, a->W);
         a->target_acc[at] += sdy_fs_zonal_mean(tsum, 1, a->W);
       }
   return SDY_OK;
@@ -264,16 +245,14 @@ extern "C" int sdy_zonal_accumulate_host(const sdy_zonal_args* a) {
 
 extern "C" int sdy_zonal_accumulate(const sdy_zonal_args* a, void* stream) {
   SDY_TRY(check_zonal(a));
-  bool vec = (a->W & 3) == 0 && ((a->gs0 | a->gs1 | a->ts1) & 3) == 0;
-  for (int v = 0; v < a->nvars; ++v) vec = vec && (((uintptr_t)a->gen[v] | (uintptr_t)a->target[v]) & 15) == 0;
+  const bool vec = sdy_window_vec4(&a->win, a->W);
   const int units = vec ? a->W / 4 : a->W;
   int G = 1;                                       // lanes per latitude row: one wave, or a power-of-two part of one
   while (G < 64 && G < units) G <<= 1;
-  const unsigned long n_rows = (unsigned long)a->n1 * a->T * a->H;
+  const unsigned long n_rows = (unsigned long)a->win.n1 * a->win.T * a->H;
   const unsigned long rows_per_block = 256 / G;
-  const unsigned long blocks = (n_rows + rows_per_block - 1) / rows_per_block;
-  const unsigned long cap = kBlocksPerLaunch / a->nvars > 32 ? kBlocksPerLaunch / a->nvars : 32;
-  const dim3 grid((unsigned)(blocks < cap ? blocks : cap), a->nvars);
+  const dim3 grid(sdy_grid_cap((n_rows + rows_per_block - 1) / rows_per_block, a->win.nvars, kBlocksPerLaunch, kMinBlocksPerVar),
+                  a->win.nvars);
   if (vec)
     hipLaunchKernelGGL(zonal_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, *a, G, n_rows);
   else

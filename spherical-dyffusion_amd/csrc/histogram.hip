@@ -198,7 +198,6 @@ void chunking(int len, int cap, int* per_row, int* chunk) {
 
 }  // namespace
 
-extern "C" size_t sdy_hist_args_bytes(void) { return sizeof(sdy_hist_args); }
 extern "C" size_t sdy_hist_state_bytes(int nvars) { return nvars > 0 ? (size_t)nvars * kStateWords * 4 : 0; }
 
 extern "C" int sdy_hist_state_unpack_host(const void* state_host, int v, float* start, float* stop, int* initialised,

@@ -12,6 +12,7 @@
 
 #include "common.h"
 #include "member_mean.h"
+#include "window.h"
 
 namespace {
 
@@ -22,13 +23,6 @@ constexpr int kMinBlocksPerVar = 32;
 constexpr int kTimesInFlight = 8;       // independent time loads a thread issues before it consumes the first
 constexpr int kMaxMembers = SDY_MEMBER_STATS_MAX_MEMBERS;
 
-template <int W>
-using Vec = std::conditional_t<W == 4, f32x4, float>;
-template <int W>
-__device__ __forceinline__ Vec<W> ld(const float* p) { return *reinterpret_cast<const Vec<W>*>(p); }
-__device__ __forceinline__ float comp(float v, int) { return v; }
-__device__ __forceinline__ float comp(f32x4 v, int c) { return v[c]; }
-
 // Work item idx of variable blockIdx.y: W grid points (4 or 1) at point W * q of row r, idx = r * (HW / W) + q; rows
 // 0 .. n0*n1 - 1 are the generated rows (member i0 = r / n1, sample i1 = r % n1), rows n0*n1 .. n0*n1 + n1 - 1 the target's.
 // Consecutive lanes touch consecutive addresses of every time and of the accumulators.  Every index is bounded by the entry
@@ -37,22 +31,22 @@ template <int W>
 __global__ __launch_bounds__(kThreads) void member_sum_kernel(const sdy_member_sum_args a, unsigned long n_items) {
   const int v = blockIdx.y;
   const unsigned long per_row = (unsigned long)(a.HW / W);
-  const unsigned long gen_rows = (unsigned long)a.n0 * (unsigned long)a.n1;
+  const unsigned long gen_rows = (unsigned long)a.win.n0 * (unsigned long)a.win.n1;
   const long HW = a.HW;
-  const int T = a.T;
+  const int T = a.win.T;
   for (unsigned long idx = (unsigned long)blockIdx.x * kThreads + threadIdx.x; idx < n_items;
        idx += (unsigned long)gridDim.x * kThreads) {
     const unsigned long r = idx / per_row, q = idx - r * per_row;
     const float* src;
     double* acc;
     if (r < gen_rows) {
-      const unsigned long i0 = r / (unsigned)a.n1, i1 = r - i0 * (unsigned)a.n1;
-      src = a.gen[v] + (long)i0 * a.gs0 + (long)i1 * a.gs1;
+      const unsigned long i0 = r / (unsigned)a.win.n1, i1 = r - i0 * (unsigned)a.win.n1;
+      src = a.win.gen[v] + (long)i0 * a.win.gs0 + (long)i1 * a.win.gs1;
       acc = a.gen_sum + ((long)v * (long)gen_rows + (long)r) * HW;
     } else {
       const unsigned long i1 = r - gen_rows;
-      src = a.target[v] + (long)i1 * a.ts1;
-      acc = a.target_sum + ((long)v * a.n1 + (long)i1) * HW;
+      src = a.win.target[v] + (long)i1 * a.win.ts1;
+      acc = a.target_sum + ((long)v * a.win.n1 + (long)i1) * HW;
     }
     src += (long)q * W;
     acc += (long)q * W;
@@ -129,20 +123,15 @@ __global__ __launch_bounds__(kThreads) void member_combine_kernel(const double* 
 
 long n_chunks(long n) { return (n + kThreads - 1) / kThreads; }
 
-// everything that bounds an address, for the device and the host entry point alike
+// the window's own checks are sdy_window_check's; here the time offset and what bounds an accumulator address
 int check_sum(const sdy_member_sum_args* a) {
   if (!a) return SDY_ERR_ARG;
-  if (a->nvars < 1 || a->nvars > SDY_MAX_VARS) return SDY_ERR_ARG;
-  if (a->n0 < 1 || a->n1 < 1 || a->T < 1 || a->HW < 1) return SDY_ERR_ARG;
-  if (a->gs0 < 0 || a->gs1 < 0 || a->ts1 < 0) return SDY_ERR_ARG;
-  if (a->t0 < 0 || a->t0 >= a->T) return SDY_ERR_ARG;
-  for (int v = 0; v < a->nvars; ++v)
-    if (!a->gen[v] || !a->target[v]) return SDY_ERR_ARG;
+  if (a->t0 < 0 || a->t0 >= a->win.T) return SDY_ERR_ARG;
   if (!a->gen_sum || !a->target_sum || (((uintptr_t)a->gen_sum | (uintptr_t)a->target_sum) & 7)) return SDY_ERR_ARG;
-  if ((long)a->T * a->HW > (1L << 30) || (long)a->n0 * a->n1 >= (1L << 31)) return SDY_ERR_UNSUPPORTED;
+  SDY_TRY(sdy_window_check(&a->win, a->HW));
   // 64-bit flat accumulator indices: nvars <= 96 < 2^7, n0 * n1 < 2^31, HW <= 2^30 -- the product can leave 2^50
-  const long per_var = (long)a->n0 * a->n1 * a->HW;      // < 2^61
-  if (per_var >= (1L << 50) || (long)a->nvars * per_var >= (1L << 50)) return SDY_ERR_UNSUPPORTED;
+  const long per_var = (long)a->win.n0 * a->win.n1 * a->HW;      // < 2^61
+  if (per_var >= (1L << 50) || (long)a->win.nvars * per_var >= (1L << 50)) return SDY_ERR_UNSUPPORTED;
   return SDY_OK;
 }
 
@@ -163,9 +152,6 @@ int check_stats(const sdy_member_stats_args* a, bool need_ws) {
 
 }  // namespace
 
-extern "C" size_t sdy_member_sum_args_bytes(void) { return sizeof(sdy_member_sum_args); }
-extern "C" size_t sdy_member_stats_args_bytes(void) { return sizeof(sdy_member_stats_args); }
-
 extern "C" size_t sdy_member_stats_workspace_bytes(int nvars, int M, int n1, int HW) {
   if (nvars < 1 || M < 1 || M > kMaxMembers || n1 < 1 || HW < 1) return 0;
   return (size_t)nvars * (size_t)n_chunks((long)n1 * HW) * sdy_mm_slots(M) * sizeof(double);
@@ -173,32 +159,31 @@ extern "C" size_t sdy_member_stats_workspace_bytes(int nvars, int M, int n1, int
 
 extern "C" int sdy_member_time_sum_host(const sdy_member_sum_args* a) {
   SDY_TRY(check_sum(a));
-  const long HW = a->HW, rows = (long)a->n0 * a->n1;
+  const sdy_window& w = a->win;
+  const long HW = a->HW, rows = (long)w.n0 * w.n1;
   auto add_row = [&](const float* src, double* acc) {
     for (long p = 0; p < HW; ++p) {
       double s = 0.0;
-      for (int t = a->t0; t < a->T; ++t) s = sdy_mm_add(s, src[(long)t * HW + p]);
+      for (int t = a->t0; t < w.T; ++t) s = sdy_mm_add(s, src[(long)t * HW + p]);
       acc[p] = sdy_mm_fold(acc[p], s);
     }
   };
-  for (int v = 0; v < a->nvars; ++v) {
-    for (long i0 = 0; i0 < a->n0; ++i0)
-      for (long i1 = 0; i1 < a->n1; ++i1)
-        add_row(a->gen[v] + i0 * a->gs0 + i1 * a->gs1, a->gen_sum + ((long)v * rows + i0 * a->n1 + i1) * HW);
-    for (long i1 = 0; i1 < a->n1; ++i1) add_row(a->target[v] + i1 * a->ts1, a->target_sum + ((long)v * a->n1 + i1) * HW);
+  for (int v = 0; v < w.nvars; ++v) {
+    for (long i0 = 0; i0 < w.n0; ++i0)
+      for (long i1 = 0; i1 < w.n1; ++i1)
+        add_row(w.gen[v] + i0 * w.gs0 + i1 * w.gs1, a->gen_sum + ((long)v * rows + i0 * w.n1 + i1) * HW);
+    for (long i1 = 0; i1 < w.n1; ++i1) add_row(w.target[v] + i1 * w.ts1, a->target_sum + ((long)v * w.n1 + i1) * HW);
   }
   return SDY_OK;
 }
 
 extern "C" int sdy_member_time_sum(const sdy_member_sum_args* a, void* stream) {
   SDY_TRY(check_sum(a));
-  bool vec = (a->HW & 3) == 0 && ((a->gs0 | a->gs1 | a->ts1) & 3) == 0;
-  for (int v = 0; v < a->nvars; ++v) vec = vec && (((uintptr_t)a->gen[v] | (uintptr_t)a->target[v]) & 15) == 0;
-  const unsigned long rows = (unsigned long)a->n0 * a->n1 + a->n1;
+  const bool vec = sdy_window_vec4(&a->win, a->HW);
+  const unsigned long rows = (unsigned long)a->win.n0 * a->win.n1 + a->win.n1;
   const unsigned long n_items = rows * (unsigned long)(vec ? a->HW / 4 : a->HW);
-  const unsigned long blocks = (n_items + kThreads - 1) / kThreads;
-  const unsigned long cap = kBlocksPerLaunch / a->nvars > kMinBlocksPerVar ? kBlocksPerLaunch / a->nvars : kMinBlocksPerVar;
-  const dim3 grid((unsigned)(blocks < cap ? blocks : cap), a->nvars);
+  const dim3 grid(sdy_grid_cap((n_items + kThreads - 1) / kThreads, a->win.nvars, kBlocksPerLaunch, kMinBlocksPerVar),
+                  a->win.nvars);
   if (vec)
     hipLaunchKernelGGL(member_sum_kernel<4>, grid, dim3(kThreads), 0, (hipStream_t)stream, *a, n_items);
   else

@@ -153,8 +153,6 @@ void launch(const sdy_spectrum_args* a, hipStream_t s) {
 
 }  // namespace
 
-extern "C" size_t sdy_spectrum_args_bytes(void) { return sizeof(sdy_spectrum_args); }
-
 extern "C" int sdy_degree_power_host(const sdy_spectrum_args* a) {
   SDY_TRY(check_spectrum(a));
   const long Fg = a->gen_fields, Ft = a->target_fields;

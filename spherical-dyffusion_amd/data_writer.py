@@ -40,8 +40,9 @@ from typing import Dict, List, Mapping, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from ._lib import SDY_MAX_VARS, SdyCoarsenArgs, check, current_stream, lib, ptr
-from .histogram import HistogramDataWriter, _strided_layout
+from ._lib import SdyCoarsenArgs, check, current_stream, lib, ptr
+from .histogram import HistogramDataWriter
+from .windows import runs, strided_layout
 
 TIME_DIM_NAME = "time"
 
@@ -68,8 +69,8 @@ def coarsen_tensors(tensors: Sequence[torch.Tensor], t_first: int, factor: int) 
         return [], None
     for v in tensors:
         _require_device(v)
-    lay = [_strided_layout(v) for v in tensors]
-    device = lay[0][0].device
+    lay = [strided_layout(v) for v in tensors]
+    device = tensors[0].device
     offsets, total = [], 0
     for (v, n0, n1, _, _, T, HW), orig in zip(lay, tensors):      # every call is checked before the first one is enqueued
         if v.device != device:
@@ -86,21 +87,15 @@ def coarsen_tensors(tensors: Sequence[torch.Tensor], t_first: int, factor: int) 
     buf = torch.empty(total, dtype=torch.float32, device=device)
     outs = [buf[o:o + n0 * n1 * t_out * HW].view(*orig.shape[:-3], t_out, *orig.shape[-2:])
             for (o, t_out), (_, n0, n1, _, _, _, HW), orig in zip(offsets, lay, tensors)]
-    first = 0
-    while first < len(lay):
-        shape = lay[first][1:3] + lay[first][5:]
-        last = first + 1
-        while last < len(lay) and last - first < SDY_MAX_VARS and lay[last][1:3] + lay[last][5:] == shape:
-            last += 1
+    for first, last in runs(lay, lambda l: l[1:3] + l[5:]):      # consecutive tensors of one shape share a call
         a = SdyCoarsenArgs()
         a.nvars = last - first
         for j in range(first, last):
             v, _, _, s0, s1, _, _ = lay[j]
             a.data[j - first], a.s0[j - first], a.s1[j - first], a.out[j - first] = ptr(v), s0, s1, ptr(outs[j])
-        a.n0, a.n1, a.T, a.HW = shape
+        _, a.n0, a.n1, _, _, a.T, a.HW = lay[first]
         a.t_first, a.factor = int(t_first), int(factor)
         _launch(a, device)
-        first = last
     return outs, buf
 
 

@@ -37,7 +37,8 @@ from typing import Dict, List, Mapping, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from ._lib import SDY_HIST_FLAG_RANGE, SDY_HIST_MAX_BINS, SDY_MAX_VARS, SdyError, SdyHistArgs, check, current_stream, lib, ptr
+from ._lib import SDY_HIST_FLAG_RANGE, SDY_HIST_MAX_BINS, SdyError, SdyHistArgs, check, current_stream, lib, ptr
+from .windows import runs, strided_layout
 
 
 def bin_edges(start: float, stop: float, n_bins: int) -> np.ndarray:
@@ -52,26 +53,7 @@ def _layout(v: torch.Tensor) -> Tuple[torch.Tensor, int, int, int, int, int, int
     """-> (tensor to keep alive, n0, n1, s0, s1, T, HW): element (i0, i1, t, p) at data_ptr + i0*s0 + i1*s1 + t*HW + p."""
     if not v.is_cuda:
         raise RuntimeError("sdy_amd histograms run on the GPU only (no CPU fallback)")
-    return _strided_layout(v)
-
-
-def _strided_layout(v: torch.Tensor) -> Tuple[torch.Tensor, int, int, int, int, int, int]:
-    """`_layout` without the device check (shared with `sdy_amd.data_writer`, whose callers check the device themselves)."""
-    if v.dim() < 3:
-        raise ValueError(f"expected (..., time, lat, lon), got {tuple(v.shape)}")
-    v = v.to(torch.float32)
-    T, H, W = v.shape[-3:]
-    lead = tuple(v.shape[:-3])
-    inner = all(n == 1 or s == want for n, s, want in zip((T, H, W), v.stride()[-3:], (H * W, W, 1)))
-    if not inner or len(lead) > 2 or any(s < 0 for s in v.stride()[:-3]):
-        v = v.contiguous().view(-1, T, H, W)
-        lead = (v.shape[0],)
-    st = v.stride()
-    if len(lead) == 2:
-        return v, lead[0], lead[1], st[0], st[1], T, H * W
-    if len(lead) == 1:
-        return v, 1, lead[0], 0, st[0], T, H * W
-    return v, 1, 1, 0, 0, T, H * W
+    return strided_layout(v)
 
 
 class _HistogramSet:
@@ -103,23 +85,17 @@ class _HistogramSet:
                 raise ValueError(f"times {i_time_start}..{i_time_start + T - 1} outside the histogram's {self.n_times}")
             if min(n0, n1, T, HW) < 1:
                 raise ValueError("empty tensor")
-        first = 0
-        while first < len(lay):
-            shape = lay[first][1:3] + lay[first][5:]
-            last = first + 1
-            while last < len(lay) and last - first < SDY_MAX_VARS and lay[last][1:3] + lay[last][5:] == shape:
-                last += 1
+        for first, last in runs(lay, lambda l: l[1:3] + l[5:]):
             a = SdyHistArgs()
             a.nvars = last - first
             for j in range(first, last):
                 v, _, _, s0, s1, _, _ = lay[j]
                 a.data[j - first], a.s0[j - first], a.s1[j - first] = ptr(v), s0, s1
-            a.n0, a.n1, a.T, a.HW = shape
+            _, a.n0, a.n1, _, _, a.T, a.HW = lay[first]
             a.t_start, a.n_times, a.n_bins = i_time_start, self.n_times, self.n_bins
             a.state, a.counts = ptr(self.state[first]), ptr(self.counts[first])
             with torch.cuda.device(self.device):
                 check(lib.sdy_hist_add(C.byref(a), current_stream()), "sdy_hist_add")
-            first = last
 
     def read(self) -> Tuple[np.ndarray, List[Optional[np.ndarray]]]:
         """Synchronises and reads back: counts int64 (variables, n_times, n_bins) and per variable the edges (None: nothing

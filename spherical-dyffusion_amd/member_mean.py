@@ -5,27 +5,15 @@
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, Optional, Sequence
 
 import torch
 
-from ._lib import (SDY_MAX_VARS, SDY_MEMBER_STATS_MAX_MEMBERS, SdyMemberStatsArgs, SdyMemberSumArgs, check, current_stream,
-                   lib, ptr)
-from .metrics import TorchDistributed, whole_ics_message, window_layouts
+from ._lib import SDY_MEMBER_STATS_MAX_MEMBERS, SdyMemberStatsArgs, SdyMemberSumArgs, check, current_stream, lib, ptr
+from .windows import FieldAccumulator, WindowLayout, fill_window, runs, whole_ics_message, window_layouts
 
 
-def window_grids(lay) -> List[tuple]:
-    """Per variable (members, samples, lat, lon) of `window_layouts`' result."""
-    return [(l[2], l[3], l[8], l[9]) for l in lay]
-
-
-def check_same_job(names: List[str], grids: List[tuple], first_names: List[str], first_grids: List[tuple]) -> None:
-    """A later window must hold the first window's variables, in its order, on its grids, with its member and sample count."""
-    if list(names) != list(first_names) or list(grids) != list(first_grids):
-        raise ValueError("the variables, member count, sample count or grids of a window differ from the first window's")
-
-
-class EnsembleTimeMeanAggregator:
+class EnsembleTimeMeanAggregator(FieldAccumulator):
     """One time-mean map per member, and the reference's numbers on them.
 
     `record_batch(loss, target_data, gen_data, target_data_norm, gen_data_norm, i_time_start)` is what `run_inference` calls
@@ -54,64 +42,40 @@ class EnsembleTimeMeanAggregator:
 
     accepts_sample_weights = True      # (to see, and refuse, a ragged share)
 
+    _job_words = "member count, sample count"
+
     def __init__(self, area_weights: torch.Tensor, dist=None, target: str = "denorm", metadata=None, spread: bool = False,
                  max_bytes: Optional[int] = None):
         if target not in ("norm", "denorm"):
             raise ValueError(f"target must be 'norm' or 'denorm', got {target!r}")
+        super().__init__(dist=dist, metadata=metadata, max_bytes=max_bytes)      # (no time axis)
         self._area_weights = area_weights
-        self._dist = TorchDistributed() if dist is None else dist
         self._target = target
-        self._metadata = {} if metadata is None else metadata
         self._spread = bool(spread)
-        self._max_bytes = max_bytes
-        self._names: Optional[List[str]] = None
-        self._grids: List[tuple] = []                  # per variable (members, samples, lat, lon)
-        self._gen_sum: Optional[torch.Tensor] = None   # flat float64: the variables' (members, samples, lat, lon) blocks
-        self._target_sum: Optional[torch.Tensor] = None
-        self._gen_at: List[int] = []
-        self._target_at: List[int] = []
         self._n_times = 0
 
-    def _prepare(self, names: List[str], lay) -> torch.device:
-        """Everything is checked before anything changes: a refused window leaves the aggregator as it was."""
-        grids = window_grids(lay)
-        on_device = all(l[0].is_cuda and l[1].is_cuda for l in lay)
-        if self._names is None:
-            need = 8 * sum(n1 * H * W * (M + 1) for M, n1, H, W in grids)
-            limit = self._max_bytes
-            if limit is None and on_device:
-                limit = torch.cuda.get_device_properties(lay[0][0].device).total_memory // 4
-            if limit is not None and need > limit:
-                raise ValueError(f"EnsembleTimeMeanAggregator: {len(names)} variables of {grids[0][0]} members need {need} "
-                                 f"bytes of float64 accumulators, more than max_bytes = {limit}")
-        else:
-            check_same_job(names, grids, self._names, self._grids)
-        if not on_device:
-            raise RuntimeError("sdy_amd aggregators run on the GPU only (no CPU fallback)")
-        if self._names is None:
-            device = lay[0][0].device
-            gen_at, target_at, g_at, t_at = [], [], 0, 0
-            for M, n1, H, W in grids:
-                gen_at.append(g_at)
-                target_at.append(t_at)
-                g_at += M * n1 * H * W
-                t_at += n1 * H * W
-            self._gen_sum = torch.zeros(g_at, dtype=torch.float64, device=device)
-            self._target_sum = torch.zeros(t_at, dtype=torch.float64, device=device)
-            self._gen_at, self._target_at = gen_at, target_at
-            self._names, self._grids = list(names), grids
-        return self._gen_sum.device
+    def _statistics(self) -> Dict[str, float]:
+        return {"gen_sum": 0.0, "target_sum": 0.0}
 
-    def _runs(self, key=lambda i: None):
-        """Runs of consecutive variables that one launch takes: the same grid and `key`, at most SDY_MAX_VARS."""
-        first, n = 0, len(self._grids)
-        while first < n:
-            last = first + 1
-            while (last < n and last - first < SDY_MAX_VARS and self._grids[last] == self._grids[first]
-                   and key(last) == key(first)):
-                last += 1
-            yield first, last
-            first = last
+    @staticmethod
+    def _job(l: WindowLayout) -> tuple:
+        return (l.n0, l.n1, l.H, l.W)
+
+    def _elements(self, stat: str, job: tuple) -> int:
+        M, n1, H, W = job
+        return (M if stat == "gen_sum" else 1) * n1 * H * W
+
+    def _size_words(self, names, jobs) -> str:
+        return f"{len(names)} variables of {jobs[0][0]} members"
+
+    @property
+    def _gen_sum(self) -> Optional[torch.Tensor]:
+        """Flat float64: the variables' (members, samples, lat, lon) blocks (None before the first window)."""
+        return self._acc.get("gen_sum")
+
+    @property
+    def _target_sum(self) -> Optional[torch.Tensor]:
+        return self._acc.get("target_sum")
 
     @torch.no_grad()
     def record_batch(self, loss, target_data, gen_data, target_data_norm=None, gen_data_norm=None, i_time_start: int = 0,
@@ -126,23 +90,16 @@ class EnsembleTimeMeanAggregator:
             raise ValueError(whole_ics_message("EnsembleTimeMeanAggregator"))
         lay = window_layouts(target_data, gen_data)
         device = self._prepare(list(gen_data), lay)
-        for l in lay:
-            if l[0].device != device or l[1].device != device:
-                raise ValueError(f"tensors on {l[0].device} / {l[1].device}, accumulators on {device}")
-        T = lay[0][7]
+        T = lay[0].T
         t0 = 1 if int(i_time_start) == 0 else 0       # the very first time of a run is the initial condition
         if T - t0 < 1:
             return                                    # a window that holds the initial condition only
         with torch.cuda.device(device):
-            for first, last in self._runs(lambda i: lay[i][2:]):
+            for first, last in runs(lay, lambda l: l.extents):
                 a = SdyMemberSumArgs()
-                a.nvars = last - first
-                for j in range(first, last):
-                    a.gen[j - first], a.target[j - first] = ptr(lay[j][0]), ptr(lay[j][1])
-                _, _, a.n0, a.n1, a.gs0, a.gs1, a.ts1, a.T, H, W = lay[first]
-                a.HW, a.t0 = H * W, t0
-                a.gen_sum = self._gen_sum.data_ptr() + 8 * self._gen_at[first]
-                a.target_sum = self._target_sum.data_ptr() + 8 * self._target_at[first]
+                fill_window(a.win, lay, first, last)
+                a.HW, a.t0 = lay[first].H * lay[first].W, t0
+                a.gen_sum, a.target_sum = self._at("gen_sum", first), self._at("target_sum", first)
                 check(lib.sdy_member_time_sum(C.byref(a), current_stream()), "sdy_member_time_sum")
         self._n_times += T - t0
 
@@ -150,12 +107,6 @@ class EnsembleTimeMeanAggregator:
         # (raised BEFORE any collective: every rank of a job must have recorded at least one window)
         if self._gen_sum is None or self._n_times == 0:
             raise ValueError("No data recorded.")
-
-    def _block(self, i: int):
-        M, n1, H, W = self._grids[i]
-        g = self._gen_sum[self._gen_at[i]:self._gen_at[i] + M * n1 * H * W]
-        t = self._target_sum[self._target_at[i]:self._target_at[i] + n1 * H * W]
-        return g, t
 
     @torch.no_grad()
     def time_mean_maps(self) -> Dict[str, Dict[str, torch.Tensor]]:
@@ -167,9 +118,8 @@ class EnsembleTimeMeanAggregator:
         n = torch.full((), float(self._n_times), dtype=torch.float64, device=self._gen_sum.device)
         for i, name in enumerate(self._names):
             M, n1, H, W = self._grids[i]
-            g, t = self._block(i)
-            out["gen"][name] = g.view(M, n1, H, W) / n
-            out["target"][name] = t.view(n1, H, W) / n
+            out["gen"][name] = self._view("gen_sum", i, M, n1, H, W) / n
+            out["target"][name] = self._view("target_sum", i, n1, H, W) / n
         return out
 
     @torch.no_grad()
@@ -179,7 +129,7 @@ class EnsembleTimeMeanAggregator:
         device = self._gen_sum.device
         out = {}
         with torch.cuda.device(device):
-            for first, last in self._runs():
+            for first, last in runs(self._grids, lambda g: g):
                 M, n1, H, W = self._grids[first]
                 if M > SDY_MEMBER_STATS_MAX_MEMBERS:
                     raise ValueError(f"at most {SDY_MEMBER_STATS_MAX_MEMBERS} members, got {M}")
@@ -192,8 +142,7 @@ class EnsembleTimeMeanAggregator:
                 ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=device)
                 a = SdyMemberStatsArgs()
                 a.nvars, a.M, a.n1, a.HW = nvars, M, n1, H * W
-                a.gen_sum = self._gen_sum.data_ptr() + 8 * self._gen_at[first]
-                a.target_sum = self._target_sum.data_ptr() + 8 * self._target_at[first]
+                a.gen_sum, a.target_sum = self._at("gen_sum", first), self._at("target_sum", first)
                 a.weights, a.n_times, a.out = ptr(w), float(self._n_times), ptr(res)
                 a.ws, a.ws_bytes = ptr(ws), ws_bytes
                 check(lib.sdy_member_map_stats(C.byref(a), current_stream()), "sdy_member_map_stats")

@@ -15,8 +15,10 @@ from typing import Dict, List, Mapping, Optional, Sequence
 import numpy as np
 import torch
 
-from ._lib import SDY_MAX_VARS, SdyVideoArgs, SdyZonalArgs, aligned, check, current_stream, lib, ptr
-from .histogram import _strided_layout
+from ._lib import SdyVideoArgs, SdyZonalArgs, aligned, check, current_stream, lib, ptr
+from .member_mean import EnsembleTimeMeanAggregator
+from .spectrum import PowerSpectrumAggregator
+from .windows import FieldAccumulator, TorchDistributed, fill_window, whole_ics_message, window_layouts  # noqa: F401
 
 
 def spherical_area_weights(lats, num_lon: int) -> torch.Tensor:
@@ -52,54 +54,6 @@ def ensemble_metrics(truth: torch.Tensor, predicted: torch.Tensor, weights: torc
     spread = out[:, 1].sqrt().reshape(lead) * ((E + 1) / E) ** 0.5
     return {"rmse": rmse, "spread": spread, "spread_skill_ratio": spread / rmse, "crps": out[:, 2].reshape(lead),
             "bias": out[:, 3].reshape(lead)}
-
-
-class TorchDistributed:
-    """`reduce_mean` / `reduce_sum` of the reference's `Distributed` singleton (`src/ace_inference/core/distributed.py:70-94`):
-    `torch.distributed.all_reduce` over ranks (RCCL over xGMI on the GPU box; identity without a process group).  The reduce
-    is issued on a side stream: it belongs to `get_logs`, not to the sampling path, and never blocks the compute stream."""
-
-    def __init__(self):
-        import torch.distributed as dist
-
-        self._dist = dist if dist.is_available() and dist.is_initialized() else None
-        self._stream = None
-
-    @property
-    def world_size(self) -> int:
-        return self._dist.get_world_size() if self._dist is not None else 1
-
-    def reduce_sum(self, tensor: torch.Tensor) -> torch.Tensor:
-        return tensor if self._dist is None else self._reduce(tensor, self._dist.ReduceOp.SUM)
-
-    def _reduce(self, tensor: torch.Tensor, op) -> torch.Tensor:
-        if self._dist is None:
-            return tensor
-        if not tensor.is_cuda:
-            out = tensor.clone()
-            self._dist.all_reduce(out, op=op)
-            return out
-        if self._stream is None:
-            self._stream = torch.cuda.Stream(device=tensor.device)
-        self._stream.wait_stream(torch.cuda.current_stream(tensor.device))
-        with torch.cuda.stream(self._stream):
-            out = tensor.clone()
-            self._dist.all_reduce(out, op=op)
-        torch.cuda.current_stream(tensor.device).wait_stream(self._stream)
-        return out
-
-    def reduce_mean(self, tensor: torch.Tensor) -> torch.Tensor:
-        if self._dist is None:
-            return tensor
-        return self.reduce_sum(tensor) / self.world_size
-
-    def reduce_min(self, tensor: torch.Tensor) -> torch.Tensor:
-        """What the reference's `VideoAggregator` asks of its `dist` for the error extremes: all_reduce with MIN (`reduce_max`:
-        MAX) on the side stream; identity without a process group."""
-        return tensor if self._dist is None else self._reduce(tensor, self._dist.ReduceOp.MIN)
-
-    def reduce_max(self, tensor: torch.Tensor) -> torch.Tensor:
-        return tensor if self._dist is None else self._reduce(tensor, self._dist.ReduceOp.MAX)
 
 
 class TimeMeanAggregator:
@@ -260,13 +214,6 @@ def grad_mag_percent_diff(s: torch.Tensor) -> torch.Tensor:
     """`gradient_magnitude_percent_diff` (`metrics.py:223-241`) from `ensemble_series(..., grad_mag=True)` rows:
     100 (P - T) / T per plane; a truth plane without gradient gives inf / nan, as in the reference."""
     return 100.0 * (s[..., 9] - s[..., 8]) / s[..., 8]
-
-
-def whole_ics_message(who: str) -> str:
-    """What an ensemble aggregator says to a ragged share (flat rows: an initial condition's members cut by a rank boundary)."""
-    return (f"{who} needs member-stacked (members, samples, time, lat, lon) "
-            "predictions: ensemble-mean RMSE / CRPS / spread of an initial condition need all of its "
-            "members on one rank (shard whole initial conditions, or use TimeMeanAggregator)")
 
 
 class MeanAggregator:
@@ -456,139 +403,7 @@ class OneStepMeanAggregator:
         return {k: float(self._dist.reduce_mean(logs[k].reshape(1))[0]) for k in sorted(logs)}
 
 
-def window_layouts(target_data, gen_data):
-    """Per generated variable (gen, target, n0, n1, gs0, gs1, ts1, T, H, W) of one window, everything checked but the place of
-    its times in a run; nothing is enqueued."""
-    if len(gen_data) == 0:
-        raise ValueError("No data in gen_data")
-    out = []
-    for name, g in gen_data.items():
-        if name not in target_data:
-            raise ValueError(f"no target for generated variable {name!r}")
-        t = target_data[name]
-        if g.dim() not in (4, 5) or t.dim() != 4:
-            raise ValueError(f"{name!r}: generated data are (samples, time, lat, lon) or (members, samples, time, lat, lon)"
-                             f" and targets (samples, time, lat, lon), got {tuple(g.shape)} and {tuple(t.shape)}")
-        if tuple(g.shape[-4:]) != tuple(t.shape):
-            raise ValueError(f"{name!r}: generated {tuple(g.shape)} against target {tuple(t.shape)}")
-        H, W = g.shape[-2:]
-        gv, n0, n1, gs0, gs1, T, _ = _strided_layout(g)
-        tv, _, tn1, _, ts1, _, _ = _strided_layout(t)
-        if min(n0, n1, T, H, W) < 1:
-            raise ValueError("empty tensor")
-        if (n0, n1) != (1 if g.dim() == 4 else g.shape[0], tn1):   # (a 5-D view that had to be copied came back flat)
-            gv = gv.view(g.shape)
-            n0, n1, gs0, gs1 = g.shape[0], g.shape[1], gv.stride(0), gv.stride(1)
-        out.append((gv, tv, n0, n1, gs0, gs1, ts1, T, H, W))
-    T = out[0][7]
-    if any(l[7] != T for l in out):
-        raise ValueError("the variables of one window differ in their number of times")
-    return out
-
-
-class _FieldAccumulator:
-    """What `VideoAggregator` and `ZonalMeanAggregator` share: the layouts of a window's tensors, the float64 accumulators
-    (one flat device buffer per statistic, the variables' blocks in dict order, so a run of same-shaped variables is one
-    contiguous `(nvars, ...)` block: what one launch takes), the memory limit and the per-time batch counts (host integers)."""
-
-    def __init__(self, n_timesteps: int, dist=None, metadata=None, max_bytes: Optional[int] = None):
-        if n_timesteps < 1:
-            raise ValueError(f"n_timesteps must be positive, got {n_timesteps}")
-        self._n_timesteps = int(n_timesteps)
-        self._dist = TorchDistributed() if dist is None else dist
-        self._metadata = {} if metadata is None else metadata
-        self._max_bytes = max_bytes
-        self._n_batches = [0] * self._n_timesteps
-        self._names: Optional[List[str]] = None
-        self._grids: List[tuple] = []
-        self._acc: Dict[str, torch.Tensor] = {}
-        self._offsets: List[int] = []
-
-    # -- to be provided: statistic name -> fill value, and the accumulator elements of one variable
-    def _statistics(self) -> Dict[str, float]:
-        raise NotImplementedError
-
-    def _block(self, n1: int, H: int, W: int) -> int:
-        raise NotImplementedError
-
-    def _layouts(self, target_data, gen_data, i_time_start: int):
-        """`window_layouts` of a window whose times must lie inside the aggregator's."""
-        out = window_layouts(target_data, gen_data)
-        T = out[0][7]
-        if i_time_start < 0 or i_time_start + T > self._n_timesteps:
-            raise ValueError(f"times {i_time_start}..{i_time_start + T - 1} outside the aggregator's {self._n_timesteps}")
-        return out
-
-    def _prepare(self, names: List[str], lay) -> torch.device:
-        """First batch: the memory limit, the device check, then the accumulators.  Later batches: the same variables and
-        grids as the first."""
-        on_device = all(l[0].is_cuda and l[1].is_cuda for l in lay)
-        grids = [(l[3], l[8], l[9]) for l in lay]
-        if self._names is None:
-            stats = self._statistics()
-            total = sum(self._block(*g) for g in grids) * self._n_timesteps
-            need = len(stats) * total * 8
-            device = lay[0][0].device
-            limit = self._max_bytes
-            if limit is None and on_device:
-                limit = torch.cuda.get_device_properties(device).total_memory // 4
-            if limit is not None and need > limit:
-                raise ValueError(f"{type(self).__name__}: {len(stats)} statistics x {len(names)} variables x "
-                                 f"{self._n_timesteps} timesteps need {need} bytes of float64 accumulators, more than "
-                                 f"max_bytes = {limit}")
-        elif names != self._names or grids != self._grids:
-            raise ValueError("the variables, sample count or grids of a window differ from the first window's")
-        if not on_device:
-            raise RuntimeError("sdy_amd aggregators run on the GPU only (no CPU fallback)")
-        if self._names is None:
-            self._acc = {k: torch.full((total,), fill, dtype=torch.float64, device=device) for k, fill in stats.items()}
-            self._offsets, at = [], 0
-            for g in grids:
-                self._offsets.append(at)
-                at += self._block(*g) * self._n_timesteps
-            self._names, self._grids = list(names), grids
-        return next(iter(self._acc.values())).device
-
-    def _runs(self, lay):
-        """Runs of consecutive variables that one launch takes: same extents and strides, at most SDY_MAX_VARS."""
-        first = 0
-        while first < len(lay):
-            last = first + 1
-            while last < len(lay) and last - first < SDY_MAX_VARS and lay[last][2:] == lay[first][2:]:
-                last += 1
-            yield first, last
-            first = last
-
-    def _record(self, target_data, gen_data, i_time_start: int) -> None:
-        i_time_start = int(i_time_start)
-        lay = self._layouts(target_data, gen_data, i_time_start)
-        device = self._prepare(list(gen_data), lay)
-        for l in lay:
-            if l[0].device != device or l[1].device != device:
-                raise ValueError(f"tensors on {l[0].device} / {l[1].device}, accumulators on {device}")
-        with torch.cuda.device(device):
-            for first, last in self._runs(lay):
-                self._launch(lay, first, last, i_time_start)
-        for t in range(i_time_start, i_time_start + lay[0][7]):
-            self._n_batches[t] += 1
-
-    def _counts(self) -> torch.Tensor:
-        if self._names is None:
-            raise RuntimeError("No data recorded")
-        return torch.tensor(self._n_batches, dtype=torch.float64, device=next(iter(self._acc.values())).device)
-
-    def _view(self, stat: str, i: int, *shape) -> torch.Tensor:
-        n = 1
-        for d in shape:
-            n *= d
-        return self._acc[stat][self._offsets[i]:self._offsets[i] + n].view(*shape)
-
-    def get_logs(self, label: str) -> Dict[str, object]:
-        """{}: the wandb videos / images of the reference are out of scope, and the log key sets stay what they were."""
-        return {}
-
-
-class VideoAggregator(_FieldAccumulator):
+class VideoAggregator(FieldAccumulator):
     """Videos of state evolution: device mirror of `VideoAggregator`
     (`src/ace_inference/core/aggregator/inference/video.py`) minus the wandb rendering.
 
@@ -625,18 +440,16 @@ class VideoAggregator(_FieldAccumulator):
             stats.update(gen_sq=0.0, target_sq=0.0, err_var=0.0, err_min=float("inf"), err_max=float("-inf"))
         return stats
 
-    def _block(self, n1: int, H: int, W: int) -> int:
-        return H * W
+    def _elements(self, stat: str, job: tuple) -> int:
+        _, H, W = job
+        return self._n_timesteps * H * W
 
     def _launch(self, lay, first: int, last: int, t_start: int) -> None:
         a = SdyVideoArgs()
-        a.nvars = last - first
-        for j in range(first, last):
-            a.gen[j - first], a.target[j - first] = ptr(lay[j][0]), ptr(lay[j][1])
-        _, _, a.n0, a.n1, a.gs0, a.gs1, a.ts1, a.T, H, W = lay[first]
-        a.HW, a.t_start, a.n_timesteps = H * W, t_start, self._n_timesteps
-        for stat, buf in self._acc.items():
-            setattr(a, stat, buf.data_ptr() + 8 * self._offsets[first])
+        fill_window(a.win, lay, first, last)
+        a.HW, a.t_start, a.n_timesteps = lay[first].H * lay[first].W, t_start, self._n_timesteps
+        for stat in self._acc:
+            setattr(a, stat, self._at(stat, first))
         check(lib.sdy_video_accumulate(C.byref(a), current_stream()), "sdy_video_accumulate")
 
     @torch.no_grad()
@@ -682,7 +495,7 @@ class VideoAggregator(_FieldAccumulator):
         return out
 
 
-class ZonalMeanAggregator(_FieldAccumulator):
+class ZonalMeanAggregator(FieldAccumulator):
     """Zonal means as a function of latitude and time (hovmollers): device mirror of `ZonalMeanAggregator`
     (`src/ace_inference/core/aggregator/inference/zonal_mean.py`) minus the wandb images.
 
@@ -702,18 +515,16 @@ class ZonalMeanAggregator(_FieldAccumulator):
     def _statistics(self) -> Dict[str, float]:
         return {"gen_acc": 0.0, "target_acc": 0.0}
 
-    def _block(self, n1: int, H: int, W: int) -> int:
-        return n1 * H
+    def _elements(self, stat: str, job: tuple) -> int:
+        n1, H, _ = job
+        return n1 * self._n_timesteps * H
 
     def _launch(self, lay, first: int, last: int, t_start: int) -> None:
         a = SdyZonalArgs()
-        a.nvars = last - first
-        for j in range(first, last):
-            a.gen[j - first], a.target[j - first] = ptr(lay[j][0]), ptr(lay[j][1])
-        _, _, a.n0, a.n1, a.gs0, a.gs1, a.ts1, a.T, a.H, a.W = lay[first]
-        a.t_start, a.n_timesteps = t_start, self._n_timesteps
-        for stat, buf in self._acc.items():
-            setattr(a, stat, buf.data_ptr() + 8 * self._offsets[first])
+        fill_window(a.win, lay, first, last)
+        a.H, a.W, a.t_start, a.n_timesteps = lay[first].H, lay[first].W, t_start, self._n_timesteps
+        for stat in self._acc:
+            setattr(a, stat, self._at(stat, first))
         check(lib.sdy_zonal_accumulate(C.byref(a), current_stream()), "sdy_zonal_accumulate")
 
     @torch.no_grad()
@@ -792,13 +603,9 @@ class InferenceAggregator:
         if zonal_mean_data:
             self._aggregators["zonal_mean"] = ZonalMeanAggregator(n_timesteps=n_timesteps, dist=dist, metadata=metadata)
         if power_spectrum_data:
-            from .spectrum import PowerSpectrumAggregator      # (spectrum.py builds on this module)
-
             self._aggregators["power_spectrum"] = PowerSpectrumAggregator(n_timesteps=n_timesteps, grid=spectrum_grid,
                                                                           dist=dist, metadata=metadata)
         if ensemble_time_mean_data or ensemble_time_mean_spread:
-            from .member_mean import EnsembleTimeMeanAggregator      # (member_mean.py builds on this module)
-
             self._aggregators["time_mean_ensemble"] = EnsembleTimeMeanAggregator(
                 area_weights, dist=dist, metadata=metadata, spread=ensemble_time_mean_spread)
 

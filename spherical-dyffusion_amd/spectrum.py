@@ -25,7 +25,7 @@ from typing import Dict, List, Optional
 import torch
 
 from ._lib import SdySpectrumArgs, check, current_stream, lib, ptr
-from .metrics import _FieldAccumulator
+from .windows import FieldAccumulator
 from .sht import ShtPlan
 
 #: default `max_workspace_bytes`: packed rows, grid-frequency tensor and the coefficients of both sides of one chunk
@@ -138,7 +138,7 @@ def power_spectrum(x: torch.Tensor, grid: str = "equiangular", lmax: Optional[in
     return out.view(*lead, plan.lmax)
 
 
-class PowerSpectrumAggregator(_FieldAccumulator):
+class PowerSpectrumAggregator(FieldAccumulator):
     """Per-degree power spectra of the generated and the target fields and of their difference, per variable and lead time.
 
     Same `record_batch` as the other inference aggregators, on the denormalised dicts: gen `(samples, time, lat, lon)` or
@@ -174,7 +174,11 @@ class PowerSpectrumAggregator(_FieldAccumulator):
     def _statistics(self) -> Dict[str, float]:
         return {"gen_power": 0.0, "target_power": 0.0, "err_power": 0.0}
 
-    def _block(self, n1: int, H: int, W: int) -> int:
+    def _elements(self, stat: str, job: tuple) -> int:
+        return self._n_timesteps * self._degrees(job)
+
+    def _degrees(self, job: tuple) -> int:
+        _, H, _ = job
         return self._lmax or H
 
     @property
@@ -194,13 +198,13 @@ class PowerSpectrumAggregator(_FieldAccumulator):
         xb, Xf, Cg, Ct, zeros = self._ws.parts(device, Fx * H * W, Fx * plan.mtr * H * 2, Fg * per_cs, Ft * per_cs, Fx)
         zeros.zero_()
         scales = []
-        for side, F, rows, rows_p, Cs in ((0, Fg, R, Rp, Cg), (1, Ft, n1, Sp, Ct)):
+        for side, F, rows, rows_p, Cs in (("gen", Fg, R, Rp, Cg), ("target", Ft, n1, Sp, Ct)):
             x = xb[:F * H * W].view(nv, T, rows_p, H, W)
             if rows_p != rows:
                 x[:, :, rows:].zero_()
             for k in range(nv):
-                v = lay[first + k][side]
-                if side == 0:
+                v = getattr(lay[first + k], side)
+                if side == "gen":
                     src = torch.as_strided(v, (n0, n1, T, H, W), (gs0, gs1, H * W, W, 1)).permute(2, 0, 1, 3, 4)
                     x[k, :, :rows].view(T, n0, n1, H, W).copy_(src)
                 else:
@@ -212,8 +216,8 @@ class PowerSpectrumAggregator(_FieldAccumulator):
         a.lmax, a.mtr, a.gen_fields, a.target_fields = plan.lmax, plan.mtr, Fg, Ft
         a.gen_var_stride, a.gen_time_stride, a.target_var_stride, a.target_time_stride = T * Rp, Rp, T * Sp, Sp
         a.nvars, a.n0, a.n1, a.T, a.t_start, a.n_timesteps = nv, n0, n1, T, t_start, self._n_timesteps
-        for stat, buf in self._acc.items():
-            setattr(a, stat, buf.data_ptr() + 8 * self._offsets[first])
+        for stat in self._acc:
+            setattr(a, stat, self._at(stat, first))
         check(lib.sdy_degree_power(C.byref(a), current_stream()), "sdy_degree_power")
 
     def _vars_per_chunk(self, l, device) -> int:
@@ -232,8 +236,8 @@ class PowerSpectrumAggregator(_FieldAccumulator):
         return n
 
     def _launch(self, lay, first: int, last: int, t_start: int) -> None:
-        """A run of same-shaped variables (`_FieldAccumulator._record`), in chunks that fit the workspace."""
-        device = lay[first][0].device
+        """A run of same-shaped variables (`FieldAccumulator._record`), in chunks that fit the workspace."""
+        device = lay[first].gen.device
         step = self._vars_per_chunk(lay[first], device)
         for c0 in range(first, last, step):
             self._chunk(lay, c0, min(c0 + step, last), t_start, device)
@@ -249,7 +253,7 @@ class PowerSpectrumAggregator(_FieldAccumulator):
         red = self._dist.reduce_mean
         data = {}
         for i, name in enumerate(self._names):
-            shape = (self._n_timesteps, self._block(*self._grids[i]))
+            shape = (self._n_timesteps, self._degrees(self._grids[i]))
             data[name] = {label: red(self._view(stat, i, *shape) / n)
                           for label, stat in (("gen", "gen_power"), ("target", "target_power"), ("error", "err_power"))}
         return data

@@ -18,6 +18,7 @@ import json
 import numpy as np
 
 import golden_utils as gu
+from window_utils import fill_window, vp
 
 U = 2.0 ** -24
 VIDEO_STATS = ("gen_mean", "target_mean", "gen_sq", "target_sq", "err_var", "err_min", "err_max")
@@ -45,28 +46,16 @@ def cases():
     return out
 
 
-def _vp(a):
-    return a.ctypes.data_as(C.c_void_p).value
-
-
 def video_args(target, gen, names, t_start, n_timesteps, acc):
     """SdyVideoArgs over contiguous numpy arrays (gen 4-D or member-stacked 5-D) and the accumulators `acc` (stat -> float64
     (nvars, n_timesteps, HW), missing = NULL); -> (args, keep-alive list)."""
     from sdy_amd._lib import SdyVideoArgs
 
     a = SdyVideoArgs()
-    keep = []
-    a.nvars = len(names)
-    for j, k in enumerate(names):
-        g, t = np.ascontiguousarray(gen[k], np.float32), np.ascontiguousarray(target[k], np.float32)
-        keep += [g, t]
-        a.gen[j], a.target[j] = _vp(g), _vp(t)
-    S, T, H, W = t.shape
-    a.n0, a.n1, a.T, a.HW = (g.shape[0] if g.ndim == 5 else 1), S, T, H * W
-    a.gs0, a.gs1, a.ts1 = (S * T * H * W if g.ndim == 5 else 0), T * H * W, T * H * W
-    a.t_start, a.n_timesteps = t_start, n_timesteps
+    keep, (H, W) = fill_window(a.win, target, gen, names)
+    a.HW, a.t_start, a.n_timesteps = H * W, t_start, n_timesteps
     for stat, buf in acc.items():
-        setattr(a, stat, _vp(buf))
+        setattr(a, stat, vp(buf))
     return a, keep
 
 
@@ -74,17 +63,9 @@ def zonal_args(target, gen, names, t_start, n_timesteps, gen_acc, target_acc):
     from sdy_amd._lib import SdyZonalArgs
 
     a = SdyZonalArgs()
-    keep = []
-    a.nvars = len(names)
-    for j, k in enumerate(names):
-        g, t = np.ascontiguousarray(gen[k], np.float32), np.ascontiguousarray(target[k], np.float32)
-        keep += [g, t]
-        a.gen[j], a.target[j] = _vp(g), _vp(t)
-    S, T, H, W = t.shape
-    a.n0, a.n1, a.T, a.H, a.W = (g.shape[0] if g.ndim == 5 else 1), S, T, H, W
-    a.gs0, a.gs1, a.ts1 = (S * T * H * W if g.ndim == 5 else 0), T * H * W, T * H * W
+    keep, (a.H, a.W) = fill_window(a.win, target, gen, names)
     a.t_start, a.n_timesteps = t_start, n_timesteps
-    a.gen_acc, a.target_acc = _vp(gen_acc), _vp(target_acc)
+    a.gen_acc, a.target_acc = vp(gen_acc), vp(target_acc)
     return a, keep
 
 

@@ -25,6 +25,7 @@ import json
 import numpy as np
 
 import golden_utils as gu
+from window_utils import fill_window, vp
 
 U = 2.0 ** -24
 
@@ -143,26 +144,14 @@ def restate(case, spread=False):
     return logs_from_raw(raw, case["names"], case["B"], case["weights"], spread), scales, xmax
 
 
-def _vp(a):
-    return a.ctypes.data_as(C.c_void_p).value
-
-
 def sum_args(target, gen, names, t0, gen_sum, target_sum):
     """SdyMemberSumArgs over contiguous numpy arrays (gen 4-D or member-stacked 5-D); -> (args, keep-alive list)."""
     from sdy_amd._lib import SdyMemberSumArgs
 
     a = SdyMemberSumArgs()
-    keep = []
-    a.nvars = len(names)
-    for j, k in enumerate(names):
-        g, t = np.ascontiguousarray(gen[k], np.float32), np.ascontiguousarray(target[k], np.float32)
-        keep += [g, t]
-        a.gen[j], a.target[j] = _vp(g), _vp(t)
-    S, T, H, W = t.shape
-    a.n0, a.n1, a.T, a.HW = (g.shape[0] if g.ndim == 5 else 1), S, T, H * W
-    a.gs0, a.gs1, a.ts1 = (S * T * H * W if g.ndim == 5 else 0), T * H * W, T * H * W
-    a.t0 = t0
-    a.gen_sum, a.target_sum = _vp(gen_sum), _vp(target_sum)
+    keep, (H, W) = fill_window(a.win, target, gen, names)
+    a.HW, a.t0 = H * W, t0
+    a.gen_sum, a.target_sum = vp(gen_sum), vp(target_sum)
     return a, keep
 
 
@@ -189,7 +178,7 @@ def stats_args(gen_sum, target_sum, weights, n_times, out):
     a.nvars, a.M, a.n1 = gen_sum.shape[:3]
     a.HW = gen_sum.shape[3] * gen_sum.shape[4]
     w = np.ascontiguousarray(weights, np.float32)
-    a.gen_sum, a.target_sum, a.weights, a.n_times, a.out = _vp(gen_sum), _vp(target_sum), _vp(w), float(n_times), _vp(out)
+    a.gen_sum, a.target_sum, a.weights, a.n_times, a.out = vp(gen_sum), vp(target_sum), vp(w), float(n_times), vp(out)
     return a, [w]
 
 

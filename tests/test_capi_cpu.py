@@ -37,6 +37,29 @@ def test_header_symbols_are_exported_and_bound(sdy):
     assert sdy.lib.sdy_version() >= 100
 
 
+def test_abi_check_covers_every_argument_structure(sdy):
+    """One handshake for every argument structure of the header, in header order: the bindings' sizes are the library's, and
+    any single wrong size or a wrong count is refused."""
+    from sdy_amd import _lib
+
+    hdr = open(os.path.join(ROOT, "include", "sdy_amd.h")).read()
+    declared = re.findall(r"\}\s*(sdy_\w+_(?:args|config|table));", hdr)
+    camel = ["Sdy" + "".join(w.capitalize() for w in name.split("_")[1:]) for name in declared]
+    assert [t.__name__ for t in _lib.ABI_STRUCTS] == camel and len(camel) == int(re.search(r"SDY_ABI_STRUCTS (\d+)", hdr)[1])
+    sizes = [C.sizeof(t) for t in _lib.ABI_STRUCTS]
+    n = len(sizes)
+    check = lambda v, k=n: sdy.lib.sdy_abi_check((C.c_size_t * len(v))(*v), k)  # noqa: E731
+    assert check(sizes) == 0
+    theirs = (C.c_size_t * n)()
+    assert sdy.lib.sdy_abi_sizes(theirs, n) == 0 and list(theirs) == sizes
+    for i in range(n):
+        for d in (8, -8):
+            assert check(sizes[:i] + [sizes[i] + d] + sizes[i + 1:]) == -1, _lib.ABI_STRUCTS[i].__name__
+    assert check(sizes, n - 1) == -1 and check(sizes + [8], n + 1) == -1 and check(sizes, 0) == -1
+    assert sdy.lib.sdy_abi_check(None, n) == -1 and sdy.lib.sdy_abi_sizes(theirs, n - 1) == -1
+    assert sdy.lib.sdy_abi_sizes(None, n) == -1
+
+
 @pytest.mark.parametrize("grid,gid", [("equiangular", 0), ("legendre-gauss", 1)])
 @pytest.mark.parametrize("nlat,nlon", [(32, 64), (180, 360)])
 def test_host_tables_match_oracle(sdy, grid, gid, nlat, nlon):

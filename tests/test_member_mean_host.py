@@ -75,8 +75,7 @@ def test_first_time_of_a_run_is_dropped(sdy, cases):
 def test_struct_sizes(sdy):
     from sdy_amd import _lib
 
-    assert sdy.lib.sdy_member_sum_args_bytes() == C.sizeof(_lib.SdyMemberSumArgs)
-    assert sdy.lib.sdy_member_stats_args_bytes() == C.sizeof(_lib.SdyMemberStatsArgs)
+    assert _lib.SdyMemberSumArgs in _lib.ABI_STRUCTS and _lib.SdyMemberStatsArgs in _lib.ABI_STRUCTS   # tests/test_capi_cpu.py
     assert _lib.SDY_MEMBER_STATS_MAX_MEMBERS == 64
 
 
@@ -194,21 +193,22 @@ def test_class_refuses_cpu_tensors(sdy):
 
 
 def test_class_refuses_another_job(sdy):
-    """What record_batch compares a later window with (`window_grids`, `check_same_job`), on host tensors: the variable set,
-    the member count, the sample count and the grid.  (Through the class on a device: tests/test_gpu_member_mean.py.)"""
-    from sdy_amd.member_mean import check_same_job, window_grids
-    from sdy_amd.metrics import window_layouts
+    """What record_batch compares a later window with (`EnsembleTimeMeanAggregator._job` of every layout, `check_same_job`),
+    on host tensors: the variable set, the member count, the sample count and the grid.  (Through the class on a device:
+    tests/test_gpu_member_mean.py.)"""
+    from sdy_amd.windows import check_same_job, window_layouts
 
     def job(**kw):
         target, gen = _window(**kw)
-        return list(gen), window_grids(window_layouts(target, gen))
+        return list(gen), [sdy.EnsembleTimeMeanAggregator._job(l) for l in window_layouts(target, gen)]
 
+    words = sdy.EnsembleTimeMeanAggregator._job_words
     first = job()
     assert first[1] == [(3, 2, 4, 6)] * 2
-    check_same_job(*job(T=2), *first)                              # another number of times is the same job
+    check_same_job(*job(T=2), *first, words)                       # another number of times is the same job
     for other in (dict(names=("a", "c")), dict(names=("b", "a")), dict(names=("a",)), dict(M=4), dict(B=3), dict(H=5)):
-        with pytest.raises(ValueError, match="differ from the first window"):
-            check_same_job(*job(**other), *first)
+        with pytest.raises(ValueError, match="member count, sample count or grids of a window differ from the first window"):
+            check_same_job(*job(**other), *first, words)
 
 
 def test_a_refused_window_changes_nothing(sdy):
