@@ -75,10 +75,10 @@ const char* sdy_error_string(int code);
  * structure below, in header order:
  *   {sdy_conv_args, sdy_mlp_args, sdy_pair_args, sdy_sfno_config, sdy_sfno_fwd_args, sdy_var_table, sdy_step_finish_args,
  *    sdy_derived_args, sdy_corrector_args, sdy_dry_air_args, sdy_hist_args, sdy_coarsen_args, sdy_video_args, sdy_zonal_args,
- *    sdy_member_sum_args, sdy_member_stats_args, sdy_spectrum_args}
+ *    sdy_member_sum_args, sdy_member_stats_args, sdy_spectrum_args, sdy_rank_hist_args}
  * SDY_OK when n == SDY_ABI_STRUCTS and every size equals the library's, SDY_ERR_ARG otherwise (the Python bindings do this at
  * import).  sdy_abi_sizes writes the library's own list, for the message of a failed check (SDY_ERR_ARG: n != SDY_ABI_STRUCTS). */
-#define SDY_ABI_STRUCTS 17
+#define SDY_ABI_STRUCTS 18
 int sdy_abi_check(const size_t* sizes, int n);
 int sdy_abi_sizes(size_t* sizes, int n);
 
@@ -907,6 +907,43 @@ typedef struct sdy_spectrum_args {
 } sdy_spectrum_args;
 int sdy_degree_power(const sdy_spectrum_args* args, void* stream);
 int sdy_degree_power_host(const sdy_spectrum_args* args);
+
+/* Rank (Talagrand) histograms of an ensemble per latitude (no counterpart in the reference): one launch adds ONE window of all
+ * variables to float64 accumulators that stay on the device.  window: see sdy_window, plane = H*W: n0 = M members, n1 samples.
+ * For the target y and the members g_0 .. g_{M-1} of a grid point (variable v, sample s, window time t, lat, lon):
+ *   rank = #{m : g_m < y}, 0 .. M.  A point whose target is NaN is counted nowhere; a NaN member is not below (the comparison
+ *   is false).  The point is a tie when y is not NaN and some g_m == y; ties do not change the rank and are counted apart.
+ *   t0:         the first counted time of the window: 1 when the window starts a run (its first time is the initial
+ *               condition), else 0; t0 == T counts nothing: SDY_OK, nothing is launched
+ *   pool_times: 0: window time t lands in slot t_start + t of n_slots; non-zero: every time lands in slot 0, n_slots must be 1
+ *               and t_start is not looked at
+ *   counts:     dev double, contiguous (nvars, n_slots, H, M + 1), zeroed by the caller before the first call:
+ *                 counts[v, slot, lat, rank] += the counted points of the row's W longitudes, n1 samples (and, pooled, T - t0
+ *                 times) with that rank
+ *   ties:       dev double, contiguous (nvars, n_slots, H), likewise: += the ties among the same points
+ * One group of lanes owns an accumulator row (v, slot, lat): the row's bins are 32-bit words in LDS (integer LDS atomics)
+ * that the owner adds to the accumulators with plain load / add / store: no global atomics, no second pass; calls on the same
+ * accumulators must be ordered on a stream.  Integers below 2^53 add exactly in any order: every count is bit-identical to
+ * the _host twin's, in any layout, batch and run.  16-byte loads when W, every stride and every pointer allow them.
+ * SDY_ERR_ARG, before anything is launched: NULL args / gen[v] / target[v] / counts / ties, an accumulator not 8-byte aligned,
+ * nvars outside 1..SDY_MAX_VARS, a non-positive n0 / n1 / T / H / W / n_slots, a negative stride, t0 outside 0..T; not pooled:
+ * t_start < 0, t_start + T > n_slots; pooled: n_slots != 1.
+ * SDY_ERR_UNSUPPORTED: n0 > SDY_RANK_HIST_MAX_MEMBERS, T*H*W > 2^30, n0*n1 >= 2^31, the points of one row in one call (n1*W,
+ * pooled: n1*W*T) >= 2^32 (the row's 32-bit words), n_slots*H >= 2^40, nvars*n_slots*H*(n0+1) >= 2^50 (flat accumulator
+ * indices are 64-bit).
+ * The _host twin: the same structure with HOST pointers and the same checks; the arithmetic is the header the kernel compiles
+ * (csrc/rank_hist.h), so the semantics can be pinned without a device. */
+#define SDY_RANK_HIST_MAX_MEMBERS 64
+typedef struct sdy_rank_hist_args {
+  sdy_window win;
+  int H, W;
+  int t0;
+  int t_start, n_slots;
+  int pool_times;
+  double *counts, *ties;
+} sdy_rank_hist_args;
+int sdy_rank_hist_accumulate(const sdy_rank_hist_args* args, void* stream);
+int sdy_rank_hist_accumulate_host(const sdy_rank_hist_args* args);
 
 /* ---------------------------------------------------------------------------------------------------------
  * Sticky status word of the CURRENT device.  Kernels only ever set bits; the host reads (and optionally clears) it once per

@@ -222,7 +222,7 @@ class SdyCoarsenArgs(C.Structure):
 
 
 class SdyWindow(C.Structure):
-    """sdy_window: embedded as `win` at the head of the three structures below (filled by `windows.fill_window`); its fields
+    """sdy_window: embedded as `win` at the head of the structures below that read a window in place (filled by `windows.fill_window`); its fields
     also read and write as the embedding structure's own (`a.T` is `a.win.T`)."""
     _fields_ = [
         ("nvars", C.c_int), ("gen", C.c_void_p * SDY_MAX_VARS), ("target", C.c_void_p * SDY_MAX_VARS),
@@ -285,10 +285,24 @@ class SdySpectrumArgs(C.Structure):
     ]
 
 
+SDY_RANK_HIST_MAX_MEMBERS = 64
+
+
+class SdyRankHistArgs(C.Structure):
+    _anonymous_ = ("win",)
+    _fields_ = [
+        ("win", SdyWindow), ("H", C.c_int), ("W", C.c_int),
+        ("t0", C.c_int),
+        ("t_start", C.c_int), ("n_slots", C.c_int),
+        ("pool_times", C.c_int),
+        ("counts", C.c_void_p), ("ties", C.c_void_p),
+    ]
+
+
 # every argument structure of include/sdy_amd.h, in header order: what sdy_abi_check compares
 ABI_STRUCTS = (SdyConvArgs, SdyMlpArgs, SdyPairArgs, SdySfnoConfig, SdySfnoFwdArgs, SdyVarTable, SdyStepFinishArgs,
                SdyDerivedArgs, SdyCorrectorArgs, SdyDryAirArgs, SdyHistArgs, SdyCoarsenArgs, SdyVideoArgs, SdyZonalArgs,
-               SdyMemberSumArgs, SdyMemberStatsArgs, SdySpectrumArgs)
+               SdyMemberSumArgs, SdyMemberStatsArgs, SdySpectrumArgs, SdyRankHistArgs)
 
 # name -> (restype, argtypes); every symbol include/sdy_amd.h declares
 SIGNATURES = {
@@ -412,6 +426,8 @@ SIGNATURES = {
     "sdy_member_stats_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "sdy_degree_power": (C.c_int, [C.POINTER(SdySpectrumArgs), C.c_void_p]),
     "sdy_degree_power_host": (C.c_int, [C.POINTER(SdySpectrumArgs)]),
+    "sdy_rank_hist_accumulate": (C.c_int, [C.POINTER(SdyRankHistArgs), C.c_void_p]),
+    "sdy_rank_hist_accumulate_host": (C.c_int, [C.POINTER(SdyRankHistArgs)]),
     "sdy_profile_enable": (C.c_int, [C.c_int]),
     "sdy_profile_stage_count": (C.c_int, []),
     "sdy_profile_stage_name": (C.c_char_p, [C.c_int]),

@@ -17,6 +17,7 @@ import torch
 
 from ._lib import SdyVideoArgs, SdyZonalArgs, aligned, check, current_stream, lib, ptr
 from .member_mean import EnsembleTimeMeanAggregator
+from .rank_hist import RankHistogramAggregator
 from .spectrum import PowerSpectrumAggregator
 from .windows import FieldAccumulator, TorchDistributed, fill_window, whole_ics_message, window_layouts  # noqa: F401
 
@@ -570,7 +571,12 @@ class InferenceAggregator:
     member and the statistics the reference's full-rollout evaluation takes of them (`rmse_member_avg`, `bias_member_avg`,
     `rmse`, `bias`, `crps` per variable; with `ensemble_time_mean_spread=True` also `spread` and `ssr`), under
     `<label>/time_mean_ensemble/...`; the maps are read with `get_ensemble_time_mean_maps()`.  Off by default: the default
-    key set of the logs does not change."""
+    key set of the logs does not change.
+
+    `rank_histogram_data=True` adds `rank_histogram` (`sdy_amd.RankHistogramAggregator`): per variable, lead time and latitude
+    the counts of the truth's rank among the members (`rank_histogram_pool_times=True`: one slot for all lead times), read
+    with `get_rank_histogram_data()`, and `reliability_index`, `outlier_fraction` and `tie_fraction` per variable under
+    `<label>/rank_histogram/...`.  Off by default as well; meaningful with more than one member (one member: two bins)."""
 
     accepts_sample_weights = True
 
@@ -580,7 +586,8 @@ class InferenceAggregator:
                  device=None, grad_mag_percent_diff: bool = False, video_data: bool = False,
                  extended_video_data: bool = False, zonal_mean_data: bool = False, power_spectrum_data: bool = False,
                  spectrum_grid: str = "equiangular", ensemble_time_mean_data: bool = False,
-                 ensemble_time_mean_spread: bool = False):
+                 ensemble_time_mean_spread: bool = False, rank_histogram_data: bool = False,
+                 rank_histogram_pool_times: bool = False):
         if log_video or enable_extended_videos or log_zonal_mean_images:
             raise NotImplementedError("video / zonal-mean image logging is out of scope of sdy_amd (DESIGN.md section 8)")
         if n_timesteps is None:
@@ -608,6 +615,9 @@ class InferenceAggregator:
         if ensemble_time_mean_data or ensemble_time_mean_spread:
             self._aggregators["time_mean_ensemble"] = EnsembleTimeMeanAggregator(
                 area_weights, dist=dist, metadata=metadata, spread=ensemble_time_mean_spread)
+        if rank_histogram_data:
+            self._aggregators["rank_histogram"] = RankHistogramAggregator(
+                area_weights, n_timesteps=n_timesteps, pool_times=rank_histogram_pool_times, dist=dist, metadata=metadata)
 
     @torch.no_grad()
     def record_batch(self, loss, target_data, gen_data, target_data_norm, gen_data_norm, i_time_start: int = 0,
@@ -647,6 +657,10 @@ class InferenceAggregator:
     def get_ensemble_time_mean_maps(self):
         """`EnsembleTimeMeanAggregator.time_mean_maps()` of the run (`ensemble_time_mean_data=True`)."""
         return self._aggregators["time_mean_ensemble"].time_mean_maps()
+
+    def get_rank_histogram_data(self):
+        """`RankHistogramAggregator.get_data()` of the run (`rank_histogram_data=True`)."""
+        return self._aggregators["rank_histogram"].get_data()
 
     def get_power_spectrum_data(self):
         """`PowerSpectrumAggregator.get_data()` of the run (`power_spectrum_data=True`)."""
