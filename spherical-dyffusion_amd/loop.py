@@ -33,6 +33,7 @@ returning a dict works too.
 """
 from __future__ import annotations
 
+import contextlib
 import queue
 import threading
 import time
@@ -155,6 +156,19 @@ class WindowStitcher:
                 ic = self._carry_target[k].to(v.device)
                 v[:, 0] = ic if ic_rows is None else ic.index_select(0, ic_rows)
 
+    def carried_state(self, names: List[str]) -> torch.Tensor:
+        """The carried generated state of a ONE-ROW stitcher as the (variables, H, W) tensor a relay hands over, variables
+        in the order of `names`."""
+        return torch.stack([self._carry_gen[k][0] for k in names], dim=0)
+
+    def resume(self, i_time: int, names: List[str], state: torch.Tensor, last_target: Mapping[str, torch.Tensor]) -> None:
+        """Positions a one-row stitcher where a window begins whose predecessors ran elsewhere: `i_time` is the time index
+        the writer is at (window w of T steps: w T + 1), `state` what `carried_state(names)` gave there, `last_target`
+        (name -> (1, H, W)) the last time step of the previous window's data for this trajectory's initial condition."""
+        self.i_time = i_time
+        self._carry_gen = {k: state[j:j + 1] for j, k in enumerate(names)}
+        self._carry_target = dict(last_target)
+
 
 def _remove_ic(d: Mapping[str, torch.Tensor], ensemble: bool) -> Dict[str, torch.Tensor]:
     return {k: (v[:, :, 1:] if ensemble else v[:, 1:]) for k, v in d.items()}
@@ -266,6 +280,259 @@ class _ChunkedMetrics(Mapping):
         return len(self._resolve())
 
 
+def _cat_parts(parts: List[Tuple[int, SteppedData]], name: str) -> Dict[str, torch.Tensor]:
+    return {k: torch.cat([getattr(s, name)[k] for _, s in parts], dim=0) for k in getattr(parts[0][1], name)}
+
+
+def _run_chunks(stepper, batch: Mapping[str, torch.Tensor], start: int, n_steps: int, max_batch: Optional[int] = None,
+                calls0=None) -> SteppedData:
+    """One window of the flat `batch` (row r = global trajectory start + r) through the stepper, at most `max_batch` rows per
+    device batch.  Every chunk gets its own `batch_offset` and, with `calls0`, replays the window's call numbers of the
+    dropout streams; a single chunk returns the stepper's object untouched, several are concatenated."""
+    module = stepper.module
+    n_rows = next(iter(batch.values())).shape[0]
+    step = n_rows if max_batch is None else min(n_rows, int(max_batch))
+    parts = []
+    for r0 in range(0, n_rows, step):
+        r1 = min(n_rows, r0 + step)
+        if hasattr(module, "set_batch_offset"):
+            module.set_batch_offset(start + r0)
+        if calls0 is not None:
+            module.set_dropout_calls(calls0)
+        chunk = batch if (r0 == 0 and r1 == n_rows) else {k: v[r0:r1] for k, v in batch.items()}
+        parts.append((r1 - r0, stepper.run_on_batch(chunk, None, n_forward_steps=n_steps, defer_metrics=True)))
+    if len(parts) == 1:
+        return parts[0][1]
+    return SteppedData(metrics=_ChunkedMetrics([(r, s.metrics) for r, s in parts]), gen_data=_cat_parts(parts, "gen_data"),
+                       target_data=batch, gen_data_norm=_cat_parts(parts, "gen_data_norm"),
+                       target_data_norm=_cat_parts(parts, "target_data_norm"))
+
+
+def _unfold_members(d: Mapping[str, torch.Tensor], n_sample: int, members: int) -> Dict[str, torch.Tensor]:
+    return {k: v.view(n_sample, members, *v.shape[1:]).transpose(0, 1) for k, v in d.items()}
+
+
+def _present(win: Mapping[str, torch.Tensor], stepped: SteppedData, plan, members: int, derive: Optional[Callable],
+             i_time: int, times):
+    """What writer and aggregator see of a stepped flat batch (tensor views and index ops only, on any device).
+
+    `win`: the window's tensors, name -> (n_sample, time, H, W); `plan`: the `plan_rows` result the batch was laid out by.
+    A rectangular share is presented like the reference: members unfolded on a leading axis (a strided view, no copy).  A
+    ragged share stays flat, with the targets of the initial conditions touched and `weights`: the share of each touched
+    initial condition's members that runs in THIS batch, i.e. what its targets weigh in a mean over batches and ranks (an
+    initial condition cut by a shard boundary is touched more than once).  `derive` is applied before the first time of a
+    later window (`i_time` > 0) is dropped (`_inference_internal_loop`, `loop.py:120-153`).
+    Returns (SteppedData, i_time_agg, weights or None, times to write, start_sample, last generated state per row)."""
+    start, n_rows, ic_list, _, rect = plan
+    stacked = rect and members > 1
+    last_state = {k: v[:, -1] for k, v in stepped.gen_data.items()}
+    weights = None
+    if rect:
+        ics, first = slice(None), slice(0, n_rows, members)
+    else:
+        touched = list(range(ic_list[0], ic_list[-1] + 1))
+        ics = slice(touched[0], touched[-1] + 1)
+        first = torch.tensor([ic_list.index(c) for c in touched], device=next(iter(last_state.values())).device)
+        weights = [ic_list.count(c) / members for c in touched]
+    win_t = {k: v[ics] for k, v in win.items()}
+    target_data = derive(win_t) if derive is not None else win_t
+    gen_data, gen_norm = stepped.gen_data, stepped.gen_data_norm
+    if stacked:
+        n_sample = next(iter(win.values())).shape[0]
+        gen_data, gen_norm = _unfold_members(gen_data, n_sample, members), _unfold_members(gen_norm, n_sample, members)
+    if derive is not None:
+        gen_data = derive(gen_data)
+    tgt_norm = {k: v[first] for k, v in stepped.target_data_norm.items()}
+    if i_time > 0:
+        gen_data, gen_norm = _remove_ic(gen_data, stacked), _remove_ic(gen_norm, stacked)
+        target_data, tgt_norm = _remove_ic(target_data, False), _remove_ic(tgt_norm, False)
+        if times is not None and hasattr(times, "isel"):
+            times = times.isel(time=slice(1, None))
+    out = SteppedData(metrics=stepped.metrics, gen_data=gen_data, target_data=target_data, gen_data_norm=gen_norm,
+                      target_data_norm=tgt_norm)
+    return out, i_time + (1 if i_time > 0 else 0), weights, times, (0 if rect else start), last_state
+
+
+class _DropoutCalls:
+    """The dropout call numbers a window starts from.  `replay` (a relay is hosted: relay work in between moves the module's
+    counters) numbers window w as origin + w x the calls of one window -- the origin being the module's counters at entry,
+    the calls of one window learned from the first resident batch; otherwise a window starts from wherever the module's
+    counters stand.  A module without counters gives None throughout."""
+
+    def __init__(self, module, replay: bool = True):
+        self.module, self.replay, self.delta = module, replay, None
+        self.origin = tuple(module.dropout_calls()) if hasattr(module, "dropout_calls") else None
+
+    def at(self, w: int):
+        if self.origin is None:
+            return None
+        if w == 0 and self.replay:
+            return self.origin
+        if not self.replay or self.delta is None:
+            return self.module.dropout_calls()
+        return tuple(b + w * d for b, d in zip(self.origin, self.delta))
+
+    def learn(self, calls0) -> None:
+        """A resident batch that started from `calls0` has just been enqueued."""
+        if self.origin is not None and self.delta is None:
+            self.delta = tuple(b - a for a, b in zip(calls0, self.module.dropout_calls()))
+
+
+class _Handover:
+    """The queue between the device batches and writer / aggregator.  A batch reaches them only after its loss terms and the
+    device's sticky status word have arrived: a window a kernel flagged (fp16 range overflow, non-finite statistics) raises
+    here, before either sees it.  With `depth` 1 batch k - 1 is handed over when batch k has been enqueued (its loss arrived
+    long ago, the device is busy with batch k meanwhile: no drain); with 0 at once."""
+
+    def __init__(self, aggregator, depth: int):
+        self.aggregator, self.depth = aggregator, depth
+        self.pending: List[tuple] = []
+
+    def add(self, entry) -> None:
+        self.pending.append(entry)
+        self.drain(self.depth)
+
+    def drain(self, keep: int = 0) -> None:
+        while len(self.pending) > keep:
+            out, i_time_agg, weights, write = self.pending.pop(0)
+            loss = float(out.metrics["loss"])      # waits for the window's read-back; raises SdyError on a flagged window
+            write()
+            weighted = weights is not None and getattr(self.aggregator, "accepts_sample_weights", False)
+            kw = {"sample_weights": weights} if weighted else {}
+            self.aggregator.record_batch(loss=loss, target_data=out.target_data, gen_data=out.gen_data,
+                                         target_data_norm=out.target_data_norm, gen_data_norm=out.gen_data_norm,
+                                         i_time_start=i_time_agg, **kw)
+
+
+class _Run:
+    """The fixed arguments of one `run_inference` call and what it accumulates: the timers, the device spans of its batches
+    and the trajectory steps it advanced."""
+
+    def __init__(self, stepper, dev: torch.device, members: int, steps: int, trajectory_offset: int,
+                 max_batch: Optional[int], derive: Optional[Callable]):
+        self.stepper, self.dev, self.members, self.steps = stepper, dev, members, steps
+        self.trajectory_offset, self.max_batch, self.derive = trajectory_offset, max_batch, derive
+        self.timers: Dict[str, float] = defaultdict(float)
+        self.t_begin = self.now = time.time()
+        self.device_spans = []     # (start event, end event) around each batch's device work
+        self.unit_steps = 0        # trajectories x forecast steps advanced by this process
+
+    def lap(self, key: str) -> None:
+        self.timers[key] += time.time() - self.now
+        self.now = time.time()
+
+    @contextlib.contextmanager
+    def relay_time(self):
+        """Host time of the hosted relay windows: booked as `relay_host` and kept out of the lap around it (the device time
+        of their batches is part of `run_on_batch`)."""
+        t = time.time()
+        yield
+        spent = time.time() - t
+        self.timers["relay_host"] += spent
+        self.now += spent
+
+    def advance(self, window, win, i: int, rows_range, stitch: WindowStitcher, calls0):
+        """One device batch of window i: the global trajectories `rows_range` (None: every member of every initial condition
+        present) through the stepper, stitched by `stitch`; `calls0`: the dropout call counters window i starts from.
+        Returns the `_Handover` entry."""
+        cur = torch.cuda.current_stream(self.dev)
+        ev0 = torch.cuda.Event(enable_timing=True)
+        ev0.record(cur)
+        plan = plan_rows(next(iter(win.values())).shape[0], self.members, self.trajectory_offset, rows_range)
+        start, n_rows, ic_list, _, rect = plan
+        ic_rows = torch.tensor(ic_list, dtype=torch.long, device=self.dev)
+        # IC-major batch: row r is global trajectory start + r = (IC ic_rows[r], member (start + r) % members)
+        batch = {k: v.index_select(0, ic_rows) for k, v in win.items()}
+        # the stitcher carries targets for the initial conditions this process touches (all of them unless ragged)
+        stitch.apply_initial_condition(batch, ic_rows if rect else ic_rows - ic_list[0])
+        stepped = _run_chunks(self.stepper, batch, start, self.steps, self.max_batch, calls0)
+        out, i_time_agg, weights, times, start_sample, last_state = _present(win, stepped, plan, self.members, self.derive,
+                                                                             i * self.steps, window.times)
+        ev1 = torch.cuda.Event(enable_timing=True)
+        ev1.record(cur)
+        self.device_spans.append((ev0, ev1))
+        self.unit_steps += n_rows * self.steps
+        # the carry-over for window i + 1 is taken now; the hand-off to the writer waits for the window's status word
+        write = stitch.append(out.target_data, out.gen_data, times, last_state=last_state, start_sample=start_sample,
+                              defer_write=True)
+        return out, i_time_agg, weights, write
+
+    def finish(self) -> Dict[str, float]:
+        timers, unit_steps = self.timers, self.unit_steps
+        torch.cuda.current_stream(self.dev).synchronize()
+        timers["writer_and_aggregator"] += time.time() - self.now
+        timers["run_on_batch"] = sum(a.elapsed_time(b) for a, b in self.device_spans) * 1e-3     # device time of the batches
+        wall = time.time() - self.t_begin
+        timers["wall"] = wall
+        timers["trajectory_steps"] = float(unit_steps)         # trajectories x forecast steps this process advanced
+        if wall > 0:
+            # the reference logs n_forward_steps x n_ICs over the whole duration (inference.py:294-298); here: x trajectories
+            timers["forecast_steps_per_second"] = unit_steps / wall
+        if timers["run_on_batch"] > 0:
+            timers["forecast_steps_per_second_run_on_batch"] = unit_steps / timers["run_on_batch"]
+        for name, duration in timers.items():
+            print(f"{name}: {duration:.2f}" + ("" if ("per_second" in name or name == "trajectory_steps") else "s"))
+        return dict(timers)
+
+
+class _RelayHost:
+    """This rank's slices of the relayed remainder trajectories (`ensemble.RelayRunner` drives `_step` at window boundaries):
+    the windows some hosted slice still has to go through, one stitcher per trajectory hosted right now, and the state that
+    travels (`WindowStitcher.carried_state` of the generated variables)."""
+
+    def __init__(self, run: _Run, relay, comm, writer, n_forward_steps: int, handover: _Handover, calls: _DropoutCalls):
+        from . import ensemble
+
+        self.run, self.writer, self.n_forward_steps, self.handover, self.calls = run, writer, n_forward_steps, handover, calls
+        self.n_windows = n_forward_steps // run.steps
+        self.names: List[str] = list(run.stepper.out_names)
+        self.retained: Dict[int, tuple] = {}   # window index -> (window, device tensors, last time step of the window before)
+        self.stitchers: Dict[int, WindowStitcher] = {}
+        self.last_step = None      # last time step of the previous window's data (a relay trajectory's carried targets)
+        # (only a rank that hosts a slice gets here: a default comm for EVERY rank of a relay= job belongs in run_inference)
+        comm = comm if comm is not None else ensemble.RelayComm(device=run.dev)
+        self.runner = ensemble.RelayRunner(relay, comm, self._step, lambda task: None, self._state_like)
+
+    def _state_like(self, task):
+        any_win = next(iter(self.retained.values()))[1]
+        h, wd = next(iter(any_win.values())).shape[-2:]
+        return torch.empty(len(self.names), h, wd, dtype=torch.float32, device=self.run.dev)
+
+    def _step(self, task, w: int, state):
+        run = self.run
+        window, win, prev_last = self.retained[w]
+        st = self.stitchers.get(task.unit)
+        if st is None:              # the trajectory arrives here: a stitcher that stands where window w begins
+            st = self.stitchers[task.unit] = WindowStitcher(self.n_forward_steps, self.writer, is_ensemble=run.members > 1)
+            if w > 0:
+                ic = task.unit // run.members - run.trajectory_offset
+                st.resume(w * run.steps + 1, self.names, state, {k: v[ic:ic + 1] for k, v in prev_last.items()})
+        # (the window's own call numbers; the resident batch sets its own again at its next window)
+        self.handover.add(run.advance(window, win, w, (task.unit, 1), st, self.calls.at(w)))
+        if w + 1 >= task.w_end:          # the slice ends: what travels is the stitcher's carried generated state
+            self.stitchers.pop(task.unit)
+            return st.carried_state(self.names) if w + 1 < self.n_windows else None
+        return state
+
+    def after_window(self, i: int, window, win) -> None:
+        """Window i has been loaded and the resident batch advanced through it.  The window stays (its device tensors, with
+        the last time step of the window before it) while some hosted slice still has to go through it: a slice whose state
+        has not arrived yet catches up later."""
+        if i in self.runner.pending_windows():
+            self.retained[i] = (window, win, self.last_step)
+        self.last_step = {k: v[:, -1].clone() for k, v in win.items()}
+        with self.run.relay_time():
+            self.runner.after_window(i)
+            keep = self.runner.pending_windows()
+            for w in [w for w in self.retained if w not in keep]:
+                del self.retained[w]
+
+    def drain(self) -> None:
+        with self.run.relay_time():
+            self.runner.drain(self.n_windows - 1)
+        self.run.timers["relay_recv_wait"] = getattr(self.runner.comm, "recv_wait_s", 0.0)
+
+
 def run_inference(aggregator, stepper, data, n_forward_steps: int, forward_steps_in_memory: int,
                   n_ensemble_members: int = 1, eval_device=None, writer=None, derive: Optional[Callable] = None,
                   host_outputs: bool = False, trajectory_offset: int = 0,
@@ -291,7 +558,10 @@ def run_inference(aggregator, stepper, data, n_forward_steps: int, forward_steps
         once it has loaded that window itself and the state is there (`ensemble.RelayRunner`: lockstep with catch-up), so the
         loader is consumed in order and no rank waits before the end of the job.  Relay rows reach writer / aggregator as
         flat one-row batches (`start_sample` = the trajectory's global index), window by window, from whichever rank hosts
-        them; the windows must hold the relay trajectories' initial conditions as well.
+        them; the windows must hold the relay trajectories' initial conditions as well.  EVERY RANK MUST ENTER WITH THE SAME
+        dropout call counters (`stepper.module.dropout_calls()`): window w replays the counters at entry + w x the calls of
+        one window, so ranks that differ there (warm-up runs differ per rank) give a relayed trajectory whose stream jumps
+        at every hand-over.  `tools/c4_rollout.py` resets them with `set_dropout_calls((0, 0))`; nothing here checks it.
     Without `unit_range` / `relay` every member of every initial condition present runs and predictions are presented as the
     reference stacks them: `(members, n_sample, time, H, W)`.
 
@@ -307,7 +577,6 @@ def run_inference(aggregator, stepper, data, n_forward_steps: int, forward_steps
     writer = writer if writer is not None else NullDataWriter()
     aggregator = aggregator if aggregator is not None else NullAggregator()
     members = int(n_ensemble_members)
-    ens = members > 1
     dev = torch.device(eval_device) if eval_device is not None else torch.device("cuda", torch.cuda.current_device())
     if dev.type != "cuda":
         raise RuntimeError("sdy_amd.run_inference runs on the GPU only (no CPU fallback)")
@@ -321,223 +590,39 @@ def run_inference(aggregator, stepper, data, n_forward_steps: int, forward_steps
         unit_range = (relay.start, relay.count)
     if host_outputs:
         writer = _DeferredHostWriter(writer, dev)
-    stitcher = WindowStitcher(n_forward_steps, writer, is_ensemble=ens)
+    stitcher = WindowStitcher(n_forward_steps, writer, is_ensemble=members > 1)
     loader = data.loader if hasattr(data, "loader") else data
-    timers: Dict[str, float] = defaultdict(float)
-    t_begin = now = time.time()
-    module = stepper.module
+    run = _Run(stepper, dev, members, forward_steps_in_memory, trajectory_offset, max_batch, derive)
     prefetcher = _WindowPrefetcher(loader, dev, prefetch) if prefetch > 0 else None
     windows = prefetcher if prefetcher is not None else _sync_windows(loader, dev)
-    device_spans = []          # (start event, end event) around each batch's device work
-    pending: List[tuple] = []  # record_batch calls waiting for THEIR loss terms (flushed one batch later: no drain)
-    unit_steps = 0             # trajectories x forecast steps advanced by this process
-
-    def flush(p):
-        # A window reaches the writer and the aggregator only after its loss terms and the device's sticky status word have
-        # arrived: a window a kernel flagged (fp16 range overflow, non-finite statistics) raises HERE, before either sees it.
-        out, i_time_agg, weights, write = p
-        loss = float(out.metrics["loss"])      # waits for the window's read-back; raises SdyError on a flagged window
-        write()
-        kw = {"sample_weights": weights} if (weights is not None and getattr(aggregator, "accepts_sample_weights", False)) \
-            else {}
-        aggregator.record_batch(loss=loss, target_data=out.target_data, gen_data=out.gen_data,
-                                target_data_norm=out.target_data_norm, gen_data_norm=out.gen_data_norm,
-                                i_time_start=i_time_agg, **kw)
-
-    def hand_over(entry):
-        # batch k - 1: its loss arrived long ago; the device is busy with batch k meanwhile
-        pending.append(entry)
-        while len(pending) > (1 if prefetch > 0 else 0):
-            flush(pending.pop(0))
-
-    def advance(window, win, i, rows_range, stitch, calls0):
-        """One device batch of window i: the global trajectories `rows_range` (None: every member of every initial condition
-        present) through the stepper, stitched by `stitch`; `calls0`: the dropout call counters window i starts from."""
-        nonlocal unit_steps
-        i_time = i * forward_steps_in_memory
-        cur = torch.cuda.current_stream(dev)
-        ev0 = torch.cuda.Event(enable_timing=True)
-        ev0.record(cur)
-        n_sample = next(iter(win.values())).shape[0]
-        start, n_rows, ic_list, _, rect = plan_rows(n_sample, members, trajectory_offset, rows_range)
-        ic_rows = torch.tensor(ic_list, dtype=torch.long, device=dev)
-        # IC-major batch: row r is global trajectory start + r = (IC ic_rows[r], member (start + r) % members)
-        batch = {k: v.index_select(0, ic_rows) for k, v in win.items()}
-        # the stitcher carries targets for the initial conditions this process touches (all of them unless ragged)
-        stitch.apply_initial_condition(batch, ic_rows if rect else ic_rows - ic_list[0])
-        step = n_rows if max_batch is None else min(n_rows, int(max_batch))
-        parts = []
-        for r0 in range(0, n_rows, step):
-            r1 = min(n_rows, r0 + step)
-            if hasattr(module, "set_batch_offset"):
-                module.set_batch_offset(start + r0)
-            if calls0 is not None:      # every chunk of the window replays the same call numbers of the dropout streams
-                module.set_dropout_calls(calls0)
-            chunk = batch if (r0 == 0 and r1 == n_rows) else {k: v[r0:r1] for k, v in batch.items()}
-            parts.append((r1 - r0, stepper.run_on_batch(chunk, None, n_forward_steps=forward_steps_in_memory,
-                                                        defer_metrics=True)))
-        if len(parts) == 1:
-            stepped = parts[0][1]
-        else:
-            cat = lambda name: {k: torch.cat([getattr(s, name)[k] for _, s in parts], dim=0)  # noqa: E731
-                                for k in getattr(parts[0][1], name)}
-            stepped = SteppedData(metrics=_ChunkedMetrics([(r, s.metrics) for r, s in parts]), gen_data=cat("gen_data"),
-                                  target_data=batch, gen_data_norm=cat("gen_data_norm"),
-                                  target_data_norm=cat("target_data_norm"))
-        del parts
-        last_state = {k: v[:, -1] for k, v in stepped.gen_data.items()}
-        weights = None
-        if rect:       # present like the reference: members on a leading axis (a strided view, no copy)
-            ics = slice(None)
-            unfold = (lambda d: {k: v.view(n_sample, members, *v.shape[1:]).transpose(0, 1) for k, v in d.items()}) \
-                if ens else (lambda d: d)
-            first = slice(0, n_rows, members)
-        else:          # a ragged share: flat rows, targets of the initial conditions touched
-            ics = slice(ic_list[0], ic_list[-1] + 1)
-            unfold = lambda d: d  # noqa: E731
-            touched = list(range(ic_list[0], ic_list[-1] + 1))
-            first = torch.tensor([ic_list.index(c) for c in touched], device=dev)
-            # share of each touched initial condition's members that runs in THIS batch: what its targets weigh in a mean
-            # over batches and ranks (an initial condition cut by a shard boundary is touched more than once)
-            weights = [ic_list.count(c) / members for c in touched]
-        flat = not rect
-        win_t = {k: v[ics] for k, v in win.items()}
-        target_data = derive(win_t) if derive is not None else win_t
-        gen_data, gen_norm = unfold(stepped.gen_data), unfold(stepped.gen_data_norm)
-        if derive is not None:
-            gen_data = derive(gen_data)
-        tgt_norm = {k: v[first] for k, v in stepped.target_data_norm.items()}
-        out = SteppedData(metrics=stepped.metrics, gen_data=gen_data, target_data=target_data, gen_data_norm=gen_norm,
-                          target_data_norm=tgt_norm)
-        ev1 = torch.cuda.Event(enable_timing=True)
-        ev1.record(cur)
-        device_spans.append((ev0, ev1))
-        unit_steps += n_rows * forward_steps_in_memory
-        # ---- _inference_internal_loop (loop.py:120-153)
-        times = window.times
-        stacked = ens and not flat
-        if i_time > 0:
-            out = SteppedData(metrics=out.metrics, gen_data=_remove_ic(out.gen_data, stacked),
-                              target_data={k: v[:, 1:] for k, v in out.target_data.items()},
-                              gen_data_norm=_remove_ic(out.gen_data_norm, stacked),
-                              target_data_norm={k: v[:, 1:] for k, v in out.target_data_norm.items()})
-            if times is not None and hasattr(times, "isel"):
-                times = times.isel(time=slice(1, None))
-            i_time_agg = i_time + 1
-        else:
-            i_time_agg = i_time
-        # the carry-over for window i + 1 is taken now; the hand-off to the writer waits for the window's status word
-        write = stitch.append(out.target_data, out.gen_data, times, last_state=last_state,
-                              start_sample=start if flat else 0, defer_write=True)
-        return out, i_time_agg, weights, write
-
-    # ---- relayed remainder trajectories (ensemble.RelayRunner drives relay_step at window boundaries)
-    runner = None
-    retained: Dict[int, tuple] = {}        # window index -> (window, device tensors, last time step of the window before)
-    calls_base = module.dropout_calls() if hasattr(module, "dropout_calls") else None
-    calls_per_window = None
-
-    def calls_at(w):
-        return tuple(b + w * d for b, d in zip(calls_base, calls_per_window)) if w > 0 else tuple(calls_base)
-
-    if relay is not None and relay.tasks:
-        from . import ensemble
-
-        comm = relay_comm if relay_comm is not None else ensemble.RelayComm(device=dev)
-        relay_stitch: Dict[int, WindowStitcher] = {}
-        gen_names: List[str] = list(stepper.out_names)
-
-        def pack_state(st):        # the stitcher's carried generated state of a one-row batch: (variables, H, W)
-            return torch.stack([st._carry_gen[k][0] for k in gen_names], dim=0)
-
-        def state_like(task):
-            any_win = next(iter(retained.values()))[1]
-            h, wd = next(iter(any_win.values())).shape[-2:]
-            return torch.empty(len(gen_names), h, wd, dtype=torch.float32, device=dev)
-
-        def relay_step(task, w, state):
-            window, win, prev_last = retained[w]
-            st = relay_stitch.get(task.unit)
-            if st is None:          # the trajectory arrives here: a stitcher that stands where window w begins
-                st = relay_stitch[task.unit] = WindowStitcher(n_forward_steps, writer, is_ensemble=ens)
-                if w > 0:
-                    ic = task.unit // members - trajectory_offset
-                    st.i_time = w * forward_steps_in_memory + 1
-                    st._carry_gen = {k: state[j:j + 1] for j, k in enumerate(gen_names)}
-                    st._carry_target = {k: v[ic:ic + 1] for k, v in prev_last.items()}
-            # (the window's own call numbers; the resident batch sets its own again at its next window)
-            hand_over(advance(window, win, w, (task.unit, 1), st, calls_at(w)))
-            if w + 1 >= task.w_end:          # the slice ends: what travels is the stitcher's carried generated state
-                relay_stitch.pop(task.unit)
-                return pack_state(st) if w + 1 < n_windows else None
-            return state
-
-        runner = ensemble.RelayRunner(relay, comm, relay_step, lambda task: None, state_like)
-    n_windows = n_forward_steps // forward_steps_in_memory
-    last_step = None           # last time step of the previous window's data (a relay trajectory's carried targets)
-
+    handover = _Handover(aggregator, depth=1 if prefetch > 0 else 0)
+    hosts_relay = relay is not None and bool(relay.tasks)
+    calls = _DropoutCalls(stepper.module, replay=hosts_relay)
+    relay_host = _RelayHost(run, relay, relay_comm, writer, n_forward_steps, handover, calls) if hosts_relay else None
+    resident = unit_range is None or unit_range[1] > 0
     try:
         for i, (window, win) in enumerate(windows):
-            timers["data_loading"] += time.time() - now
-            now = time.time()
-            calls0 = None
-            if calls_base is not None:
-                # (relay work in between moves the module's counters: with a relay every window starts from its own call
-                #  numbers, base + i x the calls of one window)
-                calls0 = calls_at(i) if (runner is not None and (calls_per_window is not None or i == 0)) \
-                    else module.dropout_calls()
-            if unit_range is None or unit_range[1] > 0:
-                entry = advance(window, win, i, unit_range, stitcher, calls0)
-            else:
-                entry = None
-            if calls_base is not None and calls_per_window is None and entry is not None:
-                calls_per_window = tuple(b - a for a, b in zip(calls0, module.dropout_calls()))
+            run.lap("data_loading")
+            entry = None
+            if resident:
+                calls0 = calls.at(i)
+                entry = run.advance(window, win, i, unit_range, stitcher, calls0)
+                calls.learn(calls0)
             if prefetch <= 0:      # the reference's timer semantics: the window is complete when the clock is read
                 torch.cuda.current_stream(dev).synchronize()
-            timers["run_on_batch_host"] += time.time() - now
-            now = time.time()
+            run.lap("run_on_batch_host")
             if entry is not None:
-                hand_over(entry)
+                handover.add(entry)
                 del entry
-            if runner is not None:
-                # a window some hosted slice still has to go through stays (its device tensors; a slice whose state has not
-                # arrived yet catches up later), with the last time step of the window before it
-                if i in runner.pending_windows():
-                    retained[i] = (window, win, last_step)
-                last_step = {k: v[:, -1].clone() for k, v in win.items()}
-                t_relay = time.time()
-                runner.after_window(i)
-                timers["relay_host"] += time.time() - t_relay      # (host time of the hosted relay windows; the device time
-                keep = runner.pending_windows()                     #  of their batches is part of run_on_batch)
-                for w in [w for w in retained if w not in keep]:
-                    del retained[w]
-                now += time.time() - t_relay
-            timers["writer_and_aggregator"] += time.time() - now
-            now = time.time()
-        if runner is not None:
-            t_relay = time.time()
-            runner.drain(n_windows - 1)
-            timers["relay_host"] += time.time() - t_relay
-            now += time.time() - t_relay
-            timers["relay_recv_wait"] = getattr(runner.comm, "recv_wait_s", 0.0)
-        while pending:
-            flush(pending.pop(0))
+            if relay_host is not None:
+                relay_host.after_window(i, window, win)
+            run.lap("writer_and_aggregator")
+        if relay_host is not None:
+            relay_host.drain()
+        handover.drain()
     finally:
         if prefetcher is not None:
             prefetcher.close()
     if hasattr(writer, "flush"):
         writer.flush()
-    torch.cuda.current_stream(dev).synchronize()
-    timers["writer_and_aggregator"] += time.time() - now
-    timers["run_on_batch"] = sum(a.elapsed_time(b) for a, b in device_spans) * 1e-3     # device time of the batches
-    wall = time.time() - t_begin
-    timers["wall"] = wall
-    timers["trajectory_steps"] = float(unit_steps)         # trajectories x forecast steps this process advanced
-    if wall > 0:
-        # the reference logs n_forward_steps x n_ICs over the whole duration (inference.py:294-298); here: x trajectories
-        timers["forecast_steps_per_second"] = unit_steps / wall
-    if timers["run_on_batch"] > 0:
-        timers["forecast_steps_per_second_run_on_batch"] = unit_steps / timers["run_on_batch"]
-    for name, duration in timers.items():
-        print(f"{name}: {duration:.2f}" + ("" if ("per_second" in name or name == "trajectory_steps") else "s"))
-    return dict(timers)
+    return run.finish()

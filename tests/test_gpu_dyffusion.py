@@ -8,6 +8,7 @@ from conftest import rel_l2
 from helpers import PhiloxMasks, make_pair
 from oracle.dyffusion import OracleDYffusion
 from oracle.sfno import SFNOConfig
+from relay_utils import MailboxComm as _MailboxComm
 
 pytestmark = pytest.mark.gpu
 
@@ -755,27 +756,6 @@ def test_interpolator_pair_with_shared_encoder_equals_two_full_forwards(hack):
                                       with_time_emb=False), 4, 0)
     with pytest.raises(sdy_amd.SdyError):
         net2(torch.zeros(1, 4, 32, 64).cuda(), reuse_encoder=True)
-
-
-class _MailboxComm:
-    """RelayComm stand-in for ranks played one after the other in ONE process (the hosts of a single relay trajectory follow
-    the rank order, so every state is in the box before its receiver runs); the transport itself -- torch.distributed send /
-    recv with the store handshake -- is covered by tests/test_distributed_cpu.py."""
-
-    def __init__(self, box):
-        self.box = box
-
-    def send(self, task, state):
-        self.box[(task.unit, task.w_end)] = state.clone()
-
-    def ready(self, task, like):
-        return (task.unit, task.w_begin) in self.box
-
-    def recv(self, task, like):
-        return self.box.pop((task.unit, task.w_begin))
-
-    def finish(self):
-        pass
 
 
 def test_relayed_remainder_member_equals_the_unsharded_ensemble():
