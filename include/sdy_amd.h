@@ -75,10 +75,11 @@ const char* sdy_error_string(int code);
  * structure below, in header order:
  *   {sdy_conv_args, sdy_mlp_args, sdy_pair_args, sdy_sfno_config, sdy_sfno_fwd_args, sdy_var_table, sdy_step_finish_args,
  *    sdy_derived_args, sdy_corrector_args, sdy_dry_air_args, sdy_hist_args, sdy_coarsen_args, sdy_video_args, sdy_zonal_args,
- *    sdy_member_sum_args, sdy_member_stats_args, sdy_spectrum_args, sdy_rank_hist_args}
+ *    sdy_member_sum_args, sdy_member_stats_args, sdy_spectrum_args, sdy_variability_args, sdy_variability_maps_args,
+ *    sdy_variability_stats_args, sdy_rank_hist_args}
  * SDY_OK when n == SDY_ABI_STRUCTS and every size equals the library's, SDY_ERR_ARG otherwise (the Python bindings do this at
  * import).  sdy_abi_sizes writes the library's own list, for the message of a failed check (SDY_ERR_ARG: n != SDY_ABI_STRUCTS). */
-#define SDY_ABI_STRUCTS 18
+#define SDY_ABI_STRUCTS 21
 int sdy_abi_check(const size_t* sizes, int n);
 int sdy_abi_sizes(size_t* sizes, int n);
 
@@ -907,6 +908,89 @@ typedef struct sdy_spectrum_args {
 } sdy_spectrum_args;
 int sdy_degree_power(const sdy_spectrum_args* args, void* stream);
 int sdy_degree_power_host(const sdy_spectrum_args* args);
+
+/* Per-trajectory time variance and lag-1 autocorrelation at every grid point (no counterpart in the reference): the second
+ * moments along time of a rollout, kept on the device.  A trajectory is a member of a sample, or a sample's target.  For its
+ * counted times x_1 .. x_n (fp32) at one grid point, in run order (csrc/variability.h):
+ *   c = x_1 (fp32),  d_t = (double)x_t - (double)c,  S1 = sum d_t,  S2 = sum d_t d_t,  P = sum_{t >= 2} d_{t-1} d_t,
+ *   last = x_n (fp32).  S1, S2, P are float64; every time's term is added to the running value in ascending time, so the bits
+ *   do not depend on how a run is cut into windows.  The shift by the first value keeps the variance of a field with a large
+ *   mean (surface pressure) to float64 rounding of the deviations.
+ * One launch adds ONE window of all variables to the state:
+ *   window:      see sdy_window, plane = HW: n0 members, n1 samples
+ *   t0:          the first counted time of the window: 1 when the window starts a run (its first time is the initial
+ *                condition), else 0
+ *   first:       non-zero for the first counted window of a run: the state is not read, c = x[t0] and x[t0] has no predecessor;
+ *                zero: the predecessor of x[t0] is the state's `last`
+ *   s1, s2, p:   dev double, contiguous (nvars, n0*n1 + n1, HW) each: row i0*n1 + i1 is member i0 of sample i1, rows n0*n1 + i1
+ *                are the targets
+ *   origin_last: dev float, contiguous (nvars, n0*n1 + n1, HW, 2): the pair (c, last), 8-byte aligned
+ * Exactly one thread owns a state element (no atomics, no LDS): calls on the same state must be ordered on a stream.  The order
+ * of every sum is fixed, so the state is bit-identical to the _host twin's, in any layout, batch and run.  16-byte loads (and
+ * 32-byte accesses of the state) when the window allows them and the state pointers are 32-byte aligned, scalar otherwise.
+ * SDY_ERR_ARG, before anything is launched: NULL args / gen[v] / target[v] / s1 / s2 / p / origin_last, a state pointer not
+ * 8-byte aligned, nvars outside 1..SDY_MAX_VARS, a non-positive n0 / n1 / T / HW, a negative stride, t0 outside 0..T-1.
+ * SDY_ERR_UNSUPPORTED: T*HW > 2^30, n0*n1 >= 2^31, nvars*(n0+1)*n1*HW >= 2^50 (flat state indices are 64-bit).
+ * The _host twin: the same structure with HOST pointers and the same checks; the arithmetic is the header the kernel compiles
+ * (csrc/variability.h), so the semantics can be pinned without a device. */
+typedef struct sdy_variability_args {
+  sdy_window win;
+  int HW;
+  int t0;
+  int first;
+  double *s1, *s2, *p;
+  float* origin_last;
+} sdy_variability_args;
+int sdy_time_variability_accumulate(const sdy_variability_args* args, void* stream);
+int sdy_time_variability_accumulate_host(const sdy_variability_args* args);
+
+/* The state after n_times counted times -> variance and lag-1 autocorrelation, elementwise over n_elems state elements:
+ *   m = S1 / n,  V = max(S2 - S1 m, 0),  variance = V / n (population),
+ *   C = P - m ((S1 - d_n) + S1) + (n - 1) m m  with d_n = (double)last - (double)c  (the lag-1 covariance sum; d_1 = 0),
+ *   lag1 = C / V where n >= 2 and V > 0, NaN otherwise.  A NaN in the state gives NaN in both.
+ *   variance, lag1: dev double (n_elems), overwritten.  Device and _host twin give the same bits.
+ * SDY_ERR_ARG: NULL args or pointer, a pointer not 8-byte aligned, n_elems < 1, n_times not finite and >= 1.
+ * SDY_ERR_UNSUPPORTED: n_elems >= 2^39. */
+typedef struct sdy_variability_maps_args {
+  long n_elems;
+  const double *s1, *s2, *p;
+  const float* origin_last;
+  double n_times;
+  double *variance, *lag1;
+} sdy_variability_maps_args;
+int sdy_time_variability_maps(const sdy_variability_maps_args* args, void* stream);
+int sdy_time_variability_maps_host(const sdy_variability_maps_args* args);
+
+/* Area-weighted sums of the maps above, all variables of one grid in one call (two launches: per-block partials into ws, then
+ * the partials of a variable in block order; no atomics, bit-identical from run to run).
+ *   s1, s2, p, origin_last: the state of M members and n1 samples, (nvars, M*n1 + n1, HW) as above;  n_times: counted times
+ *   weights:  dev float (HW), widened to double
+ *   out:      dev double (nvars, 6), overwritten.  With sum_w = the sum over the n1 samples and the HW grid points of
+ *             weights[p] * (.), per variable:
+ *               out[0] = sum_w mean_m variance_gen            out[1] = sum_w variance_target
+ *               out[2] = sum_w (mean_m sqrt(variance_gen) - sqrt(variance_target))^2
+ *               over the points where n_times >= 2 and the target and every member have V > 0:
+ *               out[3] = sum_w mean_m lag1_gen    out[4] = sum_w lag1_target    out[5] = sum_w
+ *             The caller divides by n1 * sum(weights), or by out[5] (after adding ranks, if any).
+ *   ws:       dev, 8-byte aligned, at least sdy_time_variability_workspace_bytes of (nvars, n1, HW); scratch only
+ * Everything is float64.  The _host twin (ws may be NULL) adds the same per-point terms (csrc/variability.h) in the same blocks
+ * of 256 points, each block in point order where the device uses a butterfly: equal to rounding, not to the bit.
+ * SDY_ERR_ARG, before anything is launched: NULL args / s1 / s2 / p / origin_last / weights / out / ws, a state pointer, out or
+ * ws not 8-byte aligned, a non-positive nvars / M / n1 / HW, n_times not finite and >= 1, ws_bytes too small.
+ * SDY_ERR_UNSUPPORTED: nvars > 65535, n1*HW > 2^30, nvars*(M+1)*n1*HW >= 2^50. */
+typedef struct sdy_variability_stats_args {
+  int nvars, M, n1, HW;
+  const double *s1, *s2, *p;
+  const float* origin_last;
+  const float* weights;
+  double n_times;
+  double* out;
+  void* ws;
+  size_t ws_bytes;
+} sdy_variability_stats_args;
+int sdy_time_variability_stats(const sdy_variability_stats_args* args, void* stream);
+int sdy_time_variability_stats_host(const sdy_variability_stats_args* args);
+size_t sdy_time_variability_workspace_bytes(int nvars, int n1, int HW);   /* 0 for a non-positive argument */
 
 /* Rank (Talagrand) histograms of an ensemble per latitude (no counterpart in the reference): one launch adds ONE window of all
  * variables to float64 accumulators that stay on the device.  window: see sdy_window, plane = H*W: n0 = M members, n1 samples.

@@ -285,6 +285,41 @@ class SdySpectrumArgs(C.Structure):
     ]
 
 
+class SdyVariabilityArgs(C.Structure):
+    _anonymous_ = ("win",)
+    _fields_ = [
+        ("win", SdyWindow), ("HW", C.c_int),
+        ("t0", C.c_int),
+        ("first", C.c_int),
+        ("s1", C.c_void_p), ("s2", C.c_void_p), ("p", C.c_void_p),
+        ("origin_last", C.c_void_p),
+    ]
+
+
+class SdyVariabilityMapsArgs(C.Structure):
+    _fields_ = [
+        ("n_elems", C.c_long),
+        ("s1", C.c_void_p), ("s2", C.c_void_p), ("p", C.c_void_p),
+        ("origin_last", C.c_void_p),
+        ("n_times", C.c_double),
+        ("variance", C.c_void_p), ("lag1", C.c_void_p),
+    ]
+
+
+SDY_TV_SLOTS = 6
+
+
+class SdyVariabilityStatsArgs(C.Structure):
+    _fields_ = [
+        ("nvars", C.c_int), ("M", C.c_int), ("n1", C.c_int), ("HW", C.c_int),
+        ("s1", C.c_void_p), ("s2", C.c_void_p), ("p", C.c_void_p),
+        ("origin_last", C.c_void_p), ("weights", C.c_void_p),
+        ("n_times", C.c_double),
+        ("out", C.c_void_p),
+        ("ws", C.c_void_p), ("ws_bytes", C.c_size_t),
+    ]
+
+
 SDY_RANK_HIST_MAX_MEMBERS = 64
 
 
@@ -302,7 +337,8 @@ class SdyRankHistArgs(C.Structure):
 # every argument structure of include/sdy_amd.h, in header order: what sdy_abi_check compares
 ABI_STRUCTS = (SdyConvArgs, SdyMlpArgs, SdyPairArgs, SdySfnoConfig, SdySfnoFwdArgs, SdyVarTable, SdyStepFinishArgs,
                SdyDerivedArgs, SdyCorrectorArgs, SdyDryAirArgs, SdyHistArgs, SdyCoarsenArgs, SdyVideoArgs, SdyZonalArgs,
-               SdyMemberSumArgs, SdyMemberStatsArgs, SdySpectrumArgs, SdyRankHistArgs)
+               SdyMemberSumArgs, SdyMemberStatsArgs, SdySpectrumArgs, SdyVariabilityArgs, SdyVariabilityMapsArgs,
+               SdyVariabilityStatsArgs, SdyRankHistArgs)
 
 # name -> (restype, argtypes); every symbol include/sdy_amd.h declares
 SIGNATURES = {
@@ -426,6 +462,13 @@ SIGNATURES = {
     "sdy_member_stats_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "sdy_degree_power": (C.c_int, [C.POINTER(SdySpectrumArgs), C.c_void_p]),
     "sdy_degree_power_host": (C.c_int, [C.POINTER(SdySpectrumArgs)]),
+    "sdy_time_variability_accumulate": (C.c_int, [C.POINTER(SdyVariabilityArgs), C.c_void_p]),
+    "sdy_time_variability_accumulate_host": (C.c_int, [C.POINTER(SdyVariabilityArgs)]),
+    "sdy_time_variability_maps": (C.c_int, [C.POINTER(SdyVariabilityMapsArgs), C.c_void_p]),
+    "sdy_time_variability_maps_host": (C.c_int, [C.POINTER(SdyVariabilityMapsArgs)]),
+    "sdy_time_variability_stats": (C.c_int, [C.POINTER(SdyVariabilityStatsArgs), C.c_void_p]),
+    "sdy_time_variability_stats_host": (C.c_int, [C.POINTER(SdyVariabilityStatsArgs)]),
+    "sdy_time_variability_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "sdy_rank_hist_accumulate": (C.c_int, [C.POINTER(SdyRankHistArgs), C.c_void_p]),
     "sdy_rank_hist_accumulate_host": (C.c_int, [C.POINTER(SdyRankHistArgs)]),
     "sdy_profile_enable": (C.c_int, [C.c_int]),

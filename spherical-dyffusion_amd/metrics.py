@@ -19,6 +19,7 @@ from ._lib import SdyVideoArgs, SdyZonalArgs, aligned, check, current_stream, li
 from .member_mean import EnsembleTimeMeanAggregator
 from .rank_hist import RankHistogramAggregator
 from .spectrum import PowerSpectrumAggregator
+from .variability import TimeVariabilityAggregator
 from .windows import FieldAccumulator, TorchDistributed, fill_window, whole_ics_message, window_layouts  # noqa: F401
 
 
@@ -576,7 +577,13 @@ class InferenceAggregator:
     `rank_histogram_data=True` adds `rank_histogram` (`sdy_amd.RankHistogramAggregator`): per variable, lead time and latitude
     the counts of the truth's rank among the members (`rank_histogram_pool_times=True`: one slot for all lead times), read
     with `get_rank_histogram_data()`, and `reliability_index`, `outlier_fraction` and `tie_fraction` per variable under
-    `<label>/rank_histogram/...`.  Off by default as well; meaningful with more than one member (one member: two bins)."""
+    `<label>/rank_histogram/...`.  Off by default as well; meaningful with more than one member (one member: two bins).
+
+    `time_variability_data=True` adds `time_variability` (`sdy_amd.TimeVariabilityAggregator`): per member and for the target
+    the standard deviation along time and the lag-1 autocorrelation at every grid point, read with
+    `get_time_variability_data()`, and `time_std_gen`, `time_std_target`, `time_std_ratio`, `time_std_rmse`, `lag1_gen`,
+    `lag1_target`, `lag1_bias` and `lag1_defined_fraction` per variable under `<label>/time_variability/...`.  Off by default as
+    well; its windows must arrive in run order."""
 
     accepts_sample_weights = True
 
@@ -587,7 +594,7 @@ class InferenceAggregator:
                  extended_video_data: bool = False, zonal_mean_data: bool = False, power_spectrum_data: bool = False,
                  spectrum_grid: str = "equiangular", ensemble_time_mean_data: bool = False,
                  ensemble_time_mean_spread: bool = False, rank_histogram_data: bool = False,
-                 rank_histogram_pool_times: bool = False):
+                 rank_histogram_pool_times: bool = False, time_variability_data: bool = False):
         if log_video or enable_extended_videos or log_zonal_mean_images:
             raise NotImplementedError("video / zonal-mean image logging is out of scope of sdy_amd (DESIGN.md section 8)")
         if n_timesteps is None:
@@ -618,6 +625,8 @@ class InferenceAggregator:
         if rank_histogram_data:
             self._aggregators["rank_histogram"] = RankHistogramAggregator(
                 area_weights, n_timesteps=n_timesteps, pool_times=rank_histogram_pool_times, dist=dist, metadata=metadata)
+        if time_variability_data:
+            self._aggregators["time_variability"] = TimeVariabilityAggregator(area_weights, dist=dist, metadata=metadata)
 
     @torch.no_grad()
     def record_batch(self, loss, target_data, gen_data, target_data_norm, gen_data_norm, i_time_start: int = 0,
@@ -661,6 +670,10 @@ class InferenceAggregator:
     def get_rank_histogram_data(self):
         """`RankHistogramAggregator.get_data()` of the run (`rank_histogram_data=True`)."""
         return self._aggregators["rank_histogram"].get_data()
+
+    def get_time_variability_data(self):
+        """`TimeVariabilityAggregator.get_data()` of the run (`time_variability_data=True`)."""
+        return self._aggregators["time_variability"].get_data()
 
     def get_power_spectrum_data(self):
         """`PowerSpectrumAggregator.get_data()` of the run (`power_spectrum_data=True`)."""
