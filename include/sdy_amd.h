@@ -76,10 +76,10 @@ const char* sdy_error_string(int code);
  *   {sdy_conv_args, sdy_mlp_args, sdy_pair_args, sdy_sfno_config, sdy_sfno_fwd_args, sdy_var_table, sdy_step_finish_args,
  *    sdy_derived_args, sdy_corrector_args, sdy_dry_air_args, sdy_hist_args, sdy_coarsen_args, sdy_video_args, sdy_zonal_args,
  *    sdy_member_sum_args, sdy_member_stats_args, sdy_spectrum_args, sdy_variability_args, sdy_variability_maps_args,
- *    sdy_variability_stats_args, sdy_rank_hist_args}
+ *    sdy_variability_stats_args, sdy_region_series_args, sdy_rank_hist_args}
  * SDY_OK when n == SDY_ABI_STRUCTS and every size equals the library's, SDY_ERR_ARG otherwise (the Python bindings do this at
  * import).  sdy_abi_sizes writes the library's own list, for the message of a failed check (SDY_ERR_ARG: n != SDY_ABI_STRUCTS). */
-#define SDY_ABI_STRUCTS 21
+#define SDY_ABI_STRUCTS 22
 int sdy_abi_check(const size_t* sizes, int n);
 int sdy_abi_sizes(size_t* sizes, int n);
 
@@ -991,6 +991,47 @@ typedef struct sdy_variability_stats_args {
 int sdy_time_variability_stats(const sdy_variability_stats_args* args, void* stream);
 int sdy_time_variability_stats_host(const sdy_variability_stats_args* args);
 size_t sdy_time_variability_workspace_bytes(int nvars, int n1, int HW);   /* 0 for a non-positive argument */
+
+/* Regional area-weighted metric sums (MeanAggregator's eight sums of sdy_ensemble_series, once per region): ONE launch for all
+ * variables and all regions of one window; the member and target values of a grid point are loaded once, whatever n_regions.
+ *   window:    see sdy_window, plane = HW: n0 = M members (1 for a deterministic run), n1 samples
+ *   weights:   dev float, contiguous (n_regions, HW): area weight x the region's fraction of the cell, finite and >= 0
+ *   out:       dev double, contiguous (nvars, n_regions, n1, T, 8), WRITTEN (not accumulated):
+ *                out[v][r][s][t][q] = sum over the grid points i of weights[r][i] * q_i,  q in the order of sdy_ensemble_series:
+ *                (em - y)^2 | unbiased member variance | fair CRPS | em - y | em | em^2 | y | y^2
+ *              with y the target and em the ensemble mean of the point.  M == 1: CRPS = |g - y|, variance 0.  The caller
+ *              divides by the sum of the region's weights.
+ *   ws:        dev, 8-byte aligned, at least sdy_region_series_workspace_bytes of (nvars, n_regions, n1, T, HW); scratch only
+ * Per-point arithmetic (csrc/region_series.h, compiled by the kernel and by the _host twin): float64 throughout and nothing
+ * contracted; em - y = mean_m (g_m - y) and em = y + (em - y): the deviations are taken from the differences to y, which are
+ * exact in float64 for fp32 inputs.
+ * ZERO-WEIGHT RULE: a point whose weight in a region is exactly 0 contributes NOTHING to that region, whatever its values,
+ * NaN and inf included (IEEE's 0 x NaN = NaN is deliberately not followed: an ocean-only field with NaN over land gives finite
+ * sums for a region that is zero over land).  Anywhere else a NaN propagates into the sums it belongs to.
+ * Order of the sums: a plane is cut into chunks of 1024 consecutive grid points (a rule of HW alone); a chunk's four quarters
+ * of 256 points are summed one by one and added in ascending order, the chunks' partials go to ws and are added in ascending
+ * order by a second launch: no atomics, and the 8 * n_regions sums of a plane depend on that plane and the weights only -- the
+ * same bits in any batch, layout (16-byte or scalar loads) and run.  The _host twin adds a quarter's points in point order
+ * where the device adds lane-strided partial sums over a wave: equal to the rounding of a float64 sum, not to the bit.
+ * SDY_ERR_ARG, before anything is launched: NULL args / gen[v] / target[v] / weights / out / ws, out or ws not 8-byte aligned,
+ * nvars outside 1..SDY_MAX_VARS, n_regions outside 1..SDY_REGION_MAX, a non-positive n0 / n1 / T / HW, a negative stride,
+ * ws_bytes too small.  SDY_ERR_UNSUPPORTED: n0 > SDY_REGION_MAX_MEMBERS, T*HW > 2^30, n0*n1 >= 2^31, more than 2^31 - 1
+ * (sample, time, chunk) work items per variable, nvars*n_regions*n1*T*8 >= 2^38 (the grid of the second launch).
+ * The _host twin: the same structure with HOST pointers and the same checks (ws may be NULL). */
+#define SDY_REGION_MAX 16
+#define SDY_REGION_MAX_MEMBERS 64
+typedef struct sdy_region_series_args {
+  sdy_window win;
+  int HW;
+  int n_regions;
+  const float* weights;
+  double* out;
+  void* ws;
+  size_t ws_bytes;
+} sdy_region_series_args;
+int sdy_region_series(const sdy_region_series_args* args, void* stream);
+int sdy_region_series_host(const sdy_region_series_args* args);
+size_t sdy_region_series_workspace_bytes(int nvars, int n_regions, int n1, int T, int HW);   /* 0 for an argument out of range */
 
 /* Rank (Talagrand) histograms of an ensemble per latitude (no counterpart in the reference): one launch adds ONE window of all
  * variables to float64 accumulators that stay on the device.  window: see sdy_window, plane = H*W: n0 = M members, n1 samples.

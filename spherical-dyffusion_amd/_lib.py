@@ -320,6 +320,21 @@ class SdyVariabilityStatsArgs(C.Structure):
     ]
 
 
+SDY_REGION_MAX = 16
+SDY_REGION_MAX_MEMBERS = 64
+
+
+class SdyRegionSeriesArgs(C.Structure):
+    _anonymous_ = ("win",)
+    _fields_ = [
+        ("win", SdyWindow), ("HW", C.c_int),
+        ("n_regions", C.c_int),
+        ("weights", C.c_void_p),
+        ("out", C.c_void_p),
+        ("ws", C.c_void_p), ("ws_bytes", C.c_size_t),
+    ]
+
+
 SDY_RANK_HIST_MAX_MEMBERS = 64
 
 
@@ -338,7 +353,7 @@ class SdyRankHistArgs(C.Structure):
 ABI_STRUCTS = (SdyConvArgs, SdyMlpArgs, SdyPairArgs, SdySfnoConfig, SdySfnoFwdArgs, SdyVarTable, SdyStepFinishArgs,
                SdyDerivedArgs, SdyCorrectorArgs, SdyDryAirArgs, SdyHistArgs, SdyCoarsenArgs, SdyVideoArgs, SdyZonalArgs,
                SdyMemberSumArgs, SdyMemberStatsArgs, SdySpectrumArgs, SdyVariabilityArgs, SdyVariabilityMapsArgs,
-               SdyVariabilityStatsArgs, SdyRankHistArgs)
+               SdyVariabilityStatsArgs, SdyRegionSeriesArgs, SdyRankHistArgs)
 
 # name -> (restype, argtypes); every symbol include/sdy_amd.h declares
 SIGNATURES = {
@@ -469,6 +484,9 @@ SIGNATURES = {
     "sdy_time_variability_stats": (C.c_int, [C.POINTER(SdyVariabilityStatsArgs), C.c_void_p]),
     "sdy_time_variability_stats_host": (C.c_int, [C.POINTER(SdyVariabilityStatsArgs)]),
     "sdy_time_variability_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "sdy_region_series": (C.c_int, [C.POINTER(SdyRegionSeriesArgs), C.c_void_p]),
+    "sdy_region_series_host": (C.c_int, [C.POINTER(SdyRegionSeriesArgs)]),
+    "sdy_region_series_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "sdy_rank_hist_accumulate": (C.c_int, [C.POINTER(SdyRankHistArgs), C.c_void_p]),
     "sdy_rank_hist_accumulate_host": (C.c_int, [C.POINTER(SdyRankHistArgs)]),
     "sdy_profile_enable": (C.c_int, [C.c_int]),

@@ -18,6 +18,7 @@ import torch
 from ._lib import SdyVideoArgs, SdyZonalArgs, aligned, check, current_stream, lib, ptr
 from .member_mean import EnsembleTimeMeanAggregator
 from .rank_hist import RankHistogramAggregator
+from .regions import RegionalMeanAggregator, Regions
 from .spectrum import PowerSpectrumAggregator
 from .variability import TimeVariabilityAggregator
 from .windows import FieldAccumulator, TorchDistributed, fill_window, whole_ics_message, window_layouts  # noqa: F401
@@ -583,7 +584,12 @@ class InferenceAggregator:
     the standard deviation along time and the lag-1 autocorrelation at every grid point, read with
     `get_time_variability_data()`, and `time_std_gen`, `time_std_target`, `time_std_ratio`, `time_std_rmse`, `lag1_gen`,
     `lag1_target`, `lag1_bias` and `lag1_defined_fraction` per variable under `<label>/time_variability/...`.  Off by default as
-    well; its windows must arrive in run order."""
+    well; its windows must arrive in run order.
+
+    `regions=<sdy_amd.Regions>` adds `mean_regional` (`sdy_amd.RegionalMeanAggregator` on the denormalised data): the series of
+    `mean` once per region, `<metric>/<region>/<variable>`, as one more table under `<label>/mean_regional/series`; read with
+    `get_regional_series()`.  A grid point whose weight in a region is 0 contributes nothing to it, NaN values included.  The
+    default `None` adds nothing: the default key set of the logs does not change."""
 
     accepts_sample_weights = True
 
@@ -594,7 +600,8 @@ class InferenceAggregator:
                  extended_video_data: bool = False, zonal_mean_data: bool = False, power_spectrum_data: bool = False,
                  spectrum_grid: str = "equiangular", ensemble_time_mean_data: bool = False,
                  ensemble_time_mean_spread: bool = False, rank_histogram_data: bool = False,
-                 rank_histogram_pool_times: bool = False, time_variability_data: bool = False):
+                 rank_histogram_pool_times: bool = False, time_variability_data: bool = False,
+                 regions: Optional[Regions] = None):
         if log_video or enable_extended_videos or log_zonal_mean_images:
             raise NotImplementedError("video / zonal-mean image logging is out of scope of sdy_amd (DESIGN.md section 8)")
         if n_timesteps is None:
@@ -627,6 +634,9 @@ class InferenceAggregator:
                 area_weights, n_timesteps=n_timesteps, pool_times=rank_histogram_pool_times, dist=dist, metadata=metadata)
         if time_variability_data:
             self._aggregators["time_variability"] = TimeVariabilityAggregator(area_weights, dist=dist, metadata=metadata)
+        if regions is not None:
+            self._aggregators["mean_regional"] = RegionalMeanAggregator(regions, target="denorm", n_timesteps=n_timesteps,
+                                                                        is_ensemble=self._is_ensemble, dist=dist)
 
     @torch.no_grad()
     def record_batch(self, loss, target_data, gen_data, target_data_norm, gen_data_norm, i_time_start: int = 0,
@@ -674,6 +684,10 @@ class InferenceAggregator:
     def get_time_variability_data(self):
         """`TimeVariabilityAggregator.get_data()` of the run (`time_variability_data=True`)."""
         return self._aggregators["time_variability"].get_data()
+
+    def get_regional_series(self):
+        """`RegionalMeanAggregator.get_series()` of the run (`regions=...`)."""
+        return self._aggregators["mean_regional"].get_series()
 
     def get_power_spectrum_data(self):
         """`PowerSpectrumAggregator.get_data()` of the run (`power_spectrum_data=True`)."""
