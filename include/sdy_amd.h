@@ -76,10 +76,10 @@ const char* sdy_error_string(int code);
  *   {sdy_conv_args, sdy_mlp_args, sdy_pair_args, sdy_sfno_config, sdy_sfno_fwd_args, sdy_var_table, sdy_step_finish_args,
  *    sdy_derived_args, sdy_corrector_args, sdy_dry_air_args, sdy_hist_args, sdy_coarsen_args, sdy_video_args, sdy_zonal_args,
  *    sdy_member_sum_args, sdy_member_stats_args, sdy_spectrum_args, sdy_variability_args, sdy_variability_maps_args,
- *    sdy_variability_stats_args, sdy_region_series_args, sdy_rank_hist_args}
+ *    sdy_variability_stats_args, sdy_region_series_args, sdy_event_args, sdy_rank_hist_args}
  * SDY_OK when n == SDY_ABI_STRUCTS and every size equals the library's, SDY_ERR_ARG otherwise (the Python bindings do this at
  * import).  sdy_abi_sizes writes the library's own list, for the message of a failed check (SDY_ERR_ARG: n != SDY_ABI_STRUCTS). */
-#define SDY_ABI_STRUCTS 22
+#define SDY_ABI_STRUCTS 23
 int sdy_abi_check(const size_t* sizes, int n);
 int sdy_abi_sizes(size_t* sizes, int n);
 
@@ -1032,6 +1032,64 @@ typedef struct sdy_region_series_args {
 int sdy_region_series(const sdy_region_series_args* args, void* stream);
 int sdy_region_series_host(const sdy_region_series_args* args);
 size_t sdy_region_series_workspace_bytes(int nvars, int n_regions, int n1, int T, int HW);   /* 0 for an argument out of range */
+
+/* Threshold events of an ensemble: the counts behind Brier score, reliability diagram, ROC curve and exceedance-frequency maps
+ * (no counterpart in the reference).  window: see sdy_window, plane = H*W: n0 = M members, n1 samples.  Every variable of a
+ * call has the same n_events = E events.  Event e of variable v is a threshold c and a direction: a value x is in the event
+ * when x > c, or (bit e of below[v] set) when x < c; both strict, a NaN x is never in it.  A point (sample, time, lat, lon) is
+ * COUNTED for an event when neither its target nor its threshold is NaN; a NaN member is simply not in the event.  Per counted
+ * point k = the number of members in the event (0 .. M) and o = 1 if the target is in it, else 0.  Integers only.
+ * Thresholds (device memory the caller builds once; nothing is copied per call, no address is formed from a value read from
+ * device memory):
+ *   scalars:   dev float, contiguous (nvars, E): the threshold of event e of variable v where bit e of is_map[v] is clear
+ *              (read once per block, not per point; not looked at where the bit is set).  A NaN counts nothing.
+ *   maps:      dev float, contiguous (n_maps, H*W) threshold maps; may be NULL when no is_map bit below E is set.  The map
+ *              events of variable v take the planes map_first[v], map_first[v] + 1, .. in event order; a row of a map is
+ *              loaded once per unit of 4 (or 1) longitudes, not once per member.
+ *   t0, pool_times, t_start, n_slots: as for the rank histograms below: the first time of a run is not counted; t0 == T
+ *              is SDY_OK and launches nothing
+ * sdy_event_table_accumulate:  acc = table, dev double, contiguous (nvars, n_slots, E, H, 2, M + 1), zeroed by the caller:
+ *   table[v, slot, e, lat, o, k] += the counted points of the row's W longitudes, n1 samples (and, pooled, T - t0 times) with
+ *   that (o, k).  One group of lanes owns the accumulator row (v, slot, lat): its E x 2 x (M + 1) bins are 32-bit words in LDS
+ *   (integer LDS atomics) that the owner adds to the accumulators with plain load / add / store; every member value is loaded
+ *   once and tested against all E thresholds.  The rows of a block are capped so that its LDS stays within 64 KB.
+ * sdy_event_frequency_accumulate:  acc = maps, dev double, contiguous (nvars, E, 3, H*W), zeroed by the caller:
+ *   acc[v, e, 0, p] += sum of k, acc[v, e, 1, p] += sum of o, acc[v, e, 2, p] += the counted points, over the n1 samples and
+ *   the T - t0 counted times of grid point p.  One thread owns a grid point (four with 16-byte loads), sums in integer
+ *   registers and touches the accumulator once.  All lead times are pooled: t_start / n_slots / pool_times are checked as for
+ *   the table and otherwise not used.
+ * No global atomics, no second pass; calls on the same accumulators must be ordered on a stream.  Every count is bit-identical
+ * to the _host twin's, in any layout, batch and run.  16-byte loads when W, every stride and every pointer (maps included)
+ * allow them.
+ * SDY_ERR_ARG, before anything is launched: what sdy_window refuses; NULL args / acc / scalars, acc not 8-byte aligned,
+ * n_events outside 1..SDY_EVENT_MAX, a non-positive H / W / n_slots, t0 outside 0..T; not pooled: t_start < 0, t_start + T >
+ * n_slots; pooled: n_slots != 1; a map event with maps == NULL, map_first[v] < 0 or its planes past n_maps.
+ * SDY_ERR_UNSUPPORTED: n0 > SDY_EVENT_MAX_MEMBERS; n_maps*H*W >= 2^40; table: the points of one row in one call (n1*W, pooled:
+ * n1*W*T) >= 2^32 (the row's 32-bit words), n_slots*H >= 2^40, nvars*n_slots*E*H*2*(n0+1) >= 2^50, one row's bins over 64 KB
+ * of LDS; frequency: n0*n1*T >= 2^31 (the 32-bit registers of a point), nvars*E*3*H*W >= 2^50.
+ * The _host twins: the same structure with HOST pointers and the same checks; the arithmetic is the header the kernels
+ * compile (csrc/events.h). */
+#define SDY_EVENT_MAX 8
+#define SDY_EVENT_MAX_MEMBERS 64
+typedef struct sdy_event_args {
+  sdy_window win;
+  int H, W;
+  int t0;
+  int t_start, n_slots;
+  int pool_times;
+  int n_events;
+  int n_maps;
+  unsigned char below[SDY_MAX_VARS];
+  unsigned char is_map[SDY_MAX_VARS];
+  int map_first[SDY_MAX_VARS];
+  const float* scalars;
+  const float* maps;
+  double* acc;
+} sdy_event_args;
+int sdy_event_table_accumulate(const sdy_event_args* args, void* stream);
+int sdy_event_table_accumulate_host(const sdy_event_args* args);
+int sdy_event_frequency_accumulate(const sdy_event_args* args, void* stream);
+int sdy_event_frequency_accumulate_host(const sdy_event_args* args);
 
 /* Rank (Talagrand) histograms of an ensemble per latitude (no counterpart in the reference): one launch adds ONE window of all
  * variables to float64 accumulators that stay on the device.  window: see sdy_window, plane = H*W: n0 = M members, n1 samples.

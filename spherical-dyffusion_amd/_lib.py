@@ -335,6 +335,26 @@ class SdyRegionSeriesArgs(C.Structure):
     ]
 
 
+SDY_EVENT_MAX = 8
+SDY_EVENT_MAX_MEMBERS = 64
+
+
+class SdyEventArgs(C.Structure):
+    _anonymous_ = ("win",)
+    _fields_ = [
+        ("win", SdyWindow), ("H", C.c_int), ("W", C.c_int),
+        ("t0", C.c_int),
+        ("t_start", C.c_int), ("n_slots", C.c_int),
+        ("pool_times", C.c_int),
+        ("n_events", C.c_int),
+        ("n_maps", C.c_int),
+        ("below", C.c_ubyte * SDY_MAX_VARS), ("is_map", C.c_ubyte * SDY_MAX_VARS),
+        ("map_first", C.c_int * SDY_MAX_VARS),
+        ("scalars", C.c_void_p), ("maps", C.c_void_p),
+        ("acc", C.c_void_p),
+    ]
+
+
 SDY_RANK_HIST_MAX_MEMBERS = 64
 
 
@@ -353,7 +373,7 @@ class SdyRankHistArgs(C.Structure):
 ABI_STRUCTS = (SdyConvArgs, SdyMlpArgs, SdyPairArgs, SdySfnoConfig, SdySfnoFwdArgs, SdyVarTable, SdyStepFinishArgs,
                SdyDerivedArgs, SdyCorrectorArgs, SdyDryAirArgs, SdyHistArgs, SdyCoarsenArgs, SdyVideoArgs, SdyZonalArgs,
                SdyMemberSumArgs, SdyMemberStatsArgs, SdySpectrumArgs, SdyVariabilityArgs, SdyVariabilityMapsArgs,
-               SdyVariabilityStatsArgs, SdyRegionSeriesArgs, SdyRankHistArgs)
+               SdyVariabilityStatsArgs, SdyRegionSeriesArgs, SdyEventArgs, SdyRankHistArgs)
 
 # name -> (restype, argtypes); every symbol include/sdy_amd.h declares
 SIGNATURES = {
@@ -487,6 +507,10 @@ SIGNATURES = {
     "sdy_region_series": (C.c_int, [C.POINTER(SdyRegionSeriesArgs), C.c_void_p]),
     "sdy_region_series_host": (C.c_int, [C.POINTER(SdyRegionSeriesArgs)]),
     "sdy_region_series_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "sdy_event_table_accumulate": (C.c_int, [C.POINTER(SdyEventArgs), C.c_void_p]),
+    "sdy_event_table_accumulate_host": (C.c_int, [C.POINTER(SdyEventArgs)]),
+    "sdy_event_frequency_accumulate": (C.c_int, [C.POINTER(SdyEventArgs), C.c_void_p]),
+    "sdy_event_frequency_accumulate_host": (C.c_int, [C.POINTER(SdyEventArgs)]),
     "sdy_rank_hist_accumulate": (C.c_int, [C.POINTER(SdyRankHistArgs), C.c_void_p]),
     "sdy_rank_hist_accumulate_host": (C.c_int, [C.POINTER(SdyRankHistArgs)]),
     "sdy_profile_enable": (C.c_int, [C.c_int]),

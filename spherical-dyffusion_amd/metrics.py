@@ -18,6 +18,7 @@ import torch
 from ._lib import SdyVideoArgs, SdyZonalArgs, aligned, check, current_stream, lib, ptr
 from .member_mean import EnsembleTimeMeanAggregator
 from .rank_hist import RankHistogramAggregator
+from .events import Events, EventVerificationAggregator
 from .regions import RegionalMeanAggregator, Regions
 from .spectrum import PowerSpectrumAggregator
 from .variability import TimeVariabilityAggregator
@@ -589,7 +590,13 @@ class InferenceAggregator:
     `regions=<sdy_amd.Regions>` adds `mean_regional` (`sdy_amd.RegionalMeanAggregator` on the denormalised data): the series of
     `mean` once per region, `<metric>/<region>/<variable>`, as one more table under `<label>/mean_regional/series`; read with
     `get_regional_series()`.  A grid point whose weight in a region is 0 contributes nothing to it, NaN values included.  The
-    default `None` adds nothing: the default key set of the logs does not change."""
+    default `None` adds nothing: the default key set of the logs does not change.
+
+    `events=<sdy_amd.Events>` adds `events` (`sdy_amd.EventVerificationAggregator` on the denormalised data;
+    `event_pool_times=True`: one slot for all lead times, `event_frequency_maps=True`: exceedance-frequency maps too): per
+    variable and event the table of counts behind Brier score, reliability diagram and ROC curve, read with
+    `get_event_data()`, and `brier_score`, `brier_skill_score`, `brier_reliability`, `brier_resolution`, `base_rate`,
+    `forecast_rate` and `roc_area` under `<label>/events/<metric>/<event>/<variable>`.  The default `None` adds nothing."""
 
     accepts_sample_weights = True
 
@@ -601,7 +608,8 @@ class InferenceAggregator:
                  spectrum_grid: str = "equiangular", ensemble_time_mean_data: bool = False,
                  ensemble_time_mean_spread: bool = False, rank_histogram_data: bool = False,
                  rank_histogram_pool_times: bool = False, time_variability_data: bool = False,
-                 regions: Optional[Regions] = None):
+                 regions: Optional[Regions] = None, events: Optional[Events] = None, event_pool_times: bool = False,
+                 event_frequency_maps: bool = False):
         if log_video or enable_extended_videos or log_zonal_mean_images:
             raise NotImplementedError("video / zonal-mean image logging is out of scope of sdy_amd (DESIGN.md section 8)")
         if n_timesteps is None:
@@ -637,6 +645,10 @@ class InferenceAggregator:
         if regions is not None:
             self._aggregators["mean_regional"] = RegionalMeanAggregator(regions, target="denorm", n_timesteps=n_timesteps,
                                                                         is_ensemble=self._is_ensemble, dist=dist)
+        if events is not None:
+            self._aggregators["events"] = EventVerificationAggregator(
+                events, area_weights, n_timesteps=n_timesteps, pool_times=event_pool_times,
+                frequency_maps=event_frequency_maps, dist=dist, metadata=metadata)
 
     @torch.no_grad()
     def record_batch(self, loss, target_data, gen_data, target_data_norm, gen_data_norm, i_time_start: int = 0,
@@ -684,6 +696,10 @@ class InferenceAggregator:
     def get_time_variability_data(self):
         """`TimeVariabilityAggregator.get_data()` of the run (`time_variability_data=True`)."""
         return self._aggregators["time_variability"].get_data()
+
+    def get_event_data(self):
+        """`EventVerificationAggregator.get_data()` of the run (`events=...`)."""
+        return self._aggregators["events"].get_data()
 
     def get_regional_series(self):
         """`RegionalMeanAggregator.get_series()` of the run (`regions=...`)."""
