@@ -76,10 +76,10 @@ const char* sdy_error_string(int code);
  *   {sdy_conv_args, sdy_mlp_args, sdy_pair_args, sdy_sfno_config, sdy_sfno_fwd_args, sdy_var_table, sdy_step_finish_args,
  *    sdy_derived_args, sdy_corrector_args, sdy_dry_air_args, sdy_hist_args, sdy_coarsen_args, sdy_video_args, sdy_zonal_args,
  *    sdy_member_sum_args, sdy_member_stats_args, sdy_spectrum_args, sdy_variability_args, sdy_variability_maps_args,
- *    sdy_variability_stats_args, sdy_region_series_args, sdy_event_args, sdy_rank_hist_args}
+ *    sdy_variability_stats_args, sdy_region_series_args, sdy_event_args, sdy_member_gram_args, sdy_rank_hist_args}
  * SDY_OK when n == SDY_ABI_STRUCTS and every size equals the library's, SDY_ERR_ARG otherwise (the Python bindings do this at
  * import).  sdy_abi_sizes writes the library's own list, for the message of a failed check (SDY_ERR_ARG: n != SDY_ABI_STRUCTS). */
-#define SDY_ABI_STRUCTS 23
+#define SDY_ABI_STRUCTS 24
 int sdy_abi_check(const size_t* sizes, int n);
 int sdy_abi_sizes(size_t* sizes, int n);
 
@@ -1090,6 +1090,49 @@ int sdy_event_table_accumulate(const sdy_event_args* args, void* stream);
 int sdy_event_table_accumulate_host(const sdy_event_args* args);
 int sdy_event_frequency_accumulate(const sdy_event_args* args, void* stream);
 int sdy_event_frequency_accumulate_host(const sdy_event_args* args);
+
+/* The area-weighted Gram matrix of the member errors and the truth anomaly (no counterpart in the reference): what the energy
+ * score, the member-to-member and member-to-truth distances of whole fields and the anomaly correlation are read from.  ONE
+ * launch for all variables of one window.  window: see sdy_window, plane = HW: n0 = M members (1 for a deterministic run), n1
+ * samples.  For one (variable v, sample s, time t), with g_m the members, y the target, w the weights and c the climatology,
+ * N = M + 2 float64 vectors over the grid points p:
+ *   a_0(p) = 1      a_{1+m}(p) = (double)g_m(p) - (double)y(p)      a_{M+1}(p) = (double)y(p) - (double)c(p)
+ *   Gamma[i][j] = sum_p w(p) a_i(p) a_j(p),  0 <= i <= j < N
+ * The differences are exact in float64; the errors, not the fields, enter, so that a squared distance Gamma_ii + Gamma_jj -
+ * 2 Gamma_ij does not cancel the field's own magnitude.
+ *   weights:     dev float, contiguous (HW): area weights, finite and >= 0, not normalised (Gamma[0][0] is their sum)
+ *   climatology: per variable dev float, contiguous (HW), or NULL: c = 0 (the same bits as a map of zeros)
+ *   out:         dev double, contiguous (nvars, n1, T, N (N + 1) / 2), WRITTEN: the packed upper triangle, row-major in (i, j >=
+ *                i): entry (i, j) at i N - i (i - 1) / 2 + (j - i) (sdy_gram_index, csrc/member_gram.h)
+ *   ws:          dev, 8-byte aligned, at least sdy_member_gram_workspace_bytes of (nvars, n0, n1, T, HW); scratch only
+ * ZERO-WEIGHT RULE: a point with w(p) == 0 contributes NOTHING, NaN and inf included: every a_i of that point reads as 0, it
+ * is not multiplied by 0.  Anywhere else a NaN propagates into every entry it touches and into no other: a NaN in member m
+ * poisons the entries with index 1 + m (its row and its column).
+ * Order of the sums: a plane is cut into chunks of 1024 consecutive grid points (a rule of HW alone) and a chunk into four
+ * quarters of 256; wave k of a block takes points 64 k .. 64 k + 63 of every quarter, four points per v_mfma_f64_16x16x4_f64 in
+ * ascending order, into one accumulator per entry; a chunk is wave 0 + wave 1 + wave 2 + wave 3, a plane its chunks in
+ * ascending order (a second launch): no atomics, and the entries of a plane depend on that plane, the weights and the
+ * climatology only -- the same bits in any batch, layout (16-byte or scalar loads), grouping of variables and run.  The _host
+ * twin follows the same partition with plain loops; the order in which the instruction adds its four products is its own:
+ * equal to the rounding of a float64 sum (|error| <= (HW + 4) 2^-53 sum_p w |a_i a_j| for either), not to the bit.
+ * SDY_ERR_ARG, before anything is launched: what sdy_window refuses; NULL args / weights / out / ws, weights or a climatology
+ * not 4-byte aligned, out or ws not 8-byte aligned, HW < 1, ws_bytes too small.
+ * SDY_ERR_UNSUPPORTED: n0 > SDY_GRAM_MAX_MEMBERS, more than 2^31 - 1 (sample, time, chunk) work items per variable,
+ * nvars*n1*T*N(N+1)/2 >= 2^38 (the grid of the second launch; flat ws indices then stay below 2^50).
+ * The _host twin: the same structure with HOST pointers and the same checks (ws may be NULL). */
+#define SDY_GRAM_MAX_MEMBERS 64
+typedef struct sdy_member_gram_args {
+  sdy_window win;
+  int HW;
+  const float* weights;
+  const float* climatology[SDY_MAX_VARS];
+  double* out;
+  void* ws;
+  size_t ws_bytes;
+} sdy_member_gram_args;
+int sdy_member_gram(const sdy_member_gram_args* args, void* stream);
+int sdy_member_gram_host(const sdy_member_gram_args* args);
+size_t sdy_member_gram_workspace_bytes(int nvars, int n0, int n1, int T, int HW);   /* 0 for an argument out of range */
 
 /* Rank (Talagrand) histograms of an ensemble per latitude (no counterpart in the reference): one launch adds ONE window of all
  * variables to float64 accumulators that stay on the device.  window: see sdy_window, plane = H*W: n0 = M members, n1 samples.

@@ -355,6 +355,20 @@ class SdyEventArgs(C.Structure):
     ]
 
 
+SDY_GRAM_MAX_MEMBERS = 64
+
+
+class SdyMemberGramArgs(C.Structure):
+    _anonymous_ = ("win",)
+    _fields_ = [
+        ("win", SdyWindow), ("HW", C.c_int),
+        ("weights", C.c_void_p),
+        ("climatology", C.c_void_p * SDY_MAX_VARS),
+        ("out", C.c_void_p),
+        ("ws", C.c_void_p), ("ws_bytes", C.c_size_t),
+    ]
+
+
 SDY_RANK_HIST_MAX_MEMBERS = 64
 
 
@@ -373,7 +387,7 @@ class SdyRankHistArgs(C.Structure):
 ABI_STRUCTS = (SdyConvArgs, SdyMlpArgs, SdyPairArgs, SdySfnoConfig, SdySfnoFwdArgs, SdyVarTable, SdyStepFinishArgs,
                SdyDerivedArgs, SdyCorrectorArgs, SdyDryAirArgs, SdyHistArgs, SdyCoarsenArgs, SdyVideoArgs, SdyZonalArgs,
                SdyMemberSumArgs, SdyMemberStatsArgs, SdySpectrumArgs, SdyVariabilityArgs, SdyVariabilityMapsArgs,
-               SdyVariabilityStatsArgs, SdyRegionSeriesArgs, SdyEventArgs, SdyRankHistArgs)
+               SdyVariabilityStatsArgs, SdyRegionSeriesArgs, SdyEventArgs, SdyMemberGramArgs, SdyRankHistArgs)
 
 # name -> (restype, argtypes); every symbol include/sdy_amd.h declares
 SIGNATURES = {
@@ -511,6 +525,9 @@ SIGNATURES = {
     "sdy_event_table_accumulate_host": (C.c_int, [C.POINTER(SdyEventArgs)]),
     "sdy_event_frequency_accumulate": (C.c_int, [C.POINTER(SdyEventArgs), C.c_void_p]),
     "sdy_event_frequency_accumulate_host": (C.c_int, [C.POINTER(SdyEventArgs)]),
+    "sdy_member_gram": (C.c_int, [C.POINTER(SdyMemberGramArgs), C.c_void_p]),
+    "sdy_member_gram_host": (C.c_int, [C.POINTER(SdyMemberGramArgs)]),
+    "sdy_member_gram_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "sdy_rank_hist_accumulate": (C.c_int, [C.POINTER(SdyRankHistArgs), C.c_void_p]),
     "sdy_rank_hist_accumulate_host": (C.c_int, [C.POINTER(SdyRankHistArgs)]),
     "sdy_profile_enable": (C.c_int, [C.c_int]),

@@ -19,6 +19,7 @@ from ._lib import SdyVideoArgs, SdyZonalArgs, aligned, check, current_stream, li
 from .member_mean import EnsembleTimeMeanAggregator
 from .rank_hist import RankHistogramAggregator
 from .events import Events, EventVerificationAggregator
+from .field_scores import FieldScoreAggregator
 from .regions import RegionalMeanAggregator, Regions
 from .spectrum import PowerSpectrumAggregator
 from .variability import TimeVariabilityAggregator
@@ -596,7 +597,13 @@ class InferenceAggregator:
     `event_pool_times=True`: one slot for all lead times, `event_frequency_maps=True`: exceedance-frequency maps too): per
     variable and event the table of counts behind Brier score, reliability diagram and ROC curve, read with
     `get_event_data()`, and `brier_score`, `brier_skill_score`, `brier_reliability`, `brier_resolution`, `base_rate`,
-    `forecast_rate` and `roc_area` under `<label>/events/<metric>/<event>/<variable>`.  The default `None` adds nothing."""
+    `forecast_rate` and `roc_area` under `<label>/events/<metric>/<event>/<variable>`.  The default `None` adds nothing.
+
+    `field_scores=True` adds `field_scores` (`sdy_amd.FieldScoreAggregator` on the denormalised data; `climatology=<mapping from
+    variable to a (lat, lon) tensor>` turns that variable's pattern correlation into an anomaly correlation): the energy score,
+    the member-to-truth and member-to-member distances of whole fields, their ratio, the ensemble-mean RMSE and the
+    correlation per lead time, `<metric>/<variable>`, as one more table under `<label>/field_scores/series`; read with
+    `get_field_scores()`.  The default `False` adds nothing: the default key set of the logs does not change."""
 
     accepts_sample_weights = True
 
@@ -609,7 +616,7 @@ class InferenceAggregator:
                  ensemble_time_mean_spread: bool = False, rank_histogram_data: bool = False,
                  rank_histogram_pool_times: bool = False, time_variability_data: bool = False,
                  regions: Optional[Regions] = None, events: Optional[Events] = None, event_pool_times: bool = False,
-                 event_frequency_maps: bool = False):
+                 event_frequency_maps: bool = False, field_scores: bool = False, climatology=None):
         if log_video or enable_extended_videos or log_zonal_mean_images:
             raise NotImplementedError("video / zonal-mean image logging is out of scope of sdy_amd (DESIGN.md section 8)")
         if n_timesteps is None:
@@ -649,6 +656,10 @@ class InferenceAggregator:
             self._aggregators["events"] = EventVerificationAggregator(
                 events, area_weights, n_timesteps=n_timesteps, pool_times=event_pool_times,
                 frequency_maps=event_frequency_maps, dist=dist, metadata=metadata)
+        if field_scores:
+            self._aggregators["field_scores"] = FieldScoreAggregator(
+                area_weights, n_timesteps=n_timesteps, is_ensemble=self._is_ensemble, climatology=climatology,
+                target="denorm", dist=dist)
 
     @torch.no_grad()
     def record_batch(self, loss, target_data, gen_data, target_data_norm, gen_data_norm, i_time_start: int = 0,
@@ -700,6 +711,10 @@ class InferenceAggregator:
     def get_event_data(self):
         """`EventVerificationAggregator.get_data()` of the run (`events=...`)."""
         return self._aggregators["events"].get_data()
+
+    def get_field_scores(self):
+        """`FieldScoreAggregator.get_series()` of the run (`field_scores=True`)."""
+        return self._aggregators["field_scores"].get_series()
 
     def get_regional_series(self):
         """`RegionalMeanAggregator.get_series()` of the run (`regions=...`)."""

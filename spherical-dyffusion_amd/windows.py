@@ -2,8 +2,8 @@
 the layouts of a window's variables (`WindowLayout`, the Python side of `sdy_window`, include/sdy_amd.h), the runs of
 variables one launch takes, and `FieldAccumulator`, the float64 accumulators that stay on the device.
 
-This module sits below `metrics`, `histogram`, `data_writer`, `spectrum`, `member_mean`, `rank_hist`, `events`, `variability` and
-`regions` and imports none of them.
+This module sits below `metrics`, `histogram`, `data_writer`, `spectrum`, `member_mean`, `rank_hist`, `events`, `variability`,
+`regions` and `field_scores` and imports none of them.
 """
 from __future__ import annotations
 
