@@ -9,6 +9,7 @@
 
 #include "common.h"
 #include "corrector_math.h"
+#include "ordered_sum.h"
 
 namespace {
 
@@ -57,34 +58,21 @@ __global__ __launch_bounds__(kThreads) void dry_air_reduce_kernel(const sdy_dry_
   }
   // wave butterfly, then the four waves in order: the same tree for every chunk of every row
   __shared__ double sh[kWaves][2];
-#pragma unroll
-  for (int m = 32; m > 0; m >>= 1) {
-    acc_w += __shfl_xor(acc_w, m, 64);
-    acc_d += __shfl_xor(acc_d, m, 64);
-  }
+  sdy_wave_sum(acc_w, acc_d);
   if ((threadIdx.x & 63) == 0) {
     sh[threadIdx.x >> 6][0] = acc_w;
     sh[threadIdx.x >> 6][1] = acc_d;
   }
   __syncthreads();
-  if (threadIdx.x < 2) {
-    double v = sh[0][threadIdx.x];
-#pragma unroll
-    for (int wv = 1; wv < kWaves; ++wv) v += sh[wv][threadIdx.x];
-    partials[((size_t)row * gridDim.x + blockIdx.x) * 2 + threadIdx.x] = v;
-  }
+  if (threadIdx.x < 2) partials[((size_t)row * gridDim.x + blockIdx.x) * 2 + threadIdx.x] = sdy_fold_rows(sh, threadIdx.x);
 }
 
 // the three combines, shared by the one-block kernel and the host entry point
 SDY_CORR_HD double dry_air_row_mean(const double* partials, int row, int chunks) {
 #pragma clang fp contract(off)
-  double sw = 0.0, sd = 0.0;
-  const double* r = partials + (size_t)row * chunks * 2;
-  for (int c = 0; c < chunks; ++c) {
-    sw += r[2 * c];
-    sd += r[2 * c + 1];
-  }
-  return sd / sw;
+  double s[2];   // sum of w, sum of w * dry
+  sdy_sum_chunks(partials + (size_t)row * chunks * 2, chunks, 2, 0, s);
+  return s[1] / s[0];
 }
 SDY_CORR_HD double dry_air_absdiff(const double* gm, int B, int T, int t) {
 #pragma clang fp contract(off)
@@ -142,8 +130,7 @@ int check_args(const sdy_dry_air_args* a, bool need_ws, sdy_dry_air_args* r) {
   if (a->T > 1 && (!a->absdiff || ((uintptr_t)a->absdiff & 7) || !a->mean_absdiff || ((uintptr_t)a->mean_absdiff & 7)))
     return SDY_ERR_ARG;
   if ((long)a->B * a->T > 65535) return SDY_ERR_UNSUPPORTED;
-  if (need_ws && (!a->ws || ((uintptr_t)a->ws & 7) || a->ws_bytes < sdy_dry_air_workspace_bytes(a->B, a->T, a->HW)))
-    return SDY_ERR_ARG;
+  if (need_ws && !sdy_ws_ok(a->ws, a->ws_bytes, sdy_dry_air_workspace_bytes(a->B, a->T, a->HW))) return SDY_ERR_ARG;
   *r = *a;
   bool ok = true;
   auto use_var = [&](sdy_dry_air_var& v) {
@@ -180,7 +167,7 @@ extern "C" int sdy_dry_air_series_host(const sdy_dry_air_args* args) {
     const int b = row / a.T, t = row - b * a.T;
     for (int chunk = 0; chunk < chunks; ++chunk) {
       // the device's tree: a thread's four columns in order, the butterfly over the 64 lanes of a wave, the waves in order
-      double lane[kThreads][2];
+      double lane[2][kThreads];
       for (int tid = 0; tid < kThreads; ++tid) {
         double acc_w = 0.0, acc_d = 0.0;
         const int p0 = (chunk * kThreads + tid) * kColsPerThread;
@@ -189,23 +176,14 @@ extern "C" int sdy_dry_air_series_host(const sdy_dry_air_args* args) {
           const float twp = sdy_corr_twp(sdy_corr_dp_q(K, a.ak, a.bk, ps, [&](int k) { return get(a.q[k], b, t, p); }));
           dry_air_accumulate(a.area[p], sdy_corr_dry(ps, twp), &acc_w, &acc_d);
         }
-        lane[tid][0] = acc_w;
-        lane[tid][1] = acc_d;
+        lane[0][tid] = acc_w;
+        lane[1][tid] = acc_d;
       }
-      double total[2] = {0.0, 0.0};
-      for (int wv = 0; wv < kWaves; ++wv) {
-        double (*v)[2] = lane + wv * 64;
-        for (int m = 32; m > 0; m >>= 1) {
-          double nxt[64][2];
-          for (int i = 0; i < 64; ++i)
-            for (int j = 0; j < 2; ++j) nxt[i][j] = v[i][j] + v[i ^ m][j];
-          for (int i = 0; i < 64; ++i)
-            for (int j = 0; j < 2; ++j) v[i][j] = nxt[i][j];
-        }
-        for (int j = 0; j < 2; ++j) total[j] = wv == 0 ? v[0][j] : total[j] + v[0][j];
+      for (int j = 0; j < 2; ++j) {
+        double total = sdy_wave_sum_host(lane[j]);
+        for (int wv = 1; wv < kWaves; ++wv) total += sdy_wave_sum_host(lane[j] + wv * 64);
+        partials[((size_t)row * chunks + chunk) * 2 + j] = total;
       }
-      partials[((size_t)row * chunks + chunk) * 2] = total[0];
-      partials[((size_t)row * chunks + chunk) * 2 + 1] = total[1];
     }
   }
   for (int row = 0; row < rows; ++row) a.gm[row] = dry_air_row_mean(partials.data(), row, chunks);

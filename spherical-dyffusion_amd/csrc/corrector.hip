@@ -5,6 +5,7 @@
 // (sample, 1024-column chunk) in the workspace, added in chunk order by one thread per sample; no atomics.
 #include "common.h"
 #include "corrector_math.h"
+#include "ordered_sum.h"
 
 namespace {
 
@@ -105,17 +106,12 @@ __global__ __launch_bounds__(kThreads) void corrector_reduce_kernel(const sdy_co
 #pragma unroll
   for (int j = 0; j < SDY_CORR_NSUMS; ++j) {
     double v = acc[j];
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
+    sdy_wave_sum(v);
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6][j] = v;
   }
   __syncthreads();
-  if (threadIdx.x < SDY_CORR_NSUMS) {
-    double v = sh[0][threadIdx.x];
-#pragma unroll
-    for (int wv = 1; wv < kThreads / 64; ++wv) v += sh[wv][threadIdx.x];
-    partials[((size_t)b * gridDim.x + blockIdx.x) * SDY_CORR_NSUMS + threadIdx.x] = v;
-  }
+  if (threadIdx.x < SDY_CORR_NSUMS)
+    partials[((size_t)b * gridDim.x + blockIdx.x) * SDY_CORR_NSUMS + threadIdx.x] = sdy_fold_rows(sh, threadIdx.x);
 }
 
 // one thread per sample: the chunks' partials in chunk order, then the scalar solve
@@ -124,12 +120,7 @@ __global__ __launch_bounds__(64) void corrector_solve_kernel(const double* parti
   const int b = blockIdx.x * 64 + threadIdx.x;
   if (b >= B) return;
   double s[SDY_CORR_NSUMS];
-#pragma unroll
-  for (int j = 0; j < SDY_CORR_NSUMS; ++j) s[j] = 0.0;
-  const double* row = partials + (size_t)b * chunks * SDY_CORR_NSUMS;
-  for (int c = 0; c < chunks; ++c)
-#pragma unroll
-    for (int j = 0; j < SDY_CORR_NSUMS; ++j) s[j] += row[(size_t)c * SDY_CORR_NSUMS + j];
+  sdy_sum_chunks(partials + (size_t)b * chunks * SDY_CORR_NSUMS, chunks, SDY_CORR_NSUMS, 0, s);
   scalars[b] = sdy_corr_solve(s, (flags & SDY_CORRECTOR_DRY_AIR) != 0, budget);
 }
 
@@ -222,8 +213,7 @@ int check_args(const sdy_corrector_args* a, bool need_ws, sdy_corrector_args* r,
   const Needs need = needs_of(a->flags, a->budget);
   if (need.water && (a->K < 1 || a->K > SDY_DERIVED_MAX_LEVELS)) return SDY_ERR_ARG;
   if (a->B > 65535) return SDY_ERR_UNSUPPORTED;
-  if (need_ws && (!a->ws || ((uintptr_t)a->ws & 7) || a->ws_bytes < sdy_corrector_workspace_bytes(a->B, a->HW)))
-    return SDY_ERR_ARG;
+  if (need_ws && !sdy_ws_ok(a->ws, a->ws_bytes, sdy_corrector_workspace_bytes(a->B, a->HW))) return SDY_ERR_ARG;
   *r = *a;
   if (!need.water) r->K = 1;
   const int B = a->B, HW = a->HW;

@@ -10,12 +10,13 @@
 //     words: the 16 rows x 4 points of a fragment read fall into 64 different banks.  Last: the waves' tiles are added in wave
 //     order through LDS, and wave 0 writes the chunk's packed triangle to ws.
 //     C/D of the f64 instruction: col = lane & 15, row = (lane >> 4) + 4 * reg (NOT the f32 map).
-//   gram_combine_kernel: a plane's chunks in ascending order -> out.
+//   combine_chunks_kernel (ordered_sum.hip): a plane's chunks in ascending order -> out.
 // No atomics; what a block adds, and in which order, depends on its plane, the weights and the climatology alone.
 #include <vector>
 
 #include "common.h"
 #include "member_gram.h"
+#include "ordered_sum.h"
 #include "window.h"
 
 namespace {
@@ -137,22 +138,6 @@ __global__ __launch_bounds__(kThreads) void member_gram_kernel(const sdy_member_
   });
 }
 
-// one entry of one plane: the chunks' partials in chunk order; partials: (chunks, entries) of that plane
-__host__ __device__ inline double combine_chunks(const double* partials, int chunks, long entries, long e) {
-  double x = 0.0;
-  for (int c = 0; c < chunks; ++c) x += partials[(long)c * entries + e];
-  return x;
-}
-
-// one thread per element of out (nvars * n1 * T, entries); partials (nvars * n1 * T, chunks, entries)
-__global__ __launch_bounds__(kThreads) void gram_combine_kernel(const double* partials, int chunks, long entries, long n_out,
-                                                                double* out) {
-  const long idx = (long)blockIdx.x * kThreads + threadIdx.x;
-  if (idx >= n_out) return;
-  const long e = idx % entries, plane = idx / entries;
-  out[idx] = combine_chunks(partials + plane * chunks * entries, chunks, entries, e);
-}
-
 int check(const sdy_member_gram_args* a, bool need_ws) {
   if (!a) return SDY_ERR_ARG;
   if (a->HW < 1) return SDY_ERR_ARG;
@@ -164,11 +149,11 @@ int check(const sdy_member_gram_args* a, bool need_ws) {
   const long planes = (long)a->win.n1 * a->win.T, entries = sdy_gram_entries(a->win.n0 + 2);
   // 32-bit block numbers within a variable
   if (planes * sdy_gram_chunks(a->HW) > 0x7fffffffL) return SDY_ERR_UNSUPPORTED;
-  // ... and of the combine launch (256 elements of out per block).  Flat indices of ws then stay below 2^50: nvars * entries
-  // <= 96 * 2211 < 2^18 times planes * chunks < 2^31
+  // ... and flat indices of out below 2^38.  Those of ws then stay below 2^50: nvars * entries <= 96 * 2211 < 2^18 times
+  // planes * chunks < 2^31
   if ((long)a->win.nvars * entries * planes >= (1L << 38)) return SDY_ERR_UNSUPPORTED;
-  if (need_ws && (!a->ws || ((uintptr_t)a->ws & 7) ||
-                  a->ws_bytes < sdy_member_gram_workspace_bytes(a->win.nvars, a->win.n0, a->win.n1, a->win.T, a->HW)))
+  if (need_ws && !sdy_ws_ok(a->ws, a->ws_bytes,
+                            sdy_member_gram_workspace_bytes(a->win.nvars, a->win.n0, a->win.n1, a->win.T, a->HW)))
     return SDY_ERR_ARG;
   return SDY_OK;
 }
@@ -240,7 +225,7 @@ extern "C" int sdy_member_gram_host(const sdy_member_gram_args* a) {
           }
         }
         double* out = a->out + (((long)v * w.n1 + s) * w.T + t) * entries;
-        for (long e = 0; e < entries; ++e) out[e] = combine_chunks(partials.data(), chunks, entries, e);
+        for (long e = 0; e < entries; ++e) out[e] = sdy_sum_chunks(partials.data(), chunks, entries, e);
       }
   return SDY_OK;
 }
@@ -270,8 +255,5 @@ extern "C" int sdy_member_gram(const sdy_member_gram_args* a, void* stream) {
     case 5: rc = launch<5>(a, grid, chunks, partials, (hipStream_t)stream); break;
   }
   SDY_TRY(rc);
-  const long n_out = (long)a->win.nvars * planes * entries;
-  hipLaunchKernelGGL(gram_combine_kernel, dim3((unsigned)((n_out + kThreads - 1) / kThreads)), dim3(kThreads), 0,
-                     (hipStream_t)stream, partials, chunks, entries, n_out, a->out);
-  return sdy_launch_status();
+  return sdy_combine_chunks_launch(partials, (long)a->win.nvars * planes, chunks, entries, a->out, (hipStream_t)stream);
 }

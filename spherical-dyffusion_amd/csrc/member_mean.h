@@ -6,6 +6,8 @@
 
 #include <math.h>
 
+#include "ensemble_point.h"
+
 #if defined(__HIPCC__) || defined(__CUDACC__)
 #define SDY_MM_HD __host__ __device__ inline
 #else
@@ -26,36 +28,17 @@ enum { SDY_MM_ENS_SQ = 0, SDY_MM_ENS_BIAS = 1, SDY_MM_CRPS = 2, SDY_MM_VAR = 3 }
 // One grid point of one sample.  member(i) -> the time mean g_i of member i (called more than once per member: the caller
 // re-reads it), t the target's time mean, w the area weight.  emit(slot, x) receives the point's term of every slot, each
 // slot exactly once, in the same order for every point (the device sums a slot over a wave inside emit, so every lane of a
-// wave has to arrive with the same slot).  All float64, nothing contracted.
-//   ensemble mean: t + mean_m (g_m - t)        fair CRPS: mean_m |g_m - t| - sum_{i<j} |g_i - g_j| / (M (M - 1))
-//   member variance: sum_m (g_m - mean)^2 / (M - 1), the deviations taken from the differences to t
-// M == 1: CRPS = |g - t|, variance 0.
+// wave has to arrive with the same slot).  The ensemble mean (t + mean_m (g_m - t)), the fair CRPS and the member variance
+// are sdy_ens_point's (ensemble_point.h).  All float64, nothing contracted.
 template <class Member, class Emit>
 SDY_MM_HD void sdy_mm_point(int M, double t, double w, Member member, Emit emit) {
 #pragma clang fp contract(off)
-  double sum_d = 0.0, sum_abs = 0.0;
-  for (int i = 0; i < M; ++i) {
-    const double d = member(i) - t;
-    sum_d += d;
-    sum_abs += fabs(d);
+  const sdy_ens_stats r = sdy_ens_point(M, t, member, [&](int i, double d) {
     emit(i, w * (d * d));
     emit(M + i, w * d);
-  }
-  const double em = sum_d / (double)M;          // ensemble mean minus target
-  emit(2 * M + SDY_MM_ENS_SQ, w * (em * em));
-  emit(2 * M + SDY_MM_ENS_BIAS, w * em);
-  double pairs = 0.0, dev2 = 0.0;
-  for (int i = 0; i < M; ++i) {
-    const double gi = member(i);
-    const double dev = (gi - t) - em;
-    dev2 += dev * dev;
-    for (int j = i + 1; j < M; ++j) pairs += fabs(gi - member(j));
-  }
-  double crps = sum_abs / (double)M, var = 0.0;
-  if (M > 1) {
-    crps -= pairs / ((double)M * (double)(M - 1));
-    var = dev2 / (double)(M - 1);
-  }
-  emit(2 * M + SDY_MM_CRPS, w * crps);
-  emit(2 * M + SDY_MM_VAR, w * var);
+  });
+  emit(2 * M + SDY_MM_ENS_SQ, w * (r.e * r.e));   // r.e: ensemble mean minus target
+  emit(2 * M + SDY_MM_ENS_BIAS, w * r.e);
+  emit(2 * M + SDY_MM_CRPS, w * r.crps);
+  emit(2 * M + SDY_MM_VAR, w * r.var);
 }

@@ -6,12 +6,13 @@
 //   sdy_member_map_stats: once per get_logs, reduce -> combine.  One thread per (sample, grid point); the members of a point
 //     are read from the accumulators twice (the pair term of the CRPS re-reads them from cache: M (M - 1) / 2 loads of lines
 //     that the first pass brought in), so no thread keeps a member array.  A slot's terms are added over a wave by a butterfly,
-//     over the four waves in order, and a second launch adds the blocks' partials in block order.
+//     over the four waves in order, and a second launch adds the blocks' partials in block order (ordered_sum.h).
 // The arithmetic of an element and of a grid point is member_mean.h.
 #include <vector>
 
 #include "common.h"
 #include "member_mean.h"
+#include "ordered_sum.h"
 #include "window.h"
 
 namespace {
@@ -92,33 +93,13 @@ __global__ __launch_bounds__(kThreads) void member_stats_kernel(const sdy_member
   // an idle lane contributes 0 to every slot: w = 0 and every member 0
   auto member = [&](int i) { return active ? g[(long)i * n] / n_times : 0.0; };
   auto emit = [&](int slot, double x) {
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) x += __shfl_xor(x, m, 64);
+    sdy_wave_sum(x);
     if (lane == 0) sh[wave][slot] = x;
   };
   sdy_mm_point(M, t, w, member, emit);
   __syncthreads();
   double* out = partials + ((long)v * gridDim.x + blockIdx.x) * slots;
-  for (int k = threadIdx.x; k < slots; k += kThreads) {
-    double s = sh[0][k];
-#pragma unroll
-    for (int wv = 1; wv < kWaves; ++wv) s += sh[wv][k];
-    out[k] = s;
-  }
-}
-
-// the blocks' partials of one slot, in block order
-__host__ __device__ inline double combine_slot(const double* partials, int chunks, int slots, int k) {
-  double s = 0.0;
-  for (int c = 0; c < chunks; ++c) s += partials[(long)c * slots + k];
-  return s;
-}
-
-// grid (nvars): one thread per slot
-__global__ __launch_bounds__(kThreads) void member_combine_kernel(const double* partials, int chunks, int slots, double* out) {
-  const int v = blockIdx.x;
-  for (int k = threadIdx.x; k < slots; k += kThreads)
-    out[(long)v * slots + k] = combine_slot(partials + (long)v * chunks * slots, chunks, slots, k);
+  for (int k = threadIdx.x; k < slots; k += kThreads) out[k] = sdy_fold_rows(sh, k);
 }
 
 long n_chunks(long n) { return (n + kThreads - 1) / kThreads; }
@@ -144,8 +125,7 @@ int check_stats(const sdy_member_stats_args* a, bool need_ws) {
   if (a->M > kMaxMembers) return SDY_ERR_UNSUPPORTED;
   if (a->nvars > 65535 || (long)a->n1 * a->HW > (1L << 30)) return SDY_ERR_UNSUPPORTED;
   if ((long)a->nvars * a->M * ((long)a->n1 * a->HW) >= (1L << 50)) return SDY_ERR_UNSUPPORTED;
-  if (need_ws && (!a->ws || ((uintptr_t)a->ws & 7) ||
-                  a->ws_bytes < sdy_member_stats_workspace_bytes(a->nvars, a->M, a->n1, a->HW)))
+  if (need_ws && !sdy_ws_ok(a->ws, a->ws_bytes, sdy_member_stats_workspace_bytes(a->nvars, a->M, a->n1, a->HW)))
     return SDY_ERR_ARG;
   return SDY_OK;
 }
@@ -209,7 +189,7 @@ extern "C" int sdy_member_map_stats_host(const sdy_member_stats_args* a) {
         sdy_mm_point(M, t, w, [&](int i) { return g[(long)i * n] / a->n_times; }, [&](int slot, double x) { part[slot] += x; });
       }
     }
-    for (int k = 0; k < slots; ++k) a->out[(long)v * slots + k] = combine_slot(partials.data(), (int)chunks, slots, k);
+    for (int k = 0; k < slots; ++k) a->out[(long)v * slots + k] = sdy_sum_chunks(partials.data(), (int)chunks, slots, k);
   }
   return SDY_OK;
 }
@@ -221,7 +201,5 @@ extern "C" int sdy_member_map_stats(const sdy_member_stats_args* a, void* stream
   double* partials = static_cast<double*>(a->ws);
   hipLaunchKernelGGL(member_stats_kernel, dim3(chunks, a->nvars), dim3(kThreads), 0, (hipStream_t)stream, *a, partials);
   SDY_TRY(sdy_launch_status());
-  hipLaunchKernelGGL(member_combine_kernel, dim3(a->nvars), dim3(kThreads), 0, (hipStream_t)stream, partials, chunks, slots,
-                     a->out);
-  return sdy_launch_status();
+  return sdy_combine_chunks_launch(partials, a->nvars, chunks, slots, a->out, (hipStream_t)stream);
 }

@@ -12,10 +12,12 @@
 //     The window is read once whatever n_regions; the registers hold one region's eight sums at a time.
 //   region_combine_kernel: a plane's chunks in ascending order -> out.
 // No atomics; what a block adds, and in which order, depends on its plane and the weights alone.
-// The arithmetic of a point is region_series.h.
+// The arithmetic of a point is ensemble_point.h and region_series.h, the tree of the sums ordered_sum.h.
 #include <vector>
 
 #include "common.h"
+#include "ensemble_point.h"
+#include "ordered_sum.h"
 #include "region_series.h"
 #include "window.h"
 
@@ -64,15 +66,16 @@ __global__ __launch_bounds__(kThreads) void region_series_kernel(const sdy_regio
     __syncthreads();
     {
       const long p = q0 + tid;
-      double e[1] = {0.0}, var[1] = {0.0}, crps[1] = {0.0}, y[1] = {0.0};  // past the plane: every weight reads as 0 below
+      sdy_ens_stats st = {0.0, 0.0, 0.0};                                  // past the plane: every weight reads as 0 below
+      double y = 0.0;
       if (p < HW) {
-        y[0] = (double)tgt[p];
-        sdy_rs_point<1>(M, y, [&](int i, double(&g)[1]) { g[0] = (double)sh_m[i * kThreads + tid]; }, e, var, crps);
+        y = (double)tgt[p];
+        st = sdy_ens_point(M, y, [&](int i) { return (double)sh_m[i * kThreads + tid]; }, [](int, double) {});
       }
-      sh_q[0][tid] = e[0];
-      sh_q[1][tid] = var[0];
-      sh_q[2][tid] = crps[0];
-      sh_q[3][tid] = y[0];
+      sh_q[0][tid] = st.e;
+      sh_q[1][tid] = st.var;
+      sh_q[2][tid] = st.crps;
+      sh_q[3][tid] = y;
     }
     __syncthreads();
     for (int r = wave; r < R; r += kWaves) {
@@ -89,10 +92,8 @@ __global__ __launch_bounds__(kThreads) void region_series_kernel(const sdy_regio
       }
 #pragma unroll
       for (int k = 0; k < SDY_RS_SUMS; ++k) {
-        double x = acc[k];
-#pragma unroll
-        for (int m = 32; m > 0; m >>= 1) x += __shfl_xor(x, m, 64);
-        if (lane == 0) sh_part[r][quarter][k] = x;
+        sdy_wave_sum(acc[k]);
+        if (lane == 0) sh_part[r][quarter][k] = acc[k];
       }
     }
   }
@@ -101,21 +102,11 @@ __global__ __launch_bounds__(kThreads) void region_series_kernel(const sdy_regio
   double* out = partials + ((long)v * gridDim.x + blockIdx.x) * ((long)R * SDY_RS_SUMS);
   for (int i = tid; i < R * SDY_RS_SUMS; i += kThreads) {
     const int r = i / SDY_RS_SUMS, k = i - r * SDY_RS_SUMS;
-    double x = sh_part[r][0][k];
-#pragma unroll
-    for (int q = 1; q < SDY_RS_QUARTERS; ++q) x += sh_part[r][q][k];
-    out[i] = x;
+    out[i] = sdy_fold_rows(sh_part[r], k);
   }
 }
 
-// the chunks' partials of one sum of one plane, in chunk order; partials: (chunks, R * 8) of that plane
-__host__ __device__ inline double combine_chunks(const double* partials, int chunks, int stride, int i) {
-  double x = 0.0;
-  for (int c = 0; c < chunks; ++c) x += partials[(long)c * stride + i];
-  return x;
-}
-
-// one thread per element of out (nvars, R, n1 * T, 8); partials (nvars, n1 * T, chunks, R, 8)
+// one thread per element of out (nvars, R, n1 * T, 8); partials (nvars, n1 * T, chunks, R, 8): a plane's chunks in chunk order
 __global__ __launch_bounds__(kThreads) void region_combine_kernel(const double* partials, int chunks, int R, long planes, long n_out,
                                                                   double* out) {
   const long idx = (long)blockIdx.x * kThreads + threadIdx.x;
@@ -127,7 +118,7 @@ __global__ __launch_bounds__(kThreads) void region_combine_kernel(const double* 
   const int r = (int)(rest % R);
   const long v = rest / R;
   const int stride = R * SDY_RS_SUMS;
-  out[idx] = combine_chunks(partials + (v * planes + plane) * chunks * stride, chunks, stride, r * SDY_RS_SUMS + k);
+  out[idx] = sdy_sum_chunks(partials + (v * planes + plane) * chunks * stride, chunks, stride, r * SDY_RS_SUMS + k);
 }
 
 int check(const sdy_region_series_args* a, bool need_ws) {
@@ -140,8 +131,8 @@ int check(const sdy_region_series_args* a, bool need_ws) {
   if ((long)a->win.n1 * a->win.T * sdy_rs_chunks(a->HW) > 0x7fffffffL) return SDY_ERR_UNSUPPORTED;
   // ... and of the combine launch: 256 elements of out per block (nvars * n_regions * 8 <= 96 * 16 * 8 < 2^14)
   if ((long)a->win.nvars * a->n_regions * SDY_RS_SUMS * ((long)a->win.n1 * a->win.T) >= (1L << 38)) return SDY_ERR_UNSUPPORTED;
-  if (need_ws && (!a->ws || ((uintptr_t)a->ws & 7) ||
-                  a->ws_bytes < sdy_region_series_workspace_bytes(a->win.nvars, a->n_regions, a->win.n1, a->win.T, a->HW)))
+  if (need_ws && !sdy_ws_ok(a->ws, a->ws_bytes,
+                            sdy_region_series_workspace_bytes(a->win.nvars, a->n_regions, a->win.n1, a->win.T, a->HW)))
     return SDY_ERR_ARG;
   return SDY_OK;
 }
@@ -171,10 +162,10 @@ extern "C" int sdy_region_series_host(const sdy_region_series_args* a) {
           const int n = (int)(HW - base < SDY_RS_CHUNK ? HW - base : SDY_RS_CHUNK);
           for (int at = 0; at < n; ++at) {
             const long p = base + at;
-            double e[1], var[1], crps[1];
-            const double y[1] = {(double)tgt[p]};
-            sdy_rs_point<1>(M, y, [&](int i, double(&g)[1]) { g[0] = (double)gen[(long)i * w.gs0 + p]; }, e, var, crps);
-            q[at] = e[0], q[SDY_RS_CHUNK + at] = var[0], q[2 * SDY_RS_CHUNK + at] = crps[0], q[3 * SDY_RS_CHUNK + at] = y[0];
+            const double y = (double)tgt[p];
+            const sdy_ens_stats st =
+                sdy_ens_point(M, y, [&](int i) { return (double)gen[(long)i * w.gs0 + p]; }, [](int, double) {});
+            q[at] = st.e, q[SDY_RS_CHUNK + at] = st.var, q[2 * SDY_RS_CHUNK + at] = st.crps, q[3 * SDY_RS_CHUNK + at] = y;
           }
           for (int r = 0; r < R; ++r) {
             const float* wr = a->weights + (long)r * HW;
@@ -194,7 +185,7 @@ extern "C" int sdy_region_series_host(const sdy_region_series_args* a) {
         for (int r = 0; r < R; ++r)
           for (int k = 0; k < SDY_RS_SUMS; ++k)
             a->out[((((long)v * R + r) * w.n1 + s) * w.T + t) * SDY_RS_SUMS + k] =
-                combine_chunks(partials.data(), chunks, stride, r * SDY_RS_SUMS + k);
+                sdy_sum_chunks(partials.data(), chunks, stride, r * SDY_RS_SUMS + k);
       }
   return SDY_OK;
 }

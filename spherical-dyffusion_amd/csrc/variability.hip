@@ -8,11 +8,12 @@
 //   sdy_time_variability_maps: elementwise, state -> variance and lag-1 autocorrelation.
 //   sdy_time_variability_stats: once per get_logs, reduce -> combine.  One thread per (sample, grid point) walks the members;
 //     a slot's terms are added over a wave by a butterfly, over the four waves in order, and a second launch adds the blocks'
-//     partials in block order.
+//     partials in block order (ordered_sum.h).
 // The arithmetic of an element and of a grid point is variability.h.
 #include <vector>
 
 #include "common.h"
+#include "ordered_sum.h"
 #include "variability.h"
 #include "window.h"
 
@@ -156,8 +157,7 @@ __global__ __launch_bounds__(kThreads) void variability_stats_kernel(const sdy_v
   };
   auto emit = [&](int slot, double x) {
     if (!active) x = 0.0;
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) x += __shfl_xor(x, m, 64);
+    sdy_wave_sum(x);
     if (lane == 0) sh[wave][slot] = x;
   };
   const sdy_tv_moments zero = {0.0, 0.0, 0.0};
@@ -166,25 +166,7 @@ __global__ __launch_bounds__(kThreads) void variability_stats_kernel(const sdy_v
   sdy_tv_point(M, n_times, w, t, [&](int i) { return active ? moments(i) : zero; }, emit);
   __syncthreads();
   double* out = partials + ((long)v * gridDim.x + blockIdx.x) * SDY_TV_SLOTS;
-  if (threadIdx.x < SDY_TV_SLOTS) {
-    double s = sh[0][threadIdx.x];
-#pragma unroll
-    for (int wv = 1; wv < kWaves; ++wv) s += sh[wv][threadIdx.x];
-    out[threadIdx.x] = s;
-  }
-}
-
-// the blocks' partials of one slot, in block order
-__host__ __device__ inline double combine_slot(const double* partials, int chunks, int k) {
-  double s = 0.0;
-  for (int c = 0; c < chunks; ++c) s += partials[(long)c * SDY_TV_SLOTS + k];
-  return s;
-}
-
-// grid (nvars): one thread per slot
-__global__ __launch_bounds__(64) void variability_combine_kernel(const double* partials, int chunks, double* out) {
-  const int v = blockIdx.x, k = threadIdx.x;
-  if (k < SDY_TV_SLOTS) out[(long)v * SDY_TV_SLOTS + k] = combine_slot(partials + (long)v * chunks * SDY_TV_SLOTS, chunks, k);
+  if (threadIdx.x < SDY_TV_SLOTS) out[threadIdx.x] = sdy_fold_rows(sh, threadIdx.x);
 }
 
 long n_chunks(long n) { return (n + kThreads - 1) / kThreads; }
@@ -223,8 +205,7 @@ int check_stats(const sdy_variability_stats_args* a, bool need_ws) {
   if (!(a->n_times >= 1.0) || !std::isfinite(a->n_times)) return SDY_ERR_ARG;
   if (a->nvars > 65535 || (long)a->n1 * a->HW > (1L << 30)) return SDY_ERR_UNSUPPORTED;
   if ((long)a->nvars * ((long)a->M + 1) * ((long)a->n1 * a->HW) >= (1L << 50)) return SDY_ERR_UNSUPPORTED;
-  if (need_ws && (!a->ws || ((uintptr_t)a->ws & 7) ||
-                  a->ws_bytes < sdy_time_variability_workspace_bytes(a->nvars, a->n1, a->HW)))
+  if (need_ws && !sdy_ws_ok(a->ws, a->ws_bytes, sdy_time_variability_workspace_bytes(a->nvars, a->n1, a->HW)))
     return SDY_ERR_ARG;
   return SDY_OK;
 }
@@ -329,7 +310,7 @@ extern "C" int sdy_time_variability_stats_host(const sdy_variability_stats_args*
                      [&](int slot, double x) { part[slot] += x; });
       }
     }
-    for (int k = 0; k < SDY_TV_SLOTS; ++k) a->out[(long)v * SDY_TV_SLOTS + k] = combine_slot(partials.data(), (int)chunks, k);
+    for (int k = 0; k < SDY_TV_SLOTS; ++k) a->out[(long)v * SDY_TV_SLOTS + k] = sdy_sum_chunks(partials.data(), (int)chunks, SDY_TV_SLOTS, k);
   }
   return SDY_OK;
 }
@@ -340,6 +321,5 @@ extern "C" int sdy_time_variability_stats(const sdy_variability_stats_args* a, v
   double* partials = static_cast<double*>(a->ws);
   hipLaunchKernelGGL(variability_stats_kernel, dim3(chunks, a->nvars), dim3(kThreads), 0, (hipStream_t)stream, *a, partials);
   SDY_TRY(sdy_launch_status());
-  hipLaunchKernelGGL(variability_combine_kernel, dim3(a->nvars), dim3(64), 0, (hipStream_t)stream, partials, chunks, a->out);
-  return sdy_launch_status();
+  return sdy_combine_chunks_launch(partials, a->nvars, chunks, SDY_TV_SLOTS, a->out, (hipStream_t)stream);
 }

@@ -18,7 +18,7 @@ The float64 matrix instruction: `mfma_probe` times the Gram launch pair at 62 me
 v_mfma_f64_16x16x4_f64 per four grid points and wave, where the headline window has three) on `--probe-vars` variables and
 reports the launch's time per instruction and SIMD in cycles: an UPPER bound of the instruction's issue interval (staging and
 the waves' reduction are inside the time).  Prints ONE JSON line; for the kernels separately run it under `rocprofv3
---kernel-trace --stats` with `--rounds 1`: `member_gram_kernel`, `gram_combine_kernel`.
+--kernel-trace --stats` with `--rounds 1`: `member_gram_kernel`, `combine_chunks_kernel`.
 """
 import argparse
 import ctypes as C

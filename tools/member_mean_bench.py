@@ -15,7 +15,7 @@ times, 180 x 360) as the member-stacked VIEW of the IC-major batch, targets (1, 
 The kernel reads every input value once (`bytes`) and reads and writes the float64 accumulators (`accumulator_bytes`, both
 directions): `record_GBps` = (bytes + accumulator_bytes) / time, to be held against the copy's read + write rate
 (`share_of_copy`).  Prints ONE JSON line; for the kernels separately run it under `rocprofv3 --kernel-trace --stats` with
-`--rounds 1`: `member_sum_kernel`, `member_stats_kernel`, `member_combine_kernel`.
+`--rounds 1`: `member_sum_kernel`, `member_stats_kernel`, `combine_chunks_kernel`.
 """
 import argparse
 import json

@@ -15,7 +15,7 @@ events, in the same run and alternating:
 The kernel reads every input value once (`bytes`) and reads and writes the state, 32 bytes per trajectory and grid point
 (`state_bytes`, both directions): `record_GBps` = (bytes + state_bytes) / time, to be held against the copy's read + write rate
 (`share_of_copy`).  Prints ONE JSON line; for the kernels separately run it under `rocprofv3 --kernel-trace --stats` with
-`--rounds 1`: `variability_kernel`, `variability_stats_kernel`, `variability_combine_kernel`.
+`--rounds 1`: `variability_kernel`, `variability_stats_kernel`, `combine_chunks_kernel`.
 """
 import argparse
 import json
