@@ -76,10 +76,11 @@ const char* sdy_error_string(int code);
  *   {sdy_conv_args, sdy_mlp_args, sdy_pair_args, sdy_sfno_config, sdy_sfno_fwd_args, sdy_var_table, sdy_step_finish_args,
  *    sdy_derived_args, sdy_corrector_args, sdy_dry_air_args, sdy_hist_args, sdy_coarsen_args, sdy_video_args, sdy_zonal_args,
  *    sdy_member_sum_args, sdy_member_stats_args, sdy_spectrum_args, sdy_variability_args, sdy_variability_maps_args,
- *    sdy_variability_stats_args, sdy_region_series_args, sdy_event_args, sdy_member_gram_args, sdy_rank_hist_args}
+ *    sdy_variability_stats_args, sdy_region_series_args, sdy_event_args, sdy_fss_args, sdy_member_gram_args,
+ *    sdy_rank_hist_args}
  * SDY_OK when n == SDY_ABI_STRUCTS and every size equals the library's, SDY_ERR_ARG otherwise (the Python bindings do this at
  * import).  sdy_abi_sizes writes the library's own list, for the message of a failed check (SDY_ERR_ARG: n != SDY_ABI_STRUCTS). */
-#define SDY_ABI_STRUCTS 24
+#define SDY_ABI_STRUCTS 25
 int sdy_abi_check(const size_t* sizes, int n);
 int sdy_abi_sizes(size_t* sizes, int n);
 
@@ -1090,6 +1091,66 @@ int sdy_event_table_accumulate(const sdy_event_args* args, void* stream);
 int sdy_event_table_accumulate_host(const sdy_event_args* args);
 int sdy_event_frequency_accumulate(const sdy_event_args* args, void* stream);
 int sdy_event_frequency_accumulate_host(const sdy_event_args* args);
+
+/* Neighbourhood verification of threshold events: the integer sums behind the fractions skill score (no counterpart in the
+ * reference).  window: see sdy_window, plane = H*W: n0 = M members, n1 samples.  Events, "in the event", "counted",
+ * thresholds (scalars / maps / below / is_map / map_first / n_maps) and t0 / t_start / n_slots / pool_times: exactly as for
+ * sdy_event_args above.  One definition for the kernels and the _host twin: csrc/fss.h (integers and comparisons only).
+ * Per (variable v, sample s, time t, event e) and grid point q: c(q) = 1 when q is counted, else 0; k(q) = the members in the
+ * event, o(q) = 1 when the target is in it; k = o = 0 where c = 0.  The neighbourhood of radius r >= 0 of a centre (lat, lon):
+ * the points (lat', (lon + d) mod W) with |lat' - lat| <= r, 0 <= lat' < H and |d| <= r -- longitude wraps, latitude is clipped
+ * at the poles; measured in grid points, not kilometres.  n(lat, r) = (2r + 1) (min(H - 1, lat + r) - max(0, lat - r) + 1).
+ * K, O, C = the sums of k, o, c over the neighbourhood.  A centre is COUNTED when C = n(lat, r): every point of its
+ * neighbourhood is counted (a NaN target or a NaN in a threshold map removes the centres within r of it; it is never read as
+ * "not in the event").
+ *   radii:    n_radii (1 .. SDY_FSS_MAX_RADII) radii, strictly ascending, 0 allowed, 2r + 1 <= W
+ *   acc:      dev double, contiguous (nvars, n_slots, E, n_radii, H, 6), zeroed by the caller, holding integers:
+ *             acc[v, slot, e, j, lat, :] += (count, sum K, sum O, sum K^2, sum K O, sum O^2) over the counted centres of radius
+ *             radii[j] among the row's W longitudes, the n1 samples and, pooled, the T - t0 counted times
+ *   ws:       dev, 8-byte aligned, at least sdy_fss_workspace_bytes(nvars, E, n1, T, H, W); scratch only
+ * Two launches.  sdy_fss_encode reads the window once, in place, tests every member value against all E thresholds of its
+ * point and writes one 16-bit code per (v, s, t, e, point) to ws: k in bits 0-6, o in bit 7, c in bit 8.  sdy_fss_sum: a block
+ * owns the accumulator rows of one (v, slot, e) and one band of latitudes; per radius, sample and counted time it forms in LDS
+ * the horizontal periodic sums of the band's rows and r halo rows, then the vertical clipped sums, adds the six terms of every
+ * counted centre to 64-bit integer row sums and, at the end, each row sum to acc once with a plain load / add / store.  No
+ * global atomics; no address is formed from a value read from memory; calls on the same accumulators or workspace must be
+ * ordered on a stream.  sdy_fss_accumulate is the two in order.  Every sum is an integer: the same bits in any layout, batch,
+ * band size, grouping of variables and run, and equal to the _host twin's.  One call's sums are exact (checked below); across
+ * calls the float64 accumulators are exact below 2^53 and round above it: not checked.
+ * SDY_ERR_ARG, before anything is launched: what sdy_window refuses; NULL args / acc / scalars / ws, acc or ws not 8-byte
+ * aligned, n_events outside 1..SDY_EVENT_MAX, a non-positive H / W / n_slots, t0 outside 0..T; not pooled: t_start < 0,
+ * t_start + T > n_slots; pooled: n_slots != 1; a map event with maps == NULL, map_first[v] < 0 or its planes past n_maps;
+ * n_radii outside 1..SDY_FSS_MAX_RADII, a negative radius, radii not strictly ascending, 2r + 1 > W; ws_bytes too small.
+ * SDY_ERR_UNSUPPORTED: n0 > SDY_EVENT_MAX_MEMBERS; n0 (2 r_max + 1)^2 > 65535 (K fits 16 bits, K^2 32); n_maps*H*W >= 2^40; the
+ * largest row sum of one call, n1 W (pooled: x (T - t0)) (n0 n_max)^2 with n_max = (2 r_max + 1) min(H, 2 r_max + 1), >= 2^53;
+ * n_slots*H >= 2^40, nvars*n_slots*E*n_radii*H*6 or the codes of the workspace >= 2^50; 2 r_max + 1 rows of W 32-bit sums and
+ * one of W + 2 r_max over 64 KB of LDS; more than 2^24 - 1 (counted time, band of latitudes) blocks per variable and event.
+ * The _host twin: the same structure with HOST pointers and the same checks (ws may be NULL). */
+#define SDY_FSS_MAX_RADII 4
+typedef struct sdy_fss_args {
+  sdy_window win;
+  int H, W;
+  int t0;
+  int t_start, n_slots;
+  int pool_times;
+  int n_events;
+  int n_maps;
+  unsigned char below[SDY_MAX_VARS];
+  unsigned char is_map[SDY_MAX_VARS];
+  int map_first[SDY_MAX_VARS];
+  const float* scalars;
+  const float* maps;
+  int n_radii;
+  int radii[SDY_FSS_MAX_RADII];
+  double* acc;
+  void* ws;
+  size_t ws_bytes;
+} sdy_fss_args;
+int sdy_fss_accumulate(const sdy_fss_args* args, void* stream);
+int sdy_fss_accumulate_host(const sdy_fss_args* args);
+int sdy_fss_encode(const sdy_fss_args* args, void* stream);   /* the first launch of sdy_fss_accumulate alone */
+int sdy_fss_sum(const sdy_fss_args* args, void* stream);      /* the second: ws holds the codes of sdy_fss_encode of the same args */
+size_t sdy_fss_workspace_bytes(int nvars, int n_events, int n1, int T, int H, int W);   /* 0 for an argument out of range */
 
 /* The area-weighted Gram matrix of the member errors and the truth anomaly (no counterpart in the reference): what the energy
  * score, the member-to-member and member-to-truth distances of whole fields and the anomaly correlation are read from.  ONE

@@ -355,6 +355,27 @@ class SdyEventArgs(C.Structure):
     ]
 
 
+SDY_FSS_MAX_RADII = 4
+
+
+class SdyFssArgs(C.Structure):
+    _anonymous_ = ("win",)
+    _fields_ = [
+        ("win", SdyWindow), ("H", C.c_int), ("W", C.c_int),
+        ("t0", C.c_int),
+        ("t_start", C.c_int), ("n_slots", C.c_int),
+        ("pool_times", C.c_int),
+        ("n_events", C.c_int),
+        ("n_maps", C.c_int),
+        ("below", C.c_ubyte * SDY_MAX_VARS), ("is_map", C.c_ubyte * SDY_MAX_VARS),
+        ("map_first", C.c_int * SDY_MAX_VARS),
+        ("scalars", C.c_void_p), ("maps", C.c_void_p),
+        ("n_radii", C.c_int), ("radii", C.c_int * SDY_FSS_MAX_RADII),
+        ("acc", C.c_void_p),
+        ("ws", C.c_void_p), ("ws_bytes", C.c_size_t),
+    ]
+
+
 SDY_GRAM_MAX_MEMBERS = 64
 
 
@@ -387,7 +408,8 @@ class SdyRankHistArgs(C.Structure):
 ABI_STRUCTS = (SdyConvArgs, SdyMlpArgs, SdyPairArgs, SdySfnoConfig, SdySfnoFwdArgs, SdyVarTable, SdyStepFinishArgs,
                SdyDerivedArgs, SdyCorrectorArgs, SdyDryAirArgs, SdyHistArgs, SdyCoarsenArgs, SdyVideoArgs, SdyZonalArgs,
                SdyMemberSumArgs, SdyMemberStatsArgs, SdySpectrumArgs, SdyVariabilityArgs, SdyVariabilityMapsArgs,
-               SdyVariabilityStatsArgs, SdyRegionSeriesArgs, SdyEventArgs, SdyMemberGramArgs, SdyRankHistArgs)
+               SdyVariabilityStatsArgs, SdyRegionSeriesArgs, SdyEventArgs, SdyFssArgs, SdyMemberGramArgs,
+               SdyRankHistArgs)
 
 # name -> (restype, argtypes); every symbol include/sdy_amd.h declares
 SIGNATURES = {
@@ -525,6 +547,11 @@ SIGNATURES = {
     "sdy_event_table_accumulate_host": (C.c_int, [C.POINTER(SdyEventArgs)]),
     "sdy_event_frequency_accumulate": (C.c_int, [C.POINTER(SdyEventArgs), C.c_void_p]),
     "sdy_event_frequency_accumulate_host": (C.c_int, [C.POINTER(SdyEventArgs)]),
+    "sdy_fss_accumulate": (C.c_int, [C.POINTER(SdyFssArgs), C.c_void_p]),
+    "sdy_fss_accumulate_host": (C.c_int, [C.POINTER(SdyFssArgs)]),
+    "sdy_fss_encode": (C.c_int, [C.POINTER(SdyFssArgs), C.c_void_p]),
+    "sdy_fss_sum": (C.c_int, [C.POINTER(SdyFssArgs), C.c_void_p]),
+    "sdy_fss_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "sdy_member_gram": (C.c_int, [C.POINTER(SdyMemberGramArgs), C.c_void_p]),
     "sdy_member_gram_host": (C.c_int, [C.POINTER(SdyMemberGramArgs)]),
     "sdy_member_gram_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),

@@ -44,7 +44,7 @@ extern "C" int sdy_abi_sizes(size_t* sizes, int n) {
       sizeof(sdy_video_args),     sizeof(sdy_zonal_args),    sizeof(sdy_member_sum_args),  sizeof(sdy_member_stats_args),
       sizeof(sdy_spectrum_args),  sizeof(sdy_variability_args), sizeof(sdy_variability_maps_args),
       sizeof(sdy_variability_stats_args), sizeof(sdy_region_series_args), sizeof(sdy_event_args),
-      sizeof(sdy_member_gram_args), sizeof(sdy_rank_hist_args)};
+      sizeof(sdy_fss_args),       sizeof(sdy_member_gram_args), sizeof(sdy_rank_hist_args)};
   if (!sizes || n != SDY_ABI_STRUCTS) return SDY_ERR_ARG;
   for (int i = 0; i < n; ++i) sizes[i] = mine[i];
   return SDY_OK;

@@ -11,6 +11,7 @@
 // run.  The event count is a template argument: the per-thread threshold and counter arrays are indexed at compile time only
 // and stay in registers (no private segment).  The arithmetic of a point is events.h.
 #include "common.h"
+#include "event_count.h"
 #include "events.h"
 #include "window.h"
 
@@ -23,11 +24,6 @@ constexpr int kMaxMembers = SDY_EVENT_MAX_MEMBERS;
 constexpr int kMaxEvents = SDY_EVENT_MAX;
 constexpr int kMinGroup = 4;            // lanes of the narrowest group
 constexpr int kLdsBytes = 64 * 1024;    // of a block's rows
-
-// independent member loads a thread issues before it consumes the first: with more than 4 events the thresholds and counters
-// of a unit take the registers that the second half of 8 loads would
-template <int EC>
-constexpr int kInFlight = EC > 4 ? 4 : 8;
 
 // lanes per accumulator row, the rule of rank_hist.hip: the narrowest group that covers a row of at most 16 units in one pass,
 // else the group of 16, 32 or 64 lanes that leaves the fewest lane slots idle (the wider one of equals)
@@ -51,104 +47,6 @@ int lane_group(int units) {
 
 long row_words(int E, int M) { return (long)E * 2 * (M + 1); }
 long row_bytes_lds(int E, int M) { return row_words(E, M) * 4; }
-
-// (wave-uniform 64-bit base) + (32-bit byte offset per lane), see rank_hist.hip
-typedef float __attribute__((address_space(1))) gfloat;
-template <int W4>
-__device__ __forceinline__ Vec<W4> ld_u(const float* ubase, unsigned off_b);
-template <>
-__device__ __forceinline__ f32x4 ld_u<4>(const float* ubase, unsigned off_b) { return sdy_ld16s(ubase, off_b); }
-template <>
-__device__ __forceinline__ float ld_u<1>(const float* ubase, unsigned off_b) {
-  sdy_gcptr_t b = (sdy_gcptr_t)ubase;
-  asm volatile("" : "+s"(b), "+v"(off_b));
-  return *reinterpret_cast<const gfloat*>(b + off_b);
-}
-
-// What a thread keeps per event of variable v, set once before its first unit: the sign that folds the direction into the
-// operands (sdy_ev_signed, events.h), the signed scalar threshold, and the plane of a map threshold.  All three are
-// wave-uniform, and are moved to vector registers on purpose: with 8 events they, and the map planes' 64-bit bases, would
-// take more scalar registers than a wave has, and vector registers are not what limits these kernels.
-template <int EC>
-struct EventRegs {
-  unsigned sign[EC];
-  float scalar[EC];
-  int plane[EC];
-};
-template <int EC>
-__device__ __forceinline__ void event_regs(const sdy_event_args& a, int v, unsigned is_map, unsigned below, EventRegs<EC>& r) {
-#pragma unroll
-  for (int e = 0; e < EC; ++e) {
-    r.sign[e] = sdy_ev_sign((below >> e) & 1u);
-    r.scalar[e] = sdy_ev_signed(a.scalars[v * EC + e], r.sign[e]);
-    r.plane[e] = sdy_ev_map_plane(a.map_first[v], is_map, e);
-    asm volatile("" : "+v"(r.sign[e]), "+v"(r.scalar[e]), "+v"(r.plane[e]));
-  }
-}
-
-// The signed thresholds of the W4 points from point `at` of a plane on, all EC events: a map event loads its row once per unit,
-// a scalar event costs no load.  is_map is wave-uniform: the branch does not diverge.
-template <int W4, int EC>
-__device__ __forceinline__ void thresholds(const sdy_event_args& a, unsigned is_map, const EventRegs<EC>& r, long plane,
-                                           unsigned at, float (&c)[EC][W4]) {
-  // (through a vector register and back: the EC bit tests are made here, once per unit, as scalar compares; hoisted out of
-  // the kernel's loops they would be kept as EC lane masks in pairs of scalar registers)
-  unsigned bits = is_map;
-  asm volatile("" : "+v"(bits));
-  bits = __builtin_amdgcn_readfirstlane(bits);
-#pragma unroll
-  for (int e = 0; e < EC; ++e) {
-    if ((bits >> e) & 1u) {
-      const Vec<W4> m = ld<W4>(a.maps + ((long)r.plane[e] * plane + at));
-#pragma unroll
-      for (int q = 0; q < W4; ++q) c[e][q] = sdy_ev_signed(comp(m, q), r.sign[e]);
-    } else {
-#pragma unroll
-      for (int q = 0; q < W4; ++q) c[e][q] = r.scalar[e];
-    }
-  }
-}
-
-// k += (x > c), as the pair compare-into-VCC / add-with-carry and nothing else.  Written out because the compiler, left to
-// itself, lines up the comparisons of a whole batch of members ahead of the additions -- one 64-bit lane mask in a pair of scalar
-// registers each, up to 128 of them -- and spills scalar registers.  A NaN on either side compares false.
-__device__ __forceinline__ void count_if_above(int& k, float x, float c) {
-  asm("v_cmp_gt_f32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, 0, %0, vcc" : "+v"(k) : "v"(x), "v"(c) : "vcc");
-}
-
-// k[e][q] += the members of the W4 points at byte offset off_b (of member 0's time) that are in event e, kInFlight loads in
-// flight; c: the signed thresholds
-template <int W4, int EC>
-__device__ __forceinline__ void count_members(const float* g, long gs0, int M, unsigned off_b, const EventRegs<EC>& r,
-                                              const float (&c)[EC][W4], int (&k)[EC][W4]) {
-  constexpr int F = kInFlight<EC>;
-  int i0 = 0;
-  for (; i0 + F <= M; i0 += F) {
-    Vec<W4> x[F];
-#pragma unroll
-    for (int j = 0; j < F; ++j) x[j] = ld_u<W4>(g + (long)(i0 + j) * gs0, off_b);
-#pragma unroll
-    for (int j = 0; j < F; ++j)
-#pragma unroll
-      for (int e = 0; e < EC; ++e)
-#pragma unroll
-        for (int q = 0; q < W4; ++q) count_if_above(k[e][q], sdy_ev_signed(comp(x[j], q), r.sign[e]), c[e][q]);
-  }
-  if (i0 < M) {
-    Vec<W4> x[F - 1];
-#pragma unroll
-    for (int j = 0; j < F - 1; ++j)
-      if (i0 + j < M) x[j] = ld_u<W4>(g + (long)(i0 + j) * gs0, off_b);
-#pragma unroll
-    for (int j = 0; j < F - 1; ++j)
-      if (i0 + j < M) {
-#pragma unroll
-        for (int e = 0; e < EC; ++e)
-#pragma unroll
-          for (int q = 0; q < W4; ++q) count_if_above(k[e][q], sdy_ev_signed(comp(x[j], q), r.sign[e]), c[e][q]);
-      }
-  }
-}
 
 // G lanes share accumulator row `row` of variable blockIdx.y: row = tt * H + lat, where tt numbers the counted times of the
 // window (one row per latitude when the times are pooled).  blockDim.x = rows_per_block * G; the block's rows_per_block rows of

@@ -7,8 +7,8 @@ For an M-member ensemble the forecast probability of an event takes the values k
 from an integer table of counts per (members in the event, truth in the event or not): the device accumulates the table
 exactly, every score is a few float64 operations on it at read-out (`scores`).
 
-Out of scope: quantile helpers that build threshold maps from a climatology, events over several variables, neighbourhood
-(fractions-skill) scores, plots.
+Neighbourhood (fractions-skill) scores of the same events: `sdy_amd.fss`.  Out of scope: quantile helpers that build threshold
+maps from a climatology, events over several variables, plots.
 """
 from __future__ import annotations
 
@@ -135,77 +135,38 @@ class _EventLayout(WindowLayout):
     n_events = 0
 
 
-class EventVerificationAggregator(FieldAccumulator):
-    """Per variable, event, lead time and latitude: how many counted points had k of the M members in the event while the truth
-    was (o = 1) or was not (o = 0) in it -- and everything that follows from that table.
-
-    Definition (csrc/events.h).  A value x is in an event when x > c (above) or x < c (below), strictly; a NaN x never is.  A
-    point (sample, time, lat, lon) is counted for an event when neither its target nor its threshold is NaN: a NaN in a
-    threshold map masks the point for that event, a NaN member is simply not in the event.
-
-    `record_batch(loss, target_data, gen_data, target_data_norm, gen_data_norm, i_time_start)` is what `run_inference` calls
-    once per window: targets `(samples, time, lat, lon)`, gen `(members, samples, time, lat, lon)` (a 4-D gen is one member:
-    a 2 x 2 contingency table).  Only the variables with events are read; one that is missing from the first window raises
-    `ValueError`.  One `sdy_event_table_accumulate` launch per run of variables with equal extents and equal event count reads
-    the window in place -- the member-stacked transposed view included -- and adds it to a float64 table `(n_slots, events,
-    lat, 2, M + 1)` per variable on the device; `frequency_maps=True` adds one `sdy_event_frequency_accumulate` launch per run
-    into `(events, 3, lat x lon)` maps of member hits, target hits and counted points, pooled over all lead times.  The
-    thresholds go to the device once, at the first accepted window.  The slot of window time t is the lead time `i_time_start
-    + t` of `n_timesteps`; `pool_times=True` keeps ONE slot.  The first time of a run (`i_time_start == 0`) is the initial
-    condition and is not counted.  Counts are integers held as float64: the same bits in any layout, batch, run and rank
-    count.  The first window that is accepted fixes variables, grids, member count and sample count; a later window with
-    others raises `ValueError`, and a refused window changes nothing.  The denormalised data are read.
-
-    `area_weights` is `(lat, lon)`, constant along a row (the weight of a latitude is its row's mean); others raise
-    `ValueError` at construction.
-
-    `get_data()` returns float64 device tensors, added over ranks (`dist.reduce_sum`: tables add, they are never averaged),
-    per variable and event: `table/<event>/<var>` `(n_slots, lat, 2, M + 1)`; per slot `brier_score`, `brier_reliability`,
-    `brier_resolution`, `uncertainty`, `base_rate`, `forecast_rate` and `roc_area` `(n_slots,)` and `reliability_curve`
-    `(n_slots, M + 1)` (see `scores`); with `frequency_maps=True` also `frequency_gen` = member hits / (M x counted),
-    `frequency_target` = target hits / counted (both NaN where nothing was counted) and `counted`, each `(lat, lon)`.
-    `get_logs(label)` returns Python floats from the tables pooled over all slots, `<metric>/<event>/<variable>` for the
-    metrics of `LOG_METRICS`.  Ranks hold whole initial conditions; ragged shares (flat rows with `sample_weights`) are
-    refused.  Quantile helpers for threshold maps, events over several variables, neighbourhood (fractions-skill) scores and
-    plots are out of scope."""
+class EventAccumulator(FieldAccumulator):
+    """What `EventVerificationAggregator` and `sdy_amd.FractionsSkillAggregator` share: the events of the variables and their
+    thresholds on the device, the row-constant area weights, the slots, and everything a window is checked for before anything
+    changes.  The threshold fields of `SdyEventArgs` and `SdyFssArgs` have the same names: `_fill` takes either."""
 
     accepts_sample_weights = True      # (to see, and refuse, a ragged share)
 
     _job_words = "member count, sample count"
 
-    def __init__(self, events: Events, area_weights: torch.Tensor, n_timesteps: int, pool_times: bool = False,
-                 frequency_maps: bool = False, dist=None, metadata=None, max_bytes: Optional[int] = None):
+    def __init__(self, events: Events, area_weights: torch.Tensor, n_timesteps: int, pool_times: bool = False, dist=None,
+                 metadata=None, max_bytes: Optional[int] = None):
         super().__init__(n_timesteps, dist=dist, metadata=metadata, max_bytes=max_bytes)
+        who = type(self).__name__
         if not isinstance(events, Events) or len(events) == 0:
-            raise ValueError("EventVerificationAggregator needs an sdy_amd.Events with at least one event")
+            raise ValueError(f"{who} needs an sdy_amd.Events with at least one event")
         if area_weights.dim() != 2:
             raise ValueError(f"area weights are (lat, lon), got {tuple(area_weights.shape)}")
         if not bool((area_weights == area_weights[:, :1]).all()):
-            raise ValueError("EventVerificationAggregator: the area weights vary along a latitude row; counts that are pooled "
+            raise ValueError(f"{who}: the area weights vary along a latitude row; counts that are pooled "
                              "over longitudes cannot weight them exactly")
         self._events = {v: events.of(v) for v in events.variables}          # a copy: later add()s do not reach a running job
         self._area_weights = area_weights
         self._pool_times = bool(pool_times)
-        self._frequency_maps = bool(frequency_maps)
         self._n_slots = 1 if self._pool_times else self._n_timesteps
         self._scalars: Optional[torch.Tensor] = None      # device (sum of E,) fp32, NaN at the map events
         self._maps: Optional[torch.Tensor] = None         # device fp32: every map, variable by variable, event order
         self._scalar_at: List[int] = []                   # per variable: its first scalar / the float offset of its first map
         self._map_at: List[int] = []
 
-    def _statistics(self) -> Dict[str, float]:
-        return {"table": 0.0, "maps": 0.0} if self._frequency_maps else {"table": 0.0}
-
     @staticmethod
     def _job(l: WindowLayout) -> tuple:
         return (l.n0, l.n1, l.H, l.W, l.n_events)
-
-    def _elements(self, stat: str, job: tuple) -> int:
-        M, _, H, W, E = job
-        return self._n_slots * E * H * 2 * (M + 1) if stat == "table" else E * 3 * H * W
-
-    def _size_words(self, names, jobs) -> str:
-        return f"{sum(j[4] for j in jobs)} events of {len(names)} variables, {jobs[0][0]} members x {self._n_slots} slots"
 
     def _layouts(self, target_data, gen_data):
         """-> (names, layouts) of the window's variables that have events, in window order."""
@@ -237,8 +198,9 @@ class EventVerificationAggregator(FieldAccumulator):
         self._scalars = torch.tensor(scalars, dtype=torch.float32).to(device)
         self._maps = torch.cat(maps).to(device) if maps else None
 
-    def _args(self, lay, first: int, last: int, t0: int, i_time_start: int, stat: str) -> SdyEventArgs:
-        a = SdyEventArgs()
+    def _fill(self, a, lay, first: int, last: int, t0: int, i_time_start: int) -> None:
+        """Variables first .. last - 1 of a window (one run: equal extents and event count) into the window, the slots and the
+        thresholds of an argument structure; the accumulator is the caller's."""
         fill_window(a.win, lay, first, last)
         l = lay[first]
         a.H, a.W, a.t0, a.n_events = l.H, l.W, t0, l.n_events
@@ -253,19 +215,15 @@ class EventVerificationAggregator(FieldAccumulator):
             n_maps += sum(m for _, m in bits)
         a.n_maps = n_maps
         a.maps = self._maps.data_ptr() + 4 * self._map_at[first] if n_maps else None
-        a.acc = self._at(stat, first)
-        return a
 
-    @torch.no_grad()
-    def record_batch(self, loss, target_data, gen_data, target_data_norm=None, gen_data_norm=None, i_time_start: int = 0,
-                     sample_weights: Optional[Sequence[float]] = None):
-        del loss, target_data_norm, gen_data_norm
+    def _begin(self, target_data, gen_data, i_time_start: int, sample_weights):
+        """Everything a window is checked for, the accumulators and the thresholds at the first accepted one -> (layouts, t0,
+        device); t0: the first counted time (the very first time of a run is the initial condition)."""
         ragged = sample_weights is not None or any(
             g.dim() == 4 and k in target_data and target_data[k].dim() == 4 and g.shape[0] != target_data[k].shape[0]
             for k, g in gen_data.items())
         if ragged:
-            raise ValueError(whole_ics_message("EventVerificationAggregator"))
-        i_time_start = int(i_time_start)
+            raise ValueError(whole_ics_message(type(self).__name__))
         names, lay = self._layouts(target_data, gen_data)
         T = lay[0].T
         if i_time_start < 0 or i_time_start + T > self._n_timesteps:
@@ -277,19 +235,14 @@ class EventVerificationAggregator(FieldAccumulator):
                 if e.map is not None and tuple(e.map.shape) != (l.H, l.W):
                     raise ValueError(f"event {e.name!r} of {k!r}: a {tuple(e.map.shape)} threshold map against a "
                                      f"{(l.H, l.W)} grid")
+        self._check_window(lay)
         device = self._prepare(names, lay)
         if self._scalars is None:
             self._build_thresholds(names, lay, device)
-        t0 = 1 if i_time_start == 0 else 0            # the very first time of a run is the initial condition
-        with torch.cuda.device(device):
-            for first, last in runs(lay, lambda l: (l.extents, l.n_events)):
-                a = self._args(lay, first, last, t0, i_time_start, "table")
-                check(lib.sdy_event_table_accumulate(C.byref(a), current_stream()), "sdy_event_table_accumulate")
-                if self._frequency_maps:
-                    a.acc = self._at("maps", first)
-                    check(lib.sdy_event_frequency_accumulate(C.byref(a), current_stream()), "sdy_event_frequency_accumulate")
-        for t in range(i_time_start + t0, i_time_start + T):
-            self._n_batches[t] += 1
+        return lay, (1 if i_time_start == 0 else 0), device
+
+    def _check_window(self, lay) -> None:
+        """What a subclass refuses on top, before anything changes."""
 
     def _reduced(self) -> Dict[str, torch.Tensor]:
         # (raised BEFORE any collective: every rank of a job must have recorded at least one window)
@@ -302,6 +255,79 @@ class EventVerificationAggregator(FieldAccumulator):
         if tuple(self._area_weights.shape) != (H, W):
             raise ValueError(f"area weights {tuple(self._area_weights.shape)} against a {(H, W)} grid")
         return self._area_weights.to(device, torch.float64).mean(dim=1)
+
+
+class EventVerificationAggregator(EventAccumulator):
+    """Per variable, event, lead time and latitude: how many counted points had k of the M members in the event while the truth
+    was (o = 1) or was not (o = 0) in it -- and everything that follows from that table.
+
+    Definition (csrc/events.h).  A value x is in an event when x > c (above) or x < c (below), strictly; a NaN x never is.  A
+    point (sample, time, lat, lon) is counted for an event when neither its target nor its threshold is NaN: a NaN in a
+    threshold map masks the point for that event, a NaN member is simply not in the event.
+
+    `record_batch(loss, target_data, gen_data, target_data_norm, gen_data_norm, i_time_start)` is what `run_inference` calls
+    once per window: targets `(samples, time, lat, lon)`, gen `(members, samples, time, lat, lon)` (a 4-D gen is one member:
+    a 2 x 2 contingency table).  Only the variables with events are read; one that is missing from the first window raises
+    `ValueError`.  One `sdy_event_table_accumulate` launch per run of variables with equal extents and equal event count reads
+    the window in place -- the member-stacked transposed view included -- and adds it to a float64 table `(n_slots, events,
+    lat, 2, M + 1)` per variable on the device; `frequency_maps=True` adds one `sdy_event_frequency_accumulate` launch per run
+    into `(events, 3, lat x lon)` maps of member hits, target hits and counted points, pooled over all lead times.  The
+    thresholds go to the device once, at the first accepted window.  The slot of window time t is the lead time `i_time_start
+    + t` of `n_timesteps`; `pool_times=True` keeps ONE slot.  The first time of a run (`i_time_start == 0`) is the initial
+    condition and is not counted.  Counts are integers held as float64: the same bits in any layout, batch, run and rank
+    count.  The first window that is accepted fixes variables, grids, member count and sample count; a later window with
+    others raises `ValueError`, and a refused window changes nothing.  The denormalised data are read.
+
+    `area_weights` is `(lat, lon)`, constant along a row (the weight of a latitude is its row's mean); others raise
+    `ValueError` at construction.
+
+    `get_data()` returns float64 device tensors, added over ranks (`dist.reduce_sum`: tables add, they are never averaged),
+    per variable and event: `table/<event>/<var>` `(n_slots, lat, 2, M + 1)`; per slot `brier_score`, `brier_reliability`,
+    `brier_resolution`, `uncertainty`, `base_rate`, `forecast_rate` and `roc_area` `(n_slots,)` and `reliability_curve`
+    `(n_slots, M + 1)` (see `scores`); with `frequency_maps=True` also `frequency_gen` = member hits / (M x counted),
+    `frequency_target` = target hits / counted (both NaN where nothing was counted) and `counted`, each `(lat, lon)`.
+    `get_logs(label)` returns Python floats from the tables pooled over all slots, `<metric>/<event>/<variable>` for the
+    metrics of `LOG_METRICS`.  Ranks hold whole initial conditions; ragged shares (flat rows with `sample_weights`) are
+    refused.  Quantile helpers for threshold maps, events over several variables and plots are out of scope; neighbourhood
+    (fractions-skill) scores are `sdy_amd.FractionsSkillAggregator`."""
+
+    def __init__(self, events: Events, area_weights: torch.Tensor, n_timesteps: int, pool_times: bool = False,
+                 frequency_maps: bool = False, dist=None, metadata=None, max_bytes: Optional[int] = None):
+        super().__init__(events, area_weights, n_timesteps, pool_times=pool_times, dist=dist, metadata=metadata,
+                         max_bytes=max_bytes)
+        self._frequency_maps = bool(frequency_maps)
+
+    def _statistics(self) -> Dict[str, float]:
+        return {"table": 0.0, "maps": 0.0} if self._frequency_maps else {"table": 0.0}
+
+    def _elements(self, stat: str, job: tuple) -> int:
+        M, _, H, W, E = job
+        return self._n_slots * E * H * 2 * (M + 1) if stat == "table" else E * 3 * H * W
+
+    def _size_words(self, names, jobs) -> str:
+        return f"{sum(j[4] for j in jobs)} events of {len(names)} variables, {jobs[0][0]} members x {self._n_slots} slots"
+
+    def _args(self, lay, first: int, last: int, t0: int, i_time_start: int, stat: str) -> SdyEventArgs:
+        a = SdyEventArgs()
+        self._fill(a, lay, first, last, t0, i_time_start)
+        a.acc = self._at(stat, first)
+        return a
+
+    @torch.no_grad()
+    def record_batch(self, loss, target_data, gen_data, target_data_norm=None, gen_data_norm=None, i_time_start: int = 0,
+                     sample_weights: Optional[Sequence[float]] = None):
+        del loss, target_data_norm, gen_data_norm
+        i_time_start = int(i_time_start)
+        lay, t0, device = self._begin(target_data, gen_data, i_time_start, sample_weights)
+        with torch.cuda.device(device):
+            for first, last in runs(lay, lambda l: (l.extents, l.n_events)):
+                a = self._args(lay, first, last, t0, i_time_start, "table")
+                check(lib.sdy_event_table_accumulate(C.byref(a), current_stream()), "sdy_event_table_accumulate")
+                if self._frequency_maps:
+                    a.acc = self._at("maps", first)
+                    check(lib.sdy_event_frequency_accumulate(C.byref(a), current_stream()), "sdy_event_frequency_accumulate")
+        for t in range(i_time_start + t0, i_time_start + lay[0].T):
+            self._n_batches[t] += 1
 
     def _table(self, acc: Dict[str, torch.Tensor], i: int) -> torch.Tensor:
         """-> the (n_slots, E, lat, 2, M + 1) table of variable i inside the flat (reduced) buffer."""

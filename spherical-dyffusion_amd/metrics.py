@@ -19,6 +19,7 @@ from ._lib import SdyVideoArgs, SdyZonalArgs, aligned, check, current_stream, li
 from .member_mean import EnsembleTimeMeanAggregator
 from .rank_hist import RankHistogramAggregator
 from .events import Events, EventVerificationAggregator
+from .fss import FractionsSkillAggregator
 from .field_scores import FieldScoreAggregator
 from .regions import RegionalMeanAggregator, Regions
 from .spectrum import PowerSpectrumAggregator
@@ -598,6 +599,10 @@ class InferenceAggregator:
     variable and event the table of counts behind Brier score, reliability diagram and ROC curve, read with
     `get_event_data()`, and `brier_score`, `brier_skill_score`, `brier_reliability`, `brier_resolution`, `base_rate`,
     `forecast_rate` and `roc_area` under `<label>/events/<metric>/<event>/<variable>`.  The default `None` adds nothing.
+    With events, `event_neighbourhoods=<tuple of radii in grid points>` adds `fss` (`sdy_amd.FractionsSkillAggregator` on the same
+    events, with `event_pool_times`): the neighbourhood sums read with `get_fss_data()`, and `fss`, `fbs`, `base_rate`,
+    `fss_useful` and `counted_fraction` under `<label>/fss/<metric>_r<radius>/<event>/<variable>`.  The default `None` adds
+    nothing.
 
     `field_scores=True` adds `field_scores` (`sdy_amd.FieldScoreAggregator` on the denormalised data; `climatology=<mapping from
     variable to a (lat, lon) tensor>` turns that variable's pattern correlation into an anomaly correlation): the energy score,
@@ -616,7 +621,8 @@ class InferenceAggregator:
                  ensemble_time_mean_spread: bool = False, rank_histogram_data: bool = False,
                  rank_histogram_pool_times: bool = False, time_variability_data: bool = False,
                  regions: Optional[Regions] = None, events: Optional[Events] = None, event_pool_times: bool = False,
-                 event_frequency_maps: bool = False, field_scores: bool = False, climatology=None):
+                 event_frequency_maps: bool = False, field_scores: bool = False, climatology=None,
+                 event_neighbourhoods: Optional[Sequence[int]] = None):
         if log_video or enable_extended_videos or log_zonal_mean_images:
             raise NotImplementedError("video / zonal-mean image logging is out of scope of sdy_amd (DESIGN.md section 8)")
         if n_timesteps is None:
@@ -656,6 +662,12 @@ class InferenceAggregator:
             self._aggregators["events"] = EventVerificationAggregator(
                 events, area_weights, n_timesteps=n_timesteps, pool_times=event_pool_times,
                 frequency_maps=event_frequency_maps, dist=dist, metadata=metadata)
+        if event_neighbourhoods is not None:
+            if events is None:
+                raise ValueError("event_neighbourhoods needs events=<sdy_amd.Events>")
+            self._aggregators["fss"] = FractionsSkillAggregator(
+                events, tuple(event_neighbourhoods), area_weights, n_timesteps=n_timesteps, pool_times=event_pool_times,
+                dist=dist, metadata=metadata)
         if field_scores:
             self._aggregators["field_scores"] = FieldScoreAggregator(
                 area_weights, n_timesteps=n_timesteps, is_ensemble=self._is_ensemble, climatology=climatology,
@@ -711,6 +723,10 @@ class InferenceAggregator:
     def get_event_data(self):
         """`EventVerificationAggregator.get_data()` of the run (`events=...`)."""
         return self._aggregators["events"].get_data()
+
+    def get_fss_data(self):
+        """`FractionsSkillAggregator.get_data()` of the run (`events=..., event_neighbourhoods=...`)."""
+        return self._aggregators["fss"].get_data()
 
     def get_field_scores(self):
         """`FieldScoreAggregator.get_series()` of the run (`field_scores=True`)."""
