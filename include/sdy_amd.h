@@ -910,6 +910,76 @@ typedef struct sdy_spectrum_args {
 int sdy_degree_power(const sdy_spectrum_args* args, void* stream);
 int sdy_degree_power_host(const sdy_spectrum_args* args);
 
+/* Rotational and divergent kinetic-energy spectra of a horizontal wind (no counterpart in the reference; the definition is the
+ * library's own).  A wind with eastward component u and northward component v has the tangent components
+ * V_theta = -v (colatitude) and V_lambda = u.  In the orthonormal vector harmonics Psi = grad Y / sqrt(l (l + 1)) and
+ * Phi = r x grad Y / sqrt(l (l + 1)), with A_T[f](l, m) = sum_k w_k T[m][l][k] f_m(k) the Legendre analysis by a table T of what
+ * sdy_rfft_lon delivers:
+ *   s(l,m) = A_D[V_theta] - i A_M[V_lambda]     spheroidal: the divergent part
+ *   t(l,m) = A_D[V_lambda] + i A_M[V_theta]     toroidal: the rotational part
+ *   E_div(l) = 1/2 (|s(l,0)|^2 + 2 sum_{m = 1 .. min(l, mtr - 1)} |s(l,m)|^2),   E_rot(l) the same of t,   l < lmax
+ * so that sum_l (E_rot + E_div) = 1/2 integral of (u^2 + v^2) over the unit sphere for a band-limited wind on the
+ * Legendre-Gauss grid (not an identity on the equiangular grid with lmax = nlat); units (wind unit)^2 sr.
+ *
+ * The two tables, host-only and fp64, [mmax][lmax][nlat] each (P the table of sdy_sht_tables_host, norm "ortho", csphase), both
+ * divided by sqrt(l (l + 1)) with row l = 0 identically zero:
+ *   dtab = dP_l^m / dtheta in the ladder form, finite at the poles:
+ *          m >= 1: 1/2 [sqrt((l-m)(l+m+1)) P_l^{m+1} - sqrt((l+m)(l-m+1)) P_l^{m-1}],   m = 0: sqrt(l (l+1)) P_l^1
+ *   mtab = m P_l^m / sin(theta); at the two pole nodes of the equiangular grid its limit: 0 for m != 1, and
+ *          sign(cos theta) dP_l^1 / dtheta for m = 1.
+ * SDY_ERR_ARG for a NULL table, nlat or nlon < 2, lmax or mmax < 1 or an unknown grid.  No GPU needed. */
+int sdy_vsht_tables_host(int nlat, int nlon, int lmax, int mmax, int grid, double* dtab, double* mtab);
+
+/* The vector plan of an existing plan: the two tables above, quadrature-weighted, in fp32 on the device in the layout of the
+ * scalar analysis table ([mtr][nlat][lmax rounded up to 4]).  It owns nothing else -- the longitude FFT is the base plan's --
+ * and refers to the base plan, which must outlive it.  SDY_ERR_ARG for a NULL argument. */
+typedef struct sdy_vsht_plan sdy_vsht_plan;
+int sdy_vsht_plan_create(const sdy_sht_plan* plan, sdy_vsht_plan** out);
+void sdy_vsht_plan_destroy(sdy_vsht_plan* vplan);
+/* Vector Legendre analysis of Xf as sdy_rfft_lon of the base plan writes it: Cs_d = A_D and Cs_m = A_M of every field, in the
+ * layout and with the exact zeros (m > l) of sdy_legendre_fwd.  Both products run on the fp32 batched MFMA GEMM, whatever the
+ * base plan's gemm_mode: the derivative table has the opposite equatorial parity to the scalar table, so the folded
+ * split-fp16 kernels cannot take it as it is.  Cs_d and Cs_m must not overlap.  SDY_ERR_ARG for a NULL pointer or B, C < 1;
+ * SDY_ERR_ALIGN for an odd C. */
+int sdy_vector_legendre_fwd(const sdy_vsht_plan* vplan, const float* Xf, float* Cs_d, float* Cs_m, int B, int C, void* stream);
+
+/* One launch adds ONE window of all listed wind pairs to float64 accumulators that stay on the device; everything is as for
+ * sdy_degree_power above except what follows.
+ *   struct_size: sizeof of this structure.  It stands in for the sdy_abi_check handshake, whose list this structure is not
+ *              part of: a call with another value is refused (SDY_ERR_ARG).
+ *   gen_d, gen_m, target_d, target_m: dev float, Cs_d and Cs_m of sdy_vector_legendre_fwd for ONE image per side.  The u rows
+ *              and the v rows of a side are two runs of one field batch: the field decoding of sdy_degree_power names the u
+ *              field of a row (nvars counts pairs), and its v field lies gen_v_offset / target_v_offset fields further.
+ *   gen_scale, target_scale: as above, per field (u and v fields have their own).
+ *   accumulators: dev double, contiguous (nvars, n_timesteps, lmax) each.  gen_rot, gen_div, target_rot, target_div are
+ *              required; err_rot and err_div are both given or both NULL.  Each adds the mean over the rows of E_rot / E_div
+ *              of the row; the error of generated row (i0, i1) is taken of s_gen - s_target and t_gen - t_target against
+ *              target row i1.
+ * Per row and order the eight fp32 values (re / im of A_D[u], A_D[v], A_M[u], A_M[v]) are multiplied by their field's scale in
+ * float64, combined into s and t, and the m-weight times their squared moduli is added, orders ascending; rows meet as in
+ * sdy_degree_power (csrc/vector_spectrum.h, csrc/spectrum.h).  Device and host twin give the same bits.  16-byte loads where
+ * the two pointers of a side are 16-byte aligned and its field count, v offset and two strides are multiples of 4 (a group's
+ * last quad of fields is then loaded whole and the fields past its last row are discarded: they lie inside the plane).
+ * SDY_ERR_ARG additionally for a negative v offset or one that carries the last row past its buffer; SDY_ERR_UNSUPPORTED as for
+ * sdy_degree_power.  The _host twin takes HOST pointers. */
+typedef struct sdy_vector_spectrum_args sdy_vector_spectrum_args;
+struct sdy_vector_spectrum_args {
+  size_t struct_size;
+  const float *gen_d, *gen_m, *target_d, *target_m;
+  const float* gen_scale;
+  const float* target_scale;
+  int lmax, mtr;
+  int gen_fields, target_fields;
+  int gen_v_offset, target_v_offset;
+  int gen_var_stride, gen_time_stride;
+  int target_var_stride, target_time_stride;
+  int nvars, n0, n1, T;
+  int t_start, n_timesteps;
+  double *gen_rot, *gen_div, *target_rot, *target_div, *err_rot, *err_div;
+};
+int sdy_vector_degree_power(const sdy_vector_spectrum_args* args, void* stream);
+int sdy_vector_degree_power_host(const sdy_vector_spectrum_args* args);
+
 /* Per-trajectory time variance and lag-1 autocorrelation at every grid point (no counterpart in the reference): the second
  * moments along time of a rollout, kept on the device.  A trajectory is a member of a sample, or a sample's target.  For its
  * counted times x_1 .. x_n (fp32) at one grid point, in run order (csrc/variability.h):

@@ -29,7 +29,7 @@ from .fss import FractionsSkillAggregator  # noqa: F401
 from .variability import TimeVariabilityAggregator  # noqa: F401
 from .regions import RegionalMeanAggregator, Regions  # noqa: F401
 from .field_scores import FieldScoreAggregator, member_gram  # noqa: F401
-from .spectrum import PowerSpectrumAggregator, power_spectrum  # noqa: F401
+from .spectrum import KineticEnergySpectrumAggregator, PowerSpectrumAggregator, kinetic_energy_spectrum, power_spectrum  # noqa: F401
 from .data_writer import DataWriter, DataWriterConfig, PredictionDataWriter, TimeCoarsen, TimeCoarsenConfig  # noqa: F401
 
 __version__ = "0.1.0"

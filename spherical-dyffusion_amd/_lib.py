@@ -285,6 +285,29 @@ class SdySpectrumArgs(C.Structure):
     ]
 
 
+class SdyVectorSpectrumArgs(C.Structure):
+    """`sdy_vector_spectrum_args`.  It carries its own size (`struct_size`, filled in here) and is therefore not part of
+    `ABI_STRUCTS`: the library refuses a structure of another size at every call."""
+    _fields_ = [
+        ("struct_size", C.c_size_t),
+        ("gen_d", C.c_void_p), ("gen_m", C.c_void_p), ("target_d", C.c_void_p), ("target_m", C.c_void_p),
+        ("gen_scale", C.c_void_p), ("target_scale", C.c_void_p),
+        ("lmax", C.c_int), ("mtr", C.c_int),
+        ("gen_fields", C.c_int), ("target_fields", C.c_int),
+        ("gen_v_offset", C.c_int), ("target_v_offset", C.c_int),
+        ("gen_var_stride", C.c_int), ("gen_time_stride", C.c_int),
+        ("target_var_stride", C.c_int), ("target_time_stride", C.c_int),
+        ("nvars", C.c_int), ("n0", C.c_int), ("n1", C.c_int), ("T", C.c_int),
+        ("t_start", C.c_int), ("n_timesteps", C.c_int),
+        ("gen_rot", C.c_void_p), ("gen_div", C.c_void_p), ("target_rot", C.c_void_p), ("target_div", C.c_void_p),
+        ("err_rot", C.c_void_p), ("err_div", C.c_void_p),
+    ]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_size = C.sizeof(type(self))
+
+
 class SdyVariabilityArgs(C.Structure):
     _anonymous_ = ("win",)
     _fields_ = [
@@ -533,6 +556,12 @@ SIGNATURES = {
     "sdy_member_stats_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "sdy_degree_power": (C.c_int, [C.POINTER(SdySpectrumArgs), C.c_void_p]),
     "sdy_degree_power_host": (C.c_int, [C.POINTER(SdySpectrumArgs)]),
+    "sdy_vsht_tables_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "sdy_vsht_plan_create": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "sdy_vsht_plan_destroy": (None, [C.c_void_p]),
+    "sdy_vector_legendre_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "sdy_vector_degree_power": (C.c_int, [C.POINTER(SdyVectorSpectrumArgs), C.c_void_p]),
+    "sdy_vector_degree_power_host": (C.c_int, [C.POINTER(SdyVectorSpectrumArgs)]),
     "sdy_time_variability_accumulate": (C.c_int, [C.POINTER(SdyVariabilityArgs), C.c_void_p]),
     "sdy_time_variability_accumulate_host": (C.c_int, [C.POINTER(SdyVariabilityArgs)]),
     "sdy_time_variability_maps": (C.c_int, [C.POINTER(SdyVariabilityMapsArgs), C.c_void_p]),

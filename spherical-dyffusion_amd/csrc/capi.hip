@@ -365,6 +365,67 @@ extern "C" int sdy_legendre_fwd(const sdy_sht_plan* p, const float* Xf, float* C
   return legendre_fwd_impl(p, Xf, Cs, B, C, false, stream, false, false);
 }
 
+// Vector plan: the derivative and the m / sin(theta) table of a plan's grid (sdy_vsht_tables_host), quadrature-weighted, fp32,
+// in the layout of d_wqT.  Only the fp32 GEMM reads them: the derivative table has the opposite equatorial parity to the table
+// leg_par folds, and the fp16 range of either has not been looked at.
+struct sdy_vsht_plan {
+  const sdy_sht_plan* base = nullptr;
+  float* d_dT = nullptr;   // [mtr][nlat][Lpad4]
+  float* d_mT = nullptr;   // [mtr][nlat][Lpad4]
+};
+
+extern "C" void sdy_vsht_plan_destroy(sdy_vsht_plan* v) {
+  if (!v) return;
+  if (v->d_dT) (void)hipFree(v->d_dT);
+  if (v->d_mT) (void)hipFree(v->d_mT);
+  delete v;
+}
+
+extern "C" int sdy_vsht_plan_create(const sdy_sht_plan* p, sdy_vsht_plan** out) {
+  if (!p || !out) return SDY_ERR_ARG;
+  const int nlat = p->nlat, lmax = p->lmax, mtr = p->mtr;
+  std::vector<double> dtab((size_t)mtr * lmax * nlat), mtab((size_t)mtr * lmax * nlat), w(nlat);
+  SDY_TRY(sdy_vsht_tables_host(nlat, p->nlon, lmax, mtr, p->grid, dtab.data(), mtab.data()));
+  SDY_TRY(sdy_sht_tables_host(nlat, p->nlon, lmax, mtr, p->grid, nullptr, w.data(), nullptr));
+  std::vector<float> dT((size_t)mtr * nlat * p->Lpad4, 0.0f), mT((size_t)mtr * nlat * p->Lpad4, 0.0f);
+  for (int m = 0; m < mtr; ++m)
+    for (int l = 0; l < lmax; ++l)
+      for (int k = 0; k < nlat; ++k) {
+        const size_t from = ((size_t)m * lmax + l) * nlat + k, to = ((size_t)m * nlat + k) * p->Lpad4 + l;
+        dT[to] = (float)(dtab[from] * w[k]);
+        mT[to] = (float)(mtab[from] * w[k]);
+      }
+  sdy_vsht_plan* v = new sdy_vsht_plan();
+  v->base = p;
+  hipError_t e = upload(&v->d_dT, dT);
+  if (e == hipSuccess) e = upload(&v->d_mT, mT);
+  if (e != hipSuccess) { sdy_vsht_plan_destroy(v); return (int)e; }
+  *out = v;
+  return SDY_OK;
+}
+
+// Both products on the fp32 batched GEMM, set up as legendre_fwd_impl does for LEG_GEMM_F32; m > l zeroed as sdy_legendre_fwd does
+extern "C" int sdy_vector_legendre_fwd(const sdy_vsht_plan* v, const float* Xf, float* Cs_d, float* Cs_m, int B, int C,
+                                       void* stream) {
+  if (!v || !v->base || !Xf || !Cs_d || !Cs_m || B <= 0 || C <= 0) return SDY_ERR_ARG;
+  if (C & 1) return SDY_ERR_ALIGN;
+  const sdy_sht_plan* p = v->base;
+  const int N = 2 * B * C;
+  const float* tables[2] = {v->d_dT, v->d_mT};
+  float* outs[2] = {Cs_d, Cs_m};
+  for (int i = 0; i < 2; ++i) {
+    SDY_TRY(sdy_spec_zero_upper_launch(outs[i], p->lmax, p->mtr, N, (hipStream_t)stream));
+    GemmParams g{};
+    g.A = tables[i]; g.lda = p->Lpad4; g.sA = (long)p->nlat * p->Lpad4;
+    g.B = Xf; g.ldb = N; g.sB = (long)p->nlat * N;
+    g.C = outs[i]; g.ldc = p->mtr * N; g.sC = N;
+    g.M = p->Lpad4; g.M_store = p->lmax; g.N = N; g.K = p->nlat; g.nbatch = p->mtr;
+    g.tri_mode = SDY_TRI_LEG_FWD; g.tile = SDY_TILE_64x128;
+    SDY_TRY(sdy_gemm_launch(g, (hipStream_t)stream));
+  }
+  return SDY_OK;
+}
+
 static int legendre_inv_impl(const sdy_sht_plan* p, const float* Cs, float* Yf, int B, int C, bool polar, void* stream,
                              bool tiled, bool cs_tiled) {
   if (!p || !Cs || !Yf || B <= 0 || C <= 0) return SDY_ERR_ARG;

@@ -136,6 +136,44 @@ extern "C" int sdy_sht_tables_host(int nlat, int nlon, int lmax, int mmax, int g
   return SDY_OK;
 }
 
+// The two tables of the vector Legendre analysis (include/sdy_amd.h), [mmax][lmax][nlat] each, both divided by sqrt(l (l + 1)):
+//   D = dP_l^m / dtheta in the ladder form (finite at the poles; it needs one order more than the scalar table keeps)
+//   M = m P_l^m / sin(theta); at the two pole nodes of the equiangular grid its limit: 0, for m = 1 sign(cos theta) dP_l^1/dtheta
+extern "C" int sdy_vsht_tables_host(int nlat, int nlon, int lmax, int mmax, int grid, double* dtab, double* mtab) {
+  if (nlat < 2 || nlon < 2 || lmax < 1 || mmax < 1 || !dtab || !mtab) return SDY_ERR_ARG;
+  if (grid != SDY_GRID_LEGENDRE_GAUSS && grid != SDY_GRID_EQUIANGULAR) return SDY_ERR_ARG;
+  const size_t K = (size_t)nlat;
+  std::vector<double> pct((size_t)(mmax + 1) * lmax * K), theta(nlat);
+  const int r = sdy_sht_tables_host(nlat, nlon, lmax, mmax + 1, grid, pct.data(), nullptr, theta.data());
+  if (r != SDY_OK) return r;
+  auto P = [&](int m, int l) { return pct.data() + ((size_t)m * lmax + l) * K; };
+  const bool poles = grid == SDY_GRID_EQUIANGULAR;   // Clenshaw-Curtis: nodes 0 and nlat - 1 are theta = 0 and pi
+  for (int m = 0; m < mmax; ++m)
+    for (int l = 0; l < lmax; ++l) {
+      double* d = dtab + ((size_t)m * lmax + l) * K;
+      double* q = mtab + ((size_t)m * lmax + l) * K;
+      if (l == 0 || l < m) {
+        for (size_t k = 0; k < K; ++k) d[k] = q[k] = 0.0;
+        continue;
+      }
+      const double norm = std::sqrt((double)l * (l + 1.0));
+      const double* up = P(m + 1, l);                      // identically zero for m + 1 > l
+      const double* dn = m > 0 ? P(m - 1, l) : nullptr;
+      const double* p = P(m, l);
+      const double cu = std::sqrt((double)(l - m) * (l + m + 1.0)), cd = std::sqrt((double)(l + m) * (l - m + 1.0));
+      for (size_t k = 0; k < K; ++k) {
+        const double dp = m == 0 ? norm * up[k] : 0.5 * (cu * up[k] - cd * dn[k]);
+        d[k] = dp / norm;
+        const bool pole = poles && (k == 0 || k == K - 1);
+        if (!pole)
+          q[k] = m * p[k] / std::sin(theta[k]) / norm;
+        else
+          q[k] = m == 1 ? (k == 0 ? d[k] : -d[k]) : 0.0;
+      }
+    }
+  return SDY_OK;
+}
+
 // n = product of radices, radices from {4, 2, 3, 5}; returns SDY_ERR_UNSUPPORTED for other prime factors.
 int sdy_factor_radices(int n, int* radices, int* nstages) {
   int cnt = 0;

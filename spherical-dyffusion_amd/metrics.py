@@ -22,7 +22,7 @@ from .events import Events, EventVerificationAggregator
 from .fss import FractionsSkillAggregator
 from .field_scores import FieldScoreAggregator
 from .regions import RegionalMeanAggregator, Regions
-from .spectrum import PowerSpectrumAggregator
+from .spectrum import KineticEnergySpectrumAggregator, PowerSpectrumAggregator
 from .variability import TimeVariabilityAggregator
 from .windows import FieldAccumulator, TorchDistributed, fill_window, whole_ics_message, window_layouts  # noqa: F401
 
@@ -571,6 +571,9 @@ class InferenceAggregator:
 
     `power_spectrum_data=True` adds `power_spectrum` (`sdy_amd.spectrum.PowerSpectrumAggregator` on the grid `spectrum_grid`):
     per-degree power of gen, target and error per lead time, read with `get_power_spectrum_data()`; no log keys either.
+    `wind_pairs=<mapping label -> (u_name, v_name)>` (`sdy_amd.spectrum.wind_pairs(names)` builds it) adds `kinetic_energy`
+    (`sdy_amd.KineticEnergySpectrumAggregator` on the same grid): the rotational and divergent kinetic-energy spectra of gen,
+    target and error winds per lead time, read with `get_kinetic_energy_data()`; no log keys.  The default `None` adds nothing.
 
     `ensemble_time_mean_data=True` adds `time_mean_ensemble` (`sdy_amd.EnsembleTimeMeanAggregator`): one time-mean map per
     member and the statistics the reference's full-rollout evaluation takes of them (`rmse_member_avg`, `bias_member_avg`,
@@ -622,7 +625,7 @@ class InferenceAggregator:
                  rank_histogram_pool_times: bool = False, time_variability_data: bool = False,
                  regions: Optional[Regions] = None, events: Optional[Events] = None, event_pool_times: bool = False,
                  event_frequency_maps: bool = False, field_scores: bool = False, climatology=None,
-                 event_neighbourhoods: Optional[Sequence[int]] = None):
+                 event_neighbourhoods: Optional[Sequence[int]] = None, wind_pairs=None):
         if log_video or enable_extended_videos or log_zonal_mean_images:
             raise NotImplementedError("video / zonal-mean image logging is out of scope of sdy_amd (DESIGN.md section 8)")
         if n_timesteps is None:
@@ -647,6 +650,9 @@ class InferenceAggregator:
         if power_spectrum_data:
             self._aggregators["power_spectrum"] = PowerSpectrumAggregator(n_timesteps=n_timesteps, grid=spectrum_grid,
                                                                           dist=dist, metadata=metadata)
+        if wind_pairs is not None:
+            self._aggregators["kinetic_energy"] = KineticEnergySpectrumAggregator(
+                wind_pairs, n_timesteps=n_timesteps, grid=spectrum_grid, dist=dist, metadata=metadata)
         if ensemble_time_mean_data or ensemble_time_mean_spread:
             self._aggregators["time_mean_ensemble"] = EnsembleTimeMeanAggregator(
                 area_weights, dist=dist, metadata=metadata, spread=ensemble_time_mean_spread)
@@ -735,6 +741,10 @@ class InferenceAggregator:
     def get_regional_series(self):
         """`RegionalMeanAggregator.get_series()` of the run (`regions=...`)."""
         return self._aggregators["mean_regional"].get_series()
+
+    def get_kinetic_energy_data(self):
+        """`KineticEnergySpectrumAggregator.get_data()` of the run (`wind_pairs=...`)."""
+        return self._aggregators["kinetic_energy"].get_data()
 
     def get_power_spectrum_data(self):
         """`PowerSpectrumAggregator.get_data()` of the run (`power_spectrum_data=True`)."""

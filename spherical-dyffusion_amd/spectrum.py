@@ -16,16 +16,29 @@ Fields in physical units: the split-fp16 Legendre analysis stages its input as f
 pressure in Pa would leave its range.  Every field is therefore handed to the FFT divided by the power of two at or above its
 largest magnitude (the FFT's fused per-field factor), and the reduction multiplies the coefficients back in float64; both
 steps are exact, so the result is what the unscaled fp32 arithmetic would give.
+
+Winds: `kinetic_energy_spectrum` and `KineticEnergySpectrumAggregator` give the rotational and the divergent kinetic-energy
+spectrum of a horizontal wind (u eastward, v northward).  A wind is a vector: on a latitude-longitude grid u and v are not
+scalars on the sphere, and their scalar spectra neither add up to its energy spectrum nor separate rotation from divergence.
+With V_theta = -v, V_lambda = u and the analyses A_D, A_M by the derivative table and the m / sin(theta) table of the plan's
+vector plan (`sdy_vsht_plan_create`, `sdy_vector_legendre_fwd`; include/sdy_amd.h),
+
+    s = A_D[V_theta] - i A_M[V_lambda]      t = A_D[V_lambda] + i A_M[V_theta]
+    E_div(l) = 1/2 (|s[l,0]|^2 + 2 sum_m |s[l,m]|^2)      E_rot(l) the same of t          l < lmax
+
+reduced by one `sdy_vector_degree_power` launch (`csrc/vector_spectrum.hip`).  sum_l (E_rot + E_div) is half the integral of
+u^2 + v^2 over the unit sphere for a band-limited wind on the Legendre-Gauss grid; divide by 4 pi for a mean energy per unit
+mass.  The u rows and the v rows of a side are two equal runs of ONE field batch, so one FFT and one stage call serve both.
 """
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, List, Optional
+from typing import Dict, Iterable, List, Mapping, Optional, Tuple
 
 import torch
 
-from ._lib import SdySpectrumArgs, check, current_stream, lib, ptr
-from .windows import FieldAccumulator
+from ._lib import SdySpectrumArgs, SdyVectorSpectrumArgs, check, current_stream, lib, ptr
+from .windows import FieldAccumulator, runs, window_layouts
 from .sht import ShtPlan
 
 #: default `max_workspace_bytes`: packed rows, grid-frequency tensor and the coefficients of both sides of one chunk
@@ -256,4 +269,281 @@ class PowerSpectrumAggregator(FieldAccumulator):
             shape = (self._n_timesteps, self._degrees(self._grids[i]))
             data[name] = {label: red(self._view(stat, i, *shape) / n)
                           for label, stat in (("gen", "gen_power"), ("target", "target_power"), ("error", "err_power"))}
+        return data
+
+
+# ---- winds: rotational and divergent kinetic-energy spectra ------------------------------------------------------------------
+class VectorShtPlan:
+    """The vector plan of a cached `ShtPlan` (`sdy_vsht_plan`): the two quadrature-weighted fp32 tables of the vector Legendre
+    analysis on the device.  It keeps its base plan alive; the longitude FFT stays the base plan's."""
+
+    _cache: Dict[int, "VectorShtPlan"] = {}
+
+    def __init__(self, base: ShtPlan):
+        h = C.c_void_p()
+        check(lib.sdy_vsht_plan_create(base.handle, C.byref(h)), "sdy_vsht_plan_create")
+        self.handle, self.base = h, base
+
+    @classmethod
+    def get(cls, base: ShtPlan) -> "VectorShtPlan":
+        """The vector plan of `base`, created on the current device (the caller is inside `torch.cuda.device`)."""
+        if id(base) not in cls._cache:
+            cls._cache[id(base)] = cls(base)
+        return cls._cache[id(base)]
+
+    def __del__(self):
+        try:
+            if getattr(self, "handle", None):
+                lib.sdy_vsht_plan_destroy(self.handle)
+                self.handle = None
+        except Exception:
+            pass
+
+
+def wind_pairs(names: Iterable[str]) -> Dict[str, Tuple[str, str]]:
+    """`label -> (u_name, v_name)` of the winds among `names`, in their order: `eastward_wind_<k>` / `northward_wind_<k>` as
+    `wind_<k>`, `UGRD10m` / `VGRD10m` as `wind_10m`.  A component without its partner is left out."""
+    names = list(names)
+    have, out = set(names), {}
+    for n in names:
+        if n.startswith("eastward_wind_") and "northward_wind_" + n[len("eastward_wind_"):] in have:
+            k = n[len("eastward_wind_"):]
+            out[f"wind_{k}"] = (n, f"northward_wind_{k}")
+        elif n == "UGRD10m" and "VGRD10m" in have:
+            out["wind_10m"] = ("UGRD10m", "VGRD10m")
+    return out
+
+
+def _vector_analyse(plan: ShtPlan, x: torch.Tensor, Xf: torch.Tensor, Cd: torch.Tensor, Cm: torch.Tensor,
+                    zeros: torch.Tensor) -> torch.Tensor:
+    """A_D and A_M of the fields x (F, H, W), F % 4 == 0, into Cd and Cm; returns the per-field scale to undo."""
+    F = x.shape[0]
+    inv, scale = _field_scales(x)
+    check(lib.sdy_rfft_lon(plan.handle, ptr(x), ptr(inv), ptr(zeros), None, ptr(Xf), 1, F, current_stream()), "sdy_rfft_lon")
+    check(lib.sdy_vector_legendre_fwd(VectorShtPlan.get(plan).handle, ptr(Xf), ptr(Cd), ptr(Cm), 1, F, current_stream()),
+          "sdy_vector_legendre_fwd")
+    return scale
+
+
+@torch.no_grad()
+def kinetic_energy_spectrum(u: torch.Tensor, v: torch.Tensor, grid: str = "equiangular", lmax: Optional[int] = None,
+                            max_workspace_bytes: Optional[int] = None) -> Dict[str, torch.Tensor]:
+    """u, v (..., nlat, nlon) float32 on the device, eastward and northward -> {"rot", "div"} float64 (..., lmax): the
+    rotational and the divergent kinetic-energy spectrum of every wind (module docstring)."""
+    if not (u.is_cuda and v.is_cuda):
+        raise RuntimeError("sdy_amd spectra run on the GPU only (no CPU fallback); got a CPU tensor")
+    if u.dim() < 2 or tuple(u.shape) != tuple(v.shape):
+        raise ValueError(f"expected u and v of one shape (..., nlat, nlon), got {tuple(u.shape)} and {tuple(v.shape)}")
+    if u.device != v.device:
+        raise ValueError(f"u on {u.device}, v on {v.device}")
+    H, W = u.shape[-2:]
+    lead = tuple(u.shape[:-2])
+    ru, rv = u.reshape(-1, H, W).to(torch.float32), v.reshape(-1, H, W).to(torch.float32)
+    n = ru.shape[0]
+    if n < 1:
+        raise ValueError("empty tensor")
+    limit = DEFAULT_MAX_WORKSPACE_BYTES if max_workspace_bytes is None else int(max_workspace_bytes)
+    with torch.cuda.device(u.device):
+        plan = _plan(H, W, lmax, None, grid, u.device)
+        per_x, per_cs = _floats_per_field(plan)
+        per_wind = 2 * (per_x + 2 * per_cs + 1)                # two fields, two coefficient tensors each
+        step = min(max(limit - _SLACK, 0) // (4 * per_wind) // 4 * 4, _MAX_ROWS_PER_CALL)
+        if step < 4:
+            raise ValueError(f"kinetic_energy_spectrum: four winds need {16 * per_wind} bytes of workspace, more than "
+                             f"max_workspace_bytes = {limit}")
+        rot = torch.zeros(n, plan.lmax, dtype=torch.float64, device=u.device)
+        div = torch.zeros_like(rot)
+        ws = _Workspace()
+        for r0 in range(0, n, step):
+            k = min(step, n - r0)
+            Fh = _round_up(k, 4)
+            F = 2 * Fh
+            xb, Xf, Cd, Cm, zeros = ws.parts(u.device, F * H * W, F * plan.mtr * H * 2, F * per_cs, F * per_cs, F)
+            xb = xb.view(2, Fh, H, W)
+            xb[0, :k].copy_(ru[r0:r0 + k])
+            xb[1, :k].copy_(rv[r0:r0 + k])
+            xb[:, k:].zero_()
+            zeros.zero_()
+            scale = _vector_analyse(plan, xb.view(F, H, W), Xf, Cd, Cm, zeros)
+            unused = torch.zeros(2, k, plan.lmax, dtype=torch.float64, device=u.device)
+            a = SdyVectorSpectrumArgs()
+            a.gen_d = a.target_d = ptr(Cd)
+            a.gen_m = a.target_m = ptr(Cm)
+            a.gen_scale = a.target_scale = ptr(scale)
+            a.lmax, a.mtr, a.gen_fields, a.target_fields = plan.lmax, plan.mtr, F, F
+            a.gen_v_offset = a.target_v_offset = Fh
+            a.gen_var_stride = a.target_var_stride = 0
+            a.gen_time_stride = a.target_time_stride = 1
+            a.nvars, a.n0, a.n1, a.T, a.t_start, a.n_timesteps = 1, 1, 1, k, 0, k
+            a.gen_rot, a.gen_div = rot[r0:r0 + k].data_ptr(), div[r0:r0 + k].data_ptr()
+            a.target_rot, a.target_div, a.err_rot, a.err_div = unused[0].data_ptr(), unused[1].data_ptr(), None, None
+            check(lib.sdy_vector_degree_power(C.byref(a), current_stream()), "sdy_vector_degree_power")
+    return {"rot": rot.view(*lead, plan.lmax), "div": div.view(*lead, plan.lmax)}
+
+
+class KineticEnergySpectrumAggregator(FieldAccumulator):
+    """Rotational and divergent kinetic-energy spectra of the generated and the target winds and of their difference, per wind
+    pair and lead time (module docstring; no counterpart in the reference).
+
+    `pairs` maps a label to `(u_name, v_name)`, eastward and northward (`wind_pairs(names)` builds it from the names of the
+    headline job).  Same `record_batch` as the other field aggregators, on the denormalised dicts -- member-stacked or flat
+    gen, contiguous or the time-sliced views of the window driver, `i_time_start` -- but only the paired variables are read.
+    A window is cut into chunks of pairs; per side a chunk's rows are packed into ONE field batch, the u rows of every (pair,
+    time) first and the v rows as a second, equal run (each group of rows padded with zero fields to a multiple of four),
+    transformed with `sdy_rfft_lon` of the cached `ShtPlan` and `sdy_vector_legendre_fwd` of its vector plan (fp32 MFMA GEMM)
+    and reduced by ONE `sdy_vector_degree_power` launch.  Chunks are sized so that packed rows, grid-frequency tensor and the
+    two coefficient tensors of both sides stay within `max_workspace_bytes` (default `DEFAULT_MAX_WORKSPACE_BYTES`); the
+    workspace is one grow-only buffer, reused by every window.
+
+    Per pair, time and degree l < lmax (default: lat) six float64 accumulators `(n_timesteps, lmax)` on the device add the
+    mean over the rows of E_rot and E_div of the generated winds, of the target winds, and of (generated row - its target
+    row), taken from the coefficient differences.  `get_data()` returns `{label: {"gen_rot", "gen_div", "target_rot",
+    "target_div", "error_rot", "error_div"}}`, each divided by the number of batches seen at that time and combined over ranks
+    with the equal-weight `dist.reduce_mean`.  `get_logs` returns {}: no log keys are added.
+
+    Ensembles are pooled over members x samples, the error of row (member, sample) taken against target row `sample`, as
+    `PowerSpectrumAggregator` does.  `ValueError` for a pair whose variable is missing from either dict, whose u and v differ
+    in shape or layout, or that names one variable twice."""
+
+    _STATS = (("gen_rot", "gen_rot"), ("gen_div", "gen_div"), ("target_rot", "target_rot"), ("target_div", "target_div"),
+              ("error_rot", "err_rot"), ("error_div", "err_div"))          # label of get_data, field of the argument structure
+
+    def __init__(self, pairs: Mapping[str, Tuple[str, str]], n_timesteps: int, grid: str = "equiangular",
+                 lmax: Optional[int] = None, dist=None, metadata=None, max_bytes: Optional[int] = None,
+                 max_workspace_bytes: Optional[int] = None):
+        super().__init__(n_timesteps, dist=dist, metadata=metadata, max_bytes=max_bytes)
+        self._pairs = {str(label): (str(uv[0]), str(uv[1])) for label, uv in dict(pairs).items()}
+        if not self._pairs:
+            raise ValueError("KineticEnergySpectrumAggregator: no wind pairs")
+        for label, (un, vn) in self._pairs.items():
+            if un == vn:
+                raise ValueError(f"wind pair {label!r} names {un!r} twice")
+        self._grid = grid
+        self._lmax = None if lmax is None else int(lmax)
+        self._limit = DEFAULT_MAX_WORKSPACE_BYTES if max_workspace_bytes is None else int(max_workspace_bytes)
+        self._ws = _Workspace()
+
+    def _statistics(self) -> Dict[str, float]:
+        return {stat: 0.0 for _, stat in self._STATS}
+
+    def _elements(self, stat: str, job: tuple) -> int:
+        return self._n_timesteps * self._degrees(job)
+
+    def _degrees(self, job: tuple) -> int:
+        _, H, _ = job
+        return self._lmax or H
+
+    @property
+    def workspace_bytes(self) -> int:
+        """Bytes of the workspace as it stands (it only grows)."""
+        return self._ws.bytes
+
+    def _layouts(self, target_data, gen_data):
+        """The `WindowLayout`s of the u and of the v variables, pair by pair, everything checked."""
+        for label, (un, vn) in self._pairs.items():
+            for name in (un, vn):
+                if name not in gen_data or name not in target_data:
+                    raise ValueError(f"wind pair {label!r}: no {'generated' if name not in gen_data else 'target'} "
+                                     f"variable {name!r}")
+        lay_u = window_layouts({k: target_data[un] for k, (un, _) in self._pairs.items()},
+                               {k: gen_data[un] for k, (un, _) in self._pairs.items()})
+        lay_v = window_layouts({k: target_data[vn] for k, (_, vn) in self._pairs.items()},
+                               {k: gen_data[vn] for k, (_, vn) in self._pairs.items()})
+        for (label, (un, vn)), a, b in zip(self._pairs.items(), lay_u, lay_v):
+            if gen_data[un].dim() != gen_data[vn].dim() or self._extents(a) != self._extents(b):
+                raise ValueError(f"wind pair {label!r}: {un!r} {tuple(gen_data[un].shape)} and {vn!r} "
+                                 f"{tuple(gen_data[vn].shape)} differ in shape or layout")
+        if lay_v[0].T != lay_u[0].T:
+            raise ValueError("the variables of one window differ in their number of times")
+        return lay_u, lay_v
+
+    @staticmethod
+    def _extents(l) -> tuple:
+        return (l.n0, l.n1, l.T, l.H, l.W)
+
+    def _chunk(self, lay_u, lay_v, first: int, last: int, t_start: int, device) -> None:
+        """Pairs first .. last - 1 (one shape): pack, transform and reduce both sides."""
+        n0, n1, T, H, W = self._extents(lay_u[first])
+        nv, R = last - first, n0 * n1
+        Rp, Sp = _round_up(R, 4), _round_up(n1, 4)
+        half_g, half_t = nv * T * Rp, nv * T * Sp                # the u run of a side; its v run follows
+        Fg, Ft = 2 * half_g, 2 * half_t
+        plan = _plan(H, W, self._lmax, None, self._grid, device)
+        per_cs = plan.lmax * plan.mtr * 2
+        Fx = max(Fg, Ft)
+        xb, Xf, Cgd, Cgm, Ctd, Ctm, zeros = self._ws.parts(device, Fx * H * W, Fx * plan.mtr * H * 2, Fg * per_cs, Fg * per_cs,
+                                                           Ft * per_cs, Ft * per_cs, Fx)
+        zeros.zero_()
+        scales = []
+        for side, F, rows, rows_p, Cd, Cm in (("gen", Fg, R, Rp, Cgd, Cgm), ("target", Ft, n1, Sp, Ctd, Ctm)):
+            x = xb[:F * H * W].view(2, nv, T, rows_p, H, W)
+            if rows_p != rows:
+                x[:, :, :, rows:].zero_()
+            for c, lay in enumerate((lay_u, lay_v)):
+                for k in range(nv):
+                    l = lay[first + k]
+                    if side == "gen":
+                        src = torch.as_strided(l.gen, (n0, n1, T, H, W), (l.gs0, l.gs1, H * W, W, 1)).permute(2, 0, 1, 3, 4)
+                        x[c, k, :, :rows].view(T, n0, n1, H, W).copy_(src)
+                    else:
+                        src = torch.as_strided(l.target, (n1, T, H, W), (l.ts1, H * W, W, 1)).permute(1, 0, 2, 3)
+                        x[c, k, :, :rows].copy_(src)
+            scales.append(_vector_analyse(plan, x.view(F, H, W), Xf[:F * plan.mtr * H * 2], Cd, Cm, zeros))
+        a = SdyVectorSpectrumArgs()
+        a.gen_d, a.gen_m, a.target_d, a.target_m = ptr(Cgd), ptr(Cgm), ptr(Ctd), ptr(Ctm)
+        a.gen_scale, a.target_scale = ptr(scales[0]), ptr(scales[1])
+        a.lmax, a.mtr, a.gen_fields, a.target_fields = plan.lmax, plan.mtr, Fg, Ft
+        a.gen_v_offset, a.target_v_offset = half_g, half_t
+        a.gen_var_stride, a.gen_time_stride, a.target_var_stride, a.target_time_stride = T * Rp, Rp, T * Sp, Sp
+        a.nvars, a.n0, a.n1, a.T, a.t_start, a.n_timesteps = nv, n0, n1, T, t_start, self._n_timesteps
+        for stat in self._acc:
+            setattr(a, stat, self._at(stat, first))
+        check(lib.sdy_vector_degree_power(C.byref(a), current_stream()), "sdy_vector_degree_power")
+
+    def _pairs_per_chunk(self, l, device) -> int:
+        n0, n1, T, H, W = self._extents(l)
+        plan = _plan(H, W, self._lmax, None, self._grid, device)
+        per_x, per_cs = _floats_per_field(plan)
+        fg, ft = 2 * T * _round_up(n0 * n1, 4), 2 * T * _round_up(n1, 4)
+        if fg > _MAX_FIELDS or fg * H * W > (1 << 31) - 1:
+            raise ValueError(f"KineticEnergySpectrumAggregator: one pair of a window is {fg} fields of {H} x {W}; one "
+                             f"transform call takes at most {_MAX_FIELDS} fields and 2^31 - 1 grid values")
+        per_pair = 4 * (fg * per_x + 2 * (fg + ft) * per_cs + fg)
+        n = min(max(self._limit - _SLACK, 0) // per_pair, _MAX_FIELDS // fg, ((1 << 31) - 1) // (fg * H * W))
+        if n < 1:
+            raise ValueError(f"KineticEnergySpectrumAggregator: one pair of a window ({fg} + {ft} fields of {H} x {W}) needs "
+                             f"{per_pair} bytes of workspace, more than max_workspace_bytes = {self._limit} allows")
+        return n
+
+    @torch.no_grad()
+    def record_batch(self, loss, target_data, gen_data, target_data_norm=None, gen_data_norm=None, i_time_start: int = 0):
+        del loss, target_data_norm, gen_data_norm
+        i_time_start = int(i_time_start)
+        lay_u, lay_v = self._layouts(target_data, gen_data)
+        T = lay_u[0].T
+        if i_time_start < 0 or i_time_start + T > self._n_timesteps:
+            raise ValueError(f"times {i_time_start}..{i_time_start + T - 1} outside the aggregator's {self._n_timesteps}")
+        if not all(l.gen.is_cuda and l.target.is_cuda for l in lay_v):
+            raise RuntimeError("sdy_amd aggregators run on the GPU only (no CPU fallback)")
+        first_device = lay_u[0].gen.device
+        for l in lay_v:
+            if l.gen.device != first_device or l.target.device != first_device:
+                raise ValueError(f"tensors on {l.gen.device} / {l.target.device}, the pair's u on {first_device}")
+        device = self._prepare(list(self._pairs), lay_u)
+        with torch.cuda.device(device):
+            for first, last in runs(lay_u, self._extents):
+                step = self._pairs_per_chunk(lay_u[first], device)
+                for c0 in range(first, last, step):
+                    self._chunk(lay_u, lay_v, c0, min(c0 + step, last), i_time_start, device)
+        for t in range(i_time_start, i_time_start + T):
+            self._n_batches[t] += 1
+
+    @torch.no_grad()
+    def get_data(self) -> Dict[str, Dict[str, torch.Tensor]]:
+        n = self._counts()[:, None]
+        red = self._dist.reduce_mean
+        data = {}
+        for i, name in enumerate(self._names):
+            shape = (self._n_timesteps, self._degrees(self._grids[i]))
+            data[name] = {label: red(self._view(stat, i, *shape) / n) for label, stat in self._STATS}
         return data
