@@ -1222,6 +1222,59 @@ int sdy_fss_encode(const sdy_fss_args* args, void* stream);   /* the first launc
 int sdy_fss_sum(const sdy_fss_args* args, void* stream);      /* the second: ws holds the codes of sdy_fss_encode of the same args */
 size_t sdy_fss_workspace_bytes(int nvars, int n_events, int n1, int T, int H, int W);   /* 0 for an argument out of range */
 
+/* Spell durations of threshold events: how long an event lasts along a trajectory -- consecutive dry days, warm spells (no
+ * counterpart in the reference).  window: see sdy_window, plane = H*W: n0 = M members, n1 samples.  Events, "in the event" and
+ * the thresholds (scalars / maps / below / is_map / map_first / n_maps) are those of sdy_event_args above; the fields carry the
+ * same names.  One definition for the kernel and the _host twin: csrc/spells.h (integers and comparisons only).
+ *   struct_size: sizeof of this structure.  It stands in for the sdy_abi_check handshake, whose list this structure is not
+ *              part of: a call with another value is refused (SDY_ERR_ARG).
+ * A trajectory is one member of one sample, or one sample's target, at one grid point: row r of rows = n0*n1 + n1, the
+ * generated ones first (member r / n1, sample r % n1), then the targets.  Its counted times are the window times t0 .. T - 1
+ * of every call, in call order; t0 == T is SDY_OK and launches nothing.  A value is in event e as for sdy_event_args; a NaN
+ * value never is, for the target too, so it ends a spell.  A spell is a maximal run of consecutive counted times in the event.
+ *   state:     dev, 32-bit unsigned words, contiguous (nvars, E, 4, rows, H*W), 8-byte aligned, zeroed by the caller before
+ *              the first window and carried from call to call: word 0 = run, the length of the spell open after the last
+ *              counted time (0 when that time was outside the event); 1 = longest, the maximum run has reached; 2 = spells,
+ *              the spells begun; 3 = hits, the counted times in the event.  Read and written once per call.
+ *   durations: dev double, contiguous (nvars, E, 2, H, 16), zeroed by the caller: durations[v, e, side, lat, bin] += the spells
+ *              of length d that END in this call at latitude lat, pooled over the longitudes and the generated (side 0) or
+ *              target (side 1) trajectories; bin = the number of edges 1, 2, 4, .., 16384 below d, at most 15.  A spell ends
+ *              at the first counted time outside the event after it; one that is still open is in `run` only, so state and
+ *              durations have the same bits however a run is cut into calls.
+ * A grid point whose threshold is NaN is in no event: its state stays zero and it adds nothing; what to report there is the
+ * caller's.  One block owns the accumulator row (v, lat): every (trajectory, 4 longitudes) of it is a work item of one lane,
+ * which loads its thresholds and state once, keeps the window's times in flight, tests every value once against all E
+ * thresholds and stores the state once; the row's E x 2 x 16 bins are 32-bit words in LDS (integer LDS atomics) that are added
+ * to durations with plain load / add / store.  No global atomics, no second pass; calls on the same state must be ordered on a
+ * stream.  Bit-identical to the _host twin.  16-byte accesses when W, every stride and every pointer (maps and state included)
+ * allow them.
+ * SDY_ERR_ARG, before anything is launched: what sdy_window refuses; NULL args, another struct_size, NULL state / durations /
+ * scalars, state or durations not 8-byte aligned, n_events outside 1..SDY_EVENT_MAX, a non-positive H / W, t0 outside 0..T, a
+ * map event with maps == NULL, map_first[v] < 0 or its planes past n_maps.
+ * SDY_ERR_UNSUPPORTED: n0 > SDY_EVENT_MAX_MEMBERS; n_maps*H*W >= 2^40; (n0*n1 + n1)*W*T >= 2^32 (a row's 32-bit LDS words) or
+ * (n0*n1 + n1)*W > 2^32 - 256 (its 32-bit work items);
+ * nvars*E*4*rows*H*W or nvars*E*2*H*16 >= 2^50.
+ * The _host twin: the same structure with HOST pointers and the same checks. */
+#define SDY_SPELL_BINS 16
+typedef struct sdy_event_spell_args sdy_event_spell_args;
+struct sdy_event_spell_args {
+  size_t struct_size;
+  sdy_window win;
+  int H, W;
+  int t0;
+  int n_events;
+  int n_maps;
+  unsigned char below[SDY_MAX_VARS];
+  unsigned char is_map[SDY_MAX_VARS];
+  int map_first[SDY_MAX_VARS];
+  const float* scalars;
+  const float* maps;
+  unsigned* state;
+  double* durations;
+};
+int sdy_event_spell_accumulate(const sdy_event_spell_args* args, void* stream);
+int sdy_event_spell_accumulate_host(const sdy_event_spell_args* args);
+
 /* The area-weighted Gram matrix of the member errors and the truth anomaly (no counterpart in the reference): what the energy
  * score, the member-to-member and member-to-truth distances of whole fields and the anomaly correlation are read from.  ONE
  * launch for all variables of one window.  window: see sdy_window, plane = HW: n0 = M members (1 for a deterministic run), n1

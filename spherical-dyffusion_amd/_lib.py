@@ -399,6 +399,32 @@ class SdyFssArgs(C.Structure):
     ]
 
 
+SDY_SPELL_BINS = 16
+
+
+class SdyEventSpellArgs(C.Structure):
+    """`sdy_event_spell_args`: the window and the threshold fields of `SdyEventArgs` under the same names
+    (`EventAccumulator._fill` takes it), then the state and the duration histograms.  It carries its own size (`struct_size`,
+    filled in here) and is therefore not part of `ABI_STRUCTS`: the library refuses a structure of another size at every
+    call."""
+    _anonymous_ = ("win",)
+    _fields_ = [
+        ("struct_size", C.c_size_t),
+        ("win", SdyWindow), ("H", C.c_int), ("W", C.c_int),
+        ("t0", C.c_int),
+        ("n_events", C.c_int),
+        ("n_maps", C.c_int),
+        ("below", C.c_ubyte * SDY_MAX_VARS), ("is_map", C.c_ubyte * SDY_MAX_VARS),
+        ("map_first", C.c_int * SDY_MAX_VARS),
+        ("scalars", C.c_void_p), ("maps", C.c_void_p),
+        ("state", C.c_void_p), ("durations", C.c_void_p),
+    ]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_size = C.sizeof(type(self))
+
+
 SDY_GRAM_MAX_MEMBERS = 64
 
 
@@ -576,6 +602,8 @@ SIGNATURES = {
     "sdy_event_table_accumulate_host": (C.c_int, [C.POINTER(SdyEventArgs)]),
     "sdy_event_frequency_accumulate": (C.c_int, [C.POINTER(SdyEventArgs), C.c_void_p]),
     "sdy_event_frequency_accumulate_host": (C.c_int, [C.POINTER(SdyEventArgs)]),
+    "sdy_event_spell_accumulate": (C.c_int, [C.POINTER(SdyEventSpellArgs), C.c_void_p]),
+    "sdy_event_spell_accumulate_host": (C.c_int, [C.POINTER(SdyEventSpellArgs)]),
     "sdy_fss_accumulate": (C.c_int, [C.POINTER(SdyFssArgs), C.c_void_p]),
     "sdy_fss_accumulate_host": (C.c_int, [C.POINTER(SdyFssArgs)]),
     "sdy_fss_encode": (C.c_int, [C.POINTER(SdyFssArgs), C.c_void_p]),

@@ -1,7 +1,7 @@
 // What the field aggregators that read a window in place share (field_stats.hip, member_mean.hip, rank_hist.hip,
-// event_verif.hip, fss.hip, variability.hip, region_series.hip, member_gram.hip; coarsen.hip takes the grid cap): the 16-byte /
-// 4-byte load helpers, the checks and the alignment test of an sdy_window (include/sdy_amd.h) and the grid cap of a launch
-// that covers all variables.
+// event_verif.hip, fss.hip, spells.hip, variability.hip, region_series.hip, member_gram.hip; coarsen.hip takes the grid cap):
+// the 16-byte / 4-byte load helpers, the checks and the alignment test of an sdy_window (include/sdy_amd.h) and the grid cap
+// of a launch that covers all variables.
 #pragma once
 #include "common.h"
 

@@ -7,8 +7,9 @@ For an M-member ensemble the forecast probability of an event takes the values k
 from an integer table of counts per (members in the event, truth in the event or not): the device accumulates the table
 exactly, every score is a few float64 operations on it at read-out (`scores`).
 
-Neighbourhood (fractions-skill) scores of the same events: `sdy_amd.fss`.  Out of scope: quantile helpers that build threshold
-maps from a climatology, events over several variables, plots.
+Neighbourhood (fractions-skill) scores of the same events: `sdy_amd.fss`; how long an event lasts along a trajectory (spell
+durations): `sdy_amd.spells`.  Out of scope: quantile helpers that build threshold maps from a climatology, events over several
+variables, plots.
 """
 from __future__ import annotations
 
@@ -136,9 +137,10 @@ class _EventLayout(WindowLayout):
 
 
 class EventAccumulator(FieldAccumulator):
-    """What `EventVerificationAggregator` and `sdy_amd.FractionsSkillAggregator` share: the events of the variables and their
-    thresholds on the device, the row-constant area weights, the slots, and everything a window is checked for before anything
-    changes.  The threshold fields of `SdyEventArgs` and `SdyFssArgs` have the same names: `_fill` takes either."""
+    """What `EventVerificationAggregator`, `sdy_amd.FractionsSkillAggregator` and `sdy_amd.EventSpellAggregator` share: the
+    events of the variables and their thresholds on the device, the row-constant area weights, the slots, and everything a
+    window is checked for before anything changes.  The threshold fields of `SdyEventArgs`, `SdyFssArgs` and
+    `SdyEventSpellArgs` have the same names: `_fill` takes any of them."""
 
     accepts_sample_weights = True      # (to see, and refuse, a ragged share)
 
@@ -289,7 +291,7 @@ class EventVerificationAggregator(EventAccumulator):
     `get_logs(label)` returns Python floats from the tables pooled over all slots, `<metric>/<event>/<variable>` for the
     metrics of `LOG_METRICS`.  Ranks hold whole initial conditions; ragged shares (flat rows with `sample_weights`) are
     refused.  Quantile helpers for threshold maps, events over several variables and plots are out of scope; neighbourhood
-    (fractions-skill) scores are `sdy_amd.FractionsSkillAggregator`."""
+    (fractions-skill) scores are `sdy_amd.FractionsSkillAggregator`, spell durations `sdy_amd.EventSpellAggregator`."""
 
     def __init__(self, events: Events, area_weights: torch.Tensor, n_timesteps: int, pool_times: bool = False,
                  frequency_maps: bool = False, dist=None, metadata=None, max_bytes: Optional[int] = None):

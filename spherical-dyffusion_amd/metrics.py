@@ -20,6 +20,7 @@ from .member_mean import EnsembleTimeMeanAggregator
 from .rank_hist import RankHistogramAggregator
 from .events import Events, EventVerificationAggregator
 from .fss import FractionsSkillAggregator
+from .spells import EventSpellAggregator
 from .field_scores import FieldScoreAggregator
 from .regions import RegionalMeanAggregator, Regions
 from .spectrum import KineticEnergySpectrumAggregator, PowerSpectrumAggregator
@@ -611,7 +612,14 @@ class InferenceAggregator:
     variable to a (lat, lon) tensor>` turns that variable's pattern correlation into an anomaly correlation): the energy score,
     the member-to-truth and member-to-member distances of whole fields, their ratio, the ensemble-mean RMSE and the
     correlation per lead time, `<metric>/<variable>`, as one more table under `<label>/field_scores/series`; read with
-    `get_field_scores()`.  The default `False` adds nothing: the default key set of the logs does not change."""
+    `get_field_scores()`.  The default `False` adds nothing: the default key set of the logs does not change.
+
+    With events, `event_spells=True` adds `spells` (`sdy_amd.EventSpellAggregator` on the same events): per trajectory and grid
+    point the longest spell, the spells and the times in each event, and per latitude the histogram of spell durations, read
+    with `get_spell_data()`, and `mean_duration_gen`, `mean_duration_target`, `mean_duration_ratio`, `longest_gen`,
+    `longest_target`, `longest_bias`, `onset_rate_gen`, `onset_rate_target`, `time_fraction_gen` and `time_fraction_target` under
+    `<label>/spells/<metric>/<event>/<variable>`.  Without events it raises `ValueError`; its windows must arrive in run order.
+    The default `False` adds nothing."""
 
     accepts_sample_weights = True
 
@@ -625,7 +633,7 @@ class InferenceAggregator:
                  rank_histogram_pool_times: bool = False, time_variability_data: bool = False,
                  regions: Optional[Regions] = None, events: Optional[Events] = None, event_pool_times: bool = False,
                  event_frequency_maps: bool = False, field_scores: bool = False, climatology=None,
-                 event_neighbourhoods: Optional[Sequence[int]] = None, wind_pairs=None):
+                 event_neighbourhoods: Optional[Sequence[int]] = None, wind_pairs=None, event_spells: bool = False):
         if log_video or enable_extended_videos or log_zonal_mean_images:
             raise NotImplementedError("video / zonal-mean image logging is out of scope of sdy_amd (DESIGN.md section 8)")
         if n_timesteps is None:
@@ -678,6 +686,11 @@ class InferenceAggregator:
             self._aggregators["field_scores"] = FieldScoreAggregator(
                 area_weights, n_timesteps=n_timesteps, is_ensemble=self._is_ensemble, climatology=climatology,
                 target="denorm", dist=dist)
+        if event_spells:
+            if events is None:
+                raise ValueError("event_spells needs events=<sdy_amd.Events>")
+            self._aggregators["spells"] = EventSpellAggregator(events, area_weights, n_timesteps=n_timesteps, dist=dist,
+                                                               metadata=metadata)
 
     @torch.no_grad()
     def record_batch(self, loss, target_data, gen_data, target_data_norm, gen_data_norm, i_time_start: int = 0,
@@ -733,6 +746,10 @@ class InferenceAggregator:
     def get_fss_data(self):
         """`FractionsSkillAggregator.get_data()` of the run (`events=..., event_neighbourhoods=...`)."""
         return self._aggregators["fss"].get_data()
+
+    def get_spell_data(self):
+        """`EventSpellAggregator.get_data()` of the run (`events=..., event_spells=True`)."""
+        return self._aggregators["spells"].get_data()
 
     def get_field_scores(self):
         """`FieldScoreAggregator.get_series()` of the run (`field_scores=True`)."""
