@@ -1275,6 +1275,69 @@ struct sdy_event_spell_args {
 int sdy_event_spell_accumulate(const sdy_event_spell_args* args, void* stream);
 int sdy_event_spell_accumulate_host(const sdy_event_spell_args* args);
 
+/* Per-grid-point quantiles along time of gen and target, exactly (no counterpart in the reference): the trajectories of a run
+ * kept as sortable 32-bit keys, and any set of quantiles selected out of them without sorting.  One definition for the kernels
+ * and the _host twins: csrc/quantile.h.  Both structures carry struct_size (sizeof of the structure; a call with another value
+ * is refused with SDY_ERR_ARG) and are not part of the sdy_abi_check list.
+ *   Key of an fp32 value x: -0.0 is taken as +0.0; with u the bits of x the key is u ^ 0x80000000 when the sign bit is clear
+ *     and ~u when it is set, so the unsigned order of keys is the order of values, -inf first and +inf last.  Every NaN has the
+ *     key 0xFFFFFFFF, which is also the "nothing recorded here" fill of a series.  The inverse gives x back bit for bit.
+ *   Trajectories: rows as for the spells above -- the n0*n1 generated ones (member r / n1, sample r % n1), then the n1
+ *     targets: n_traj = n0*n1 + n1, or the n1 targets alone (row = sample) when store_gen == 0.
+ *   series: dev, 32-bit unsigned keys, contiguous (nvars, n_traj, capacity, H*W), 4-byte aligned, filled with 0xFFFFFFFF by the
+ *     caller before the first window.
+ * append: window: see sdy_window, plane = H*W.  Writes the keys of the window times t0 .. T - 1 of every trajectory to
+ *   series[v][trajectory][slot0 + (t - t0)][point]; t0 == T is SDY_OK and launches nothing.  A strided copy with the key
+ *   transform: (variable, trajectory) is one contiguous run of (T - t0)*H*W values on both sides.  16-byte accesses when H*W,
+ *   every stride and every pointer (series included) allow them, 4-byte ones otherwise (same keys).
+ *   SDY_ERR_ARG, before anything is launched: what sdy_window refuses; NULL args, another struct_size, a NULL or misaligned
+ *   series, a non-positive H / W / capacity, t0 outside 0..T, slot0 < 0, slot0 + (T - t0) > capacity, store_gen not 0 or 1.
+ *   SDY_ERR_UNSUPPORTED: nvars*n_traj*capacity*H*W >= 2^50.
+ * select: ONE variable block (n_traj, capacity, plane) of a series.  Group g of n_groups pools the trajectories first + g*step
+ *   + i*stride, i < count, over the time slots 0 .. n_slots - 1: gen pooled over members per sample is first 0, step 1, count
+ *   M, stride n1, n_groups n1; gen per member count 1, n_groups M*n1; the targets first M*n1, count 1, n_groups n1.  The values
+ *   of a group at a point are its keys that are not the NaN key (nanquantile semantics); n is their number, written to
+ *   valid[group][point] (int).  out[group][i][point] (double) is the quantile q[i], NaN when n == 0.  Rank rule, all float64 with
+ *   contraction off: h = q*(n - 1); j = min(floor(h), n - 1); g = h - j; lo the j-th smallest value (0-based), hi the min(j + 1,
+ *   n - 1)-th.  method 1 (lower): lo.  2 (higher): hi when g > 0, else lo.  0 (linear): lo when g == 0 or lo == hi; otherwise,
+ *   with d = hi - lo, hi - d*(1 - g) when g >= 0.5, else lo + d*g.  lower and higher are always exactly an fp32 value of the
+ *   input.  Selection by 2-bit digits, most significant first: a lane owns a grid point (or 4 with 16-byte loads), counts per
+ *   pass the keys that share a rank's decided prefix and have the next digit below 1, 2 and 3, and fixes the digit; one more
+ *   pass settles hi.  At most 4 quantiles per launch (more are taken in two launches).  No sort, no scratch copy, no atomics.
+ *   SDY_ERR_ARG, before anything is launched: NULL args, another struct_size, NULL or misaligned series / out / valid, a
+ *   non-positive plane / n_traj / capacity / n_slots / count / n_groups, n_slots > capacity, a negative first / step / stride, a
+ *   group's trajectory past n_traj, nq outside 1..SDY_MAX_QUANTILES, a q outside [0, 1] or NaN, method outside 0..2.
+ *   SDY_ERR_UNSUPPORTED: plane > 2^30, count*n_slots >= 2^31 (32-bit counts), n_traj*capacity*plane or n_groups*nq*plane >= 2^50.
+ * Both are bit-identical to their _host twins (the same structures with HOST pointers and the same checks). */
+#define SDY_MAX_QUANTILES 8
+typedef struct sdy_time_quantile_append_args sdy_time_quantile_append_args;
+struct sdy_time_quantile_append_args {
+  size_t struct_size;
+  sdy_window win;
+  int H, W;
+  int t0;
+  int slot0;
+  int capacity;
+  int store_gen;
+  unsigned* series;
+};
+int sdy_time_quantile_append(const sdy_time_quantile_append_args* args, void* stream);
+int sdy_time_quantile_append_host(const sdy_time_quantile_append_args* args);
+typedef struct sdy_time_quantile_select_args sdy_time_quantile_select_args;
+struct sdy_time_quantile_select_args {
+  size_t struct_size;
+  const unsigned* series;
+  long plane;
+  int n_traj, capacity, n_slots;
+  int first, step, count, stride, n_groups;
+  int nq, method;
+  double q[SDY_MAX_QUANTILES];
+  double* out;
+  int* valid;
+};
+int sdy_time_quantile_select(const sdy_time_quantile_select_args* args, void* stream);
+int sdy_time_quantile_select_host(const sdy_time_quantile_select_args* args);
+
 /* The area-weighted Gram matrix of the member errors and the truth anomaly (no counterpart in the reference): what the energy
  * score, the member-to-member and member-to-truth distances of whole fields and the anomaly correlation are read from.  ONE
  * launch for all variables of one window.  window: see sdy_window, plane = HW: n0 = M members (1 for a deterministic run), n1

@@ -425,6 +425,42 @@ class SdyEventSpellArgs(C.Structure):
         self.struct_size = C.sizeof(type(self))
 
 
+SDY_MAX_QUANTILES = 8
+
+
+class _SizedStructure(C.Structure):
+    """An argument structure that carries its own size (`struct_size`, filled in here) and is therefore not part of
+    `ABI_STRUCTS`: the library refuses a structure of another size at every call."""
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_size = C.sizeof(type(self))
+
+
+class SdyTimeQuantileAppendArgs(_SizedStructure):
+    """`sdy_time_quantile_append_args`: one window into the series of sortable keys."""
+    _anonymous_ = ("win",)
+    _fields_ = [
+        ("struct_size", C.c_size_t),
+        ("win", SdyWindow), ("H", C.c_int), ("W", C.c_int),
+        ("t0", C.c_int), ("slot0", C.c_int), ("capacity", C.c_int), ("store_gen", C.c_int),
+        ("series", C.c_void_p),
+    ]
+
+
+class SdyTimeQuantileSelectArgs(_SizedStructure):
+    """`sdy_time_quantile_select_args`: quantiles of groups of trajectories of one variable block of a series."""
+    _fields_ = [
+        ("struct_size", C.c_size_t),
+        ("series", C.c_void_p), ("plane", C.c_long),
+        ("n_traj", C.c_int), ("capacity", C.c_int), ("n_slots", C.c_int),
+        ("first", C.c_int), ("step", C.c_int), ("count", C.c_int), ("stride", C.c_int), ("n_groups", C.c_int),
+        ("nq", C.c_int), ("method", C.c_int),
+        ("q", C.c_double * SDY_MAX_QUANTILES),
+        ("out", C.c_void_p), ("valid", C.c_void_p),
+    ]
+
+
 SDY_GRAM_MAX_MEMBERS = 64
 
 
@@ -604,6 +640,10 @@ SIGNATURES = {
     "sdy_event_frequency_accumulate_host": (C.c_int, [C.POINTER(SdyEventArgs)]),
     "sdy_event_spell_accumulate": (C.c_int, [C.POINTER(SdyEventSpellArgs), C.c_void_p]),
     "sdy_event_spell_accumulate_host": (C.c_int, [C.POINTER(SdyEventSpellArgs)]),
+    "sdy_time_quantile_append": (C.c_int, [C.POINTER(SdyTimeQuantileAppendArgs), C.c_void_p]),
+    "sdy_time_quantile_append_host": (C.c_int, [C.POINTER(SdyTimeQuantileAppendArgs)]),
+    "sdy_time_quantile_select": (C.c_int, [C.POINTER(SdyTimeQuantileSelectArgs), C.c_void_p]),
+    "sdy_time_quantile_select_host": (C.c_int, [C.POINTER(SdyTimeQuantileSelectArgs)]),
     "sdy_fss_accumulate": (C.c_int, [C.POINTER(SdyFssArgs), C.c_void_p]),
     "sdy_fss_accumulate_host": (C.c_int, [C.POINTER(SdyFssArgs)]),
     "sdy_fss_encode": (C.c_int, [C.POINTER(SdyFssArgs), C.c_void_p]),

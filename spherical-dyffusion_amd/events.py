@@ -8,8 +8,8 @@ from an integer table of counts per (members in the event, truth in the event or
 exactly, every score is a few float64 operations on it at read-out (`scores`).
 
 Neighbourhood (fractions-skill) scores of the same events: `sdy_amd.fss`; how long an event lasts along a trajectory (spell
-durations): `sdy_amd.spells`.  Out of scope: quantile helpers that build threshold maps from a climatology, events over several
-variables, plots.
+durations): `sdy_amd.spells`; threshold maps from the quantiles along time of a run: `sdy_amd.quantiles`.  Out of scope: events
+over several variables, plots.
 """
 from __future__ import annotations
 
@@ -44,8 +44,8 @@ class Events:
     `add(variable, name, above=c)` or `add(variable, name, below=c)`: a value x is in the event when x > c (x < c), strictly;
     a NaN x never is.  c is a finite Python float, or an `(H, W)` array or tensor (rounded once to fp32) whose NaN points are
     masked for this event.  At most 8 events per variable.  A map whose shape does not match the variable's grid is refused at
-    the first window.  Quantile helpers that build such maps from a climatology, and events over several variables, are out of
-    scope."""
+    the first window.  `sdy_amd.TimeQuantileAggregator.threshold_map` builds such maps from the quantiles of a run; events over
+    several variables are out of scope."""
 
     def __init__(self):
         self._events: Dict[str, List[Event]] = {}
@@ -290,7 +290,7 @@ class EventVerificationAggregator(EventAccumulator):
     `frequency_target` = target hits / counted (both NaN where nothing was counted) and `counted`, each `(lat, lon)`.
     `get_logs(label)` returns Python floats from the tables pooled over all slots, `<metric>/<event>/<variable>` for the
     metrics of `LOG_METRICS`.  Ranks hold whole initial conditions; ragged shares (flat rows with `sample_weights`) are
-    refused.  Quantile helpers for threshold maps, events over several variables and plots are out of scope; neighbourhood
+    refused.  Events over several variables and plots are out of scope; threshold maps: `sdy_amd.quantiles`; neighbourhood
     (fractions-skill) scores are `sdy_amd.FractionsSkillAggregator`, spell durations `sdy_amd.EventSpellAggregator`."""
 
     def __init__(self, events: Events, area_weights: torch.Tensor, n_timesteps: int, pool_times: bool = False,

@@ -21,6 +21,7 @@ from .rank_hist import RankHistogramAggregator
 from .events import Events, EventVerificationAggregator
 from .fss import FractionsSkillAggregator
 from .spells import EventSpellAggregator
+from .quantiles import TimeQuantileAggregator
 from .field_scores import FieldScoreAggregator
 from .regions import RegionalMeanAggregator, Regions
 from .spectrum import KineticEnergySpectrumAggregator, PowerSpectrumAggregator
@@ -619,7 +620,13 @@ class InferenceAggregator:
     with `get_spell_data()`, and `mean_duration_gen`, `mean_duration_target`, `mean_duration_ratio`, `longest_gen`,
     `longest_target`, `longest_bias`, `onset_rate_gen`, `onset_rate_target`, `time_fraction_gen` and `time_fraction_target` under
     `<label>/spells/<metric>/<event>/<variable>`.  Without events it raises `ValueError`; its windows must arrive in run order.
-    The default `False` adds nothing."""
+    The default `False` adds nothing.
+
+    `time_quantiles=<sequence of q in [0, 1]>` adds `time_quantiles` (`sdy_amd.TimeQuantileAggregator` on the denormalised data
+    of `time_quantile_variables`, `None`: every generated variable): per grid point the quantiles along time of gen (members
+    pooled) and of the target, read with `get_time_quantile_data()`, and `quantile_gen`, `quantile_bias`, `quantile_rmse`,
+    `quantile_target` and `defined_fraction` under `<label>/time_quantiles/<metric>/q<q>/<variable>`.  It keeps every counted
+    time of every trajectory (4 bytes each): name the variables.  The default `None` adds nothing."""
 
     accepts_sample_weights = True
 
@@ -633,7 +640,9 @@ class InferenceAggregator:
                  rank_histogram_pool_times: bool = False, time_variability_data: bool = False,
                  regions: Optional[Regions] = None, events: Optional[Events] = None, event_pool_times: bool = False,
                  event_frequency_maps: bool = False, field_scores: bool = False, climatology=None,
-                 event_neighbourhoods: Optional[Sequence[int]] = None, wind_pairs=None, event_spells: bool = False):
+                 event_neighbourhoods: Optional[Sequence[int]] = None, wind_pairs=None, event_spells: bool = False,
+                 time_quantiles: Optional[Sequence[float]] = None,
+                 time_quantile_variables: Optional[Sequence[str]] = None):
         if log_video or enable_extended_videos or log_zonal_mean_images:
             raise NotImplementedError("video / zonal-mean image logging is out of scope of sdy_amd (DESIGN.md section 8)")
         if n_timesteps is None:
@@ -691,6 +700,10 @@ class InferenceAggregator:
                 raise ValueError("event_spells needs events=<sdy_amd.Events>")
             self._aggregators["spells"] = EventSpellAggregator(events, area_weights, n_timesteps=n_timesteps, dist=dist,
                                                                metadata=metadata)
+        if time_quantiles is not None:
+            self._aggregators["time_quantiles"] = TimeQuantileAggregator(
+                time_quantiles, area_weights, n_timesteps=n_timesteps, variables=time_quantile_variables, target="denorm",
+                dist=dist, metadata=metadata)
 
     @torch.no_grad()
     def record_batch(self, loss, target_data, gen_data, target_data_norm, gen_data_norm, i_time_start: int = 0,
@@ -750,6 +763,10 @@ class InferenceAggregator:
     def get_spell_data(self):
         """`EventSpellAggregator.get_data()` of the run (`events=..., event_spells=True`)."""
         return self._aggregators["spells"].get_data()
+
+    def get_time_quantile_data(self):
+        """`TimeQuantileAggregator.get_data()` of the run (`time_quantiles=...`)."""
+        return self._aggregators["time_quantiles"].get_data()
 
     def get_field_scores(self):
         """`FieldScoreAggregator.get_series()` of the run (`field_scores=True`)."""

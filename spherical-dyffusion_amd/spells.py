@@ -6,7 +6,8 @@ of a value, which the persistence of a threshold event is not a function of.  Th
 comparisons only, so every count has the same bits in any layout, batch, run and cut of the run into windows.
 
 Out of scope: per-point duration histograms, spells of the ensemble mean or of several variables, a minimum-duration rule
-(heat waves of at least three days), quantile helpers that build threshold maps, plots, ragged rank shares.
+(heat waves of at least three days), plots, ragged rank shares.  Threshold maps from the quantiles of a run:
+`sdy_amd.quantiles.TimeQuantileAggregator.threshold_map`.
 """
 from __future__ import annotations
 

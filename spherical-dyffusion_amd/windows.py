@@ -3,7 +3,7 @@ the layouts of a window's variables (`WindowLayout`, the Python side of `sdy_win
 variables one launch takes, and `FieldAccumulator`, the float64 accumulators that stay on the device.
 
 This module sits below `metrics`, `histogram`, `data_writer`, `spectrum`, `member_mean`, `rank_hist`, `events`, `fss`, `spells`,
-`variability`, `regions` and `field_scores` and imports none of them.
+`variability`, `regions`, `field_scores` and `quantiles` and imports none of them.
 """
 from __future__ import annotations
 
@@ -184,6 +184,9 @@ class FieldAccumulator:
 
     #: what, besides the variables and the grids, a later window must repeat (the words of the refusal)
     _job_words = "sample count"
+    #: the element type of every buffer of `_acc`, and what the refusal of the memory limit calls them
+    _acc_dtype = torch.float64
+    _acc_words = "float64 accumulators"
 
     def __init__(self, n_timesteps: Optional[int] = None, dist=None, metadata=None, max_bytes: Optional[int] = None):
         if n_timesteps is not None and n_timesteps < 1:
@@ -224,14 +227,14 @@ class FieldAccumulator:
         if self._names is None:
             stats = self._statistics()
             sizes = {stat: [self._elements(stat, j) for j in jobs] for stat in stats}
-            need = 8 * sum(sum(v) for v in sizes.values())
+            need = self._acc_dtype.itemsize * sum(sum(v) for v in sizes.values())
             device = lay[0].gen.device
             limit = self._max_bytes
             if limit is None and on_device:
                 limit = torch.cuda.get_device_properties(device).total_memory // 4
             if limit is not None and need > limit:
-                raise ValueError(f"{type(self).__name__}: {self._size_words(names, jobs)} need {need} bytes of float64 "
-                                 f"accumulators, more than max_bytes = {limit}")
+                raise ValueError(f"{type(self).__name__}: {self._size_words(names, jobs)} need {need} bytes of "
+                                 f"{self._acc_words}, more than max_bytes = {limit}")
         else:
             check_same_job(names, jobs, self._names, self._grids, self._job_words)
             device = next(iter(self._acc.values())).device
@@ -241,14 +244,14 @@ class FieldAccumulator:
             if l.gen.device != device or l.target.device != device:
                 raise ValueError(f"tensors on {l.gen.device} / {l.target.device}, accumulators on {device}")
         if self._names is None:
-            self._acc = {k: torch.full((sum(sizes[k]),), fill, dtype=torch.float64, device=device) for k, fill in stats.items()}
+            self._acc = {k: torch.full((sum(sizes[k]),), fill, dtype=self._acc_dtype, device=device) for k, fill in stats.items()}
             self._offsets = {k: [0, *accumulate(v)][:-1] for k, v in sizes.items()}
             self._names, self._grids = list(names), jobs
         return device
 
     def _at(self, stat: str, i: int) -> int:
         """Device address of variable i's block of a statistic."""
-        return self._acc[stat].data_ptr() + 8 * self._offsets[stat][i]
+        return self._acc[stat].data_ptr() + self._acc_dtype.itemsize * self._offsets[stat][i]
 
     def _view(self, stat: str, i: int, *shape) -> torch.Tensor:
         at = self._offsets[stat][i]
