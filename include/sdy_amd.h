@@ -1338,6 +1338,82 @@ struct sdy_time_quantile_select_args {
 int sdy_time_quantile_select(const sdy_time_quantile_select_args* args, void* stream);
 int sdy_time_quantile_select_host(const sdy_time_quantile_select_args* args);
 
+/* Wavenumber-frequency (Wheeler-Kiladis) power of a field in an equatorial band, gen and target, on the device (no counterpart in
+ * the reference).  Two entry points: append turns the band rows of a window's times into zonal Fourier coefficients of their
+ * parts symmetric and antisymmetric about the equator and stores them in a ring of N time slots; segment_power turns the N
+ * stored times of one segment into power per frequency and adds it to the accumulators.  One definition for the kernels and the
+ * _host twins: csrc/spacetime.h.  Everything after the fp32 loads is float64, never contracted to FMA; every value is one
+ * sequential chain in ascending index order; no libm call: the tables come from the caller.  Both structures carry struct_size
+ * (a call with another value is refused with SDY_ERR_ARG) and are not part of the sdy_abi_check list.
+ *   Trajectories: as for sdy_time_quantile_append: the n0*n1 generated ones (member r / n1, sample r % n1), then the n1 targets:
+ *     n_traj = n0*n1 + n1.
+ *   coef: dev double, contiguous (nvars, n_traj, N, R, 2, K + 1, 2): slot, pair, fold (0 symmetric, 1 antisymmetric),
+ *     wavenumber, (re, im).
+ * append: window: see sdy_window, plane = H*W.  Pair p reads the rows north[p] and south[p] (equal for an equator row).  For a
+ *   window time t in t0 .. t1 - 1 (t0 == t1: SDY_OK, nothing is launched) and longitude j, in float64: s = (x_N + x_S) * 0.5, a =
+ *   (x_N - x_S) * 0.5; for fold y in (s, a) and k = 0 .. K, with i = (k*j) mod W and (cos, sin) = lon_table[2 i], [2 i + 1]:
+ *     re <- re + y*cos, im <- im - y*sin, j ascending from 0.0; stored re / W, im / W
+ *   in slot (n_first + (t - t0)) mod N.  lon_table: dev double, W pairs (cos(2 pi i / W), sin(2 pi i / W)).  A block stages a pair's
+ *   two rows in LDS and a thread owns one (fold, k) chain.  16-byte loads when W, every stride and every pointer allow them, 4-byte
+ *   ones otherwise (same bits).
+ *   SDY_ERR_ARG, before anything is launched: what sdy_window refuses; NULL args, another struct_size, a NULL lon_table or coef
+ *   or one not 8-byte aligned, a non-positive H / W / R, K outside 0..W/2, a row index outside 0..H-1, t0 or t1 outside 0..T, t1 <
+ *   t0, t1 - t0 > N, n_first < 0, N outside 4..SDY_ST_MAX_SEGMENT.
+ *   SDY_ERR_UNSUPPORTED: R > SDY_ST_MAX_PAIRS, W > SDY_ST_MAX_LON (the rows' LDS), n_first >= 2^50, nvars*n_traj*N*R*2*(K+1)*2 >= 2^50.
+ * segment_power: the segment whose first counted time sits in slot first_slot; its time n is slot (first_slot + n) mod N.  Per
+ *   column (variable, trajectory, pair, fold, k), re and im alike, with d_n = n - (N - 1) / 2:
+ *     detrend 0: z~_n = z_n;  1: z~_n = z_n - mean;  2: z~_n = (z_n - mean) - d_n * slope, mean = (sum_n z_n) / N, slope =
+ *     (sum_n d_n z_n) / (sum_n d_n d_n);  y_n = z~_n * taper[n]
+ *     X_f = sum_n y_n (cos u - i sin u), u from time_table[(f n) mod N]: re <- (re + y_re*cos) + y_im*sin, im <- (im + y_im*cos)
+ *     - y_re*sin, n ascending from 0.0;  P_f = (re*re + im*im) / (N * sum_n taper[n]^2)
+ *   acc[v][side][sample][fold][f][k] (dev double, contiguous (nvars, 2, B, 2, N, K + 1), side 0 gen and 1 target) <- acc + S,
+ *   S the chain from 0.0 over (member ascending, pair ascending; the target has one member) of P_f.  taper: dev double, N values;
+ *   time_table: dev double, N pairs (cos(2 pi i / N), sin(2 pi i / N)).  A block stages the N values of a tile of wavenumbers of
+ *   one (variable, trajectory, pair, fold) in LDS and a thread owns frequencies; the P of every column go to ws and a second
+ *   launch adds them in the order above (sdy_sum_chunks, csrc/ordered_sum.h): no atomics, the same bits in any layout, batch and
+ *   run.  A non-finite coefficient makes every frequency of its column, and so of its accumulator cells, NaN.
+ *   SDY_ERR_ARG, before anything is launched: NULL args, another struct_size, a NULL coef / taper / time_table / acc / ws or
+ *   one not 8-byte aligned, a non-positive nvars / M / B / R, K < 0, N outside 4..SDY_ST_MAX_SEGMENT, first_slot outside
+ *   0..N-1, detrend outside 0..2, ws_bytes below sdy_spacetime_workspace_bytes.
+ *   SDY_ERR_UNSUPPORTED: nvars*(M*B + B)*N*R*2*(K+1)*2 >= 2^50 or more than 2^31 - 1 blocks.
+ * Both are bit-identical to their _host twins (the same structures with HOST pointers and the same checks; ws may be NULL). */
+#define SDY_ST_MAX_PAIRS 128
+#define SDY_ST_MAX_LON 4096
+#define SDY_ST_MAX_SEGMENT 1024
+typedef struct sdy_spacetime_append_args sdy_spacetime_append_args;
+struct sdy_spacetime_append_args {
+  size_t struct_size;
+  sdy_window win;
+  int H, W;
+  int R;
+  int north[SDY_ST_MAX_PAIRS], south[SDY_ST_MAX_PAIRS];
+  int K;
+  const double* lon_table;
+  int t0, t1;
+  long n_first;
+  int N;
+  double* coef;
+};
+int sdy_spacetime_append(const sdy_spacetime_append_args* args, void* stream);
+int sdy_spacetime_append_host(const sdy_spacetime_append_args* args);
+typedef struct sdy_spacetime_segment_power_args sdy_spacetime_segment_power_args;
+struct sdy_spacetime_segment_power_args {
+  size_t struct_size;
+  const double* coef;
+  int nvars, M, B;
+  int N, R, K;
+  int first_slot;
+  int detrend;
+  const double* taper;
+  const double* time_table;
+  double* acc;
+  void* ws;
+  size_t ws_bytes;
+};
+int sdy_spacetime_segment_power(const sdy_spacetime_segment_power_args* args, void* stream);
+int sdy_spacetime_segment_power_host(const sdy_spacetime_segment_power_args* args);
+size_t sdy_spacetime_workspace_bytes(int nvars, int M, int B, int N, int R, int K);   /* 0 for an argument out of range */
+
 /* The area-weighted Gram matrix of the member errors and the truth anomaly (no counterpart in the reference): what the energy
  * score, the member-to-member and member-to-truth distances of whole fields and the anomaly correlation are read from.  ONE
  * launch for all variables of one window.  window: see sdy_window, plane = HW: n0 = M members (1 for a deterministic run), n1

@@ -461,6 +461,41 @@ class SdyTimeQuantileSelectArgs(_SizedStructure):
     ]
 
 
+SDY_ST_MAX_PAIRS = 128
+SDY_ST_MAX_LON = 4096
+SDY_ST_MAX_SEGMENT = 1024
+
+
+class SdySpacetimeAppendArgs(_SizedStructure):
+    """`sdy_spacetime_append_args`: the band rows of one window into the ring of zonal Fourier coefficients."""
+    _anonymous_ = ("win",)
+    _fields_ = [
+        ("struct_size", C.c_size_t),
+        ("win", SdyWindow), ("H", C.c_int), ("W", C.c_int),
+        ("R", C.c_int), ("north", C.c_int * SDY_ST_MAX_PAIRS), ("south", C.c_int * SDY_ST_MAX_PAIRS),
+        ("K", C.c_int),
+        ("lon_table", C.c_void_p),
+        ("t0", C.c_int), ("t1", C.c_int),
+        ("n_first", C.c_long),
+        ("N", C.c_int),
+        ("coef", C.c_void_p),
+    ]
+
+
+class SdySpacetimeSegmentPowerArgs(_SizedStructure):
+    """`sdy_spacetime_segment_power_args`: one segment of the ring into the power accumulators."""
+    _fields_ = [
+        ("struct_size", C.c_size_t),
+        ("coef", C.c_void_p),
+        ("nvars", C.c_int), ("M", C.c_int), ("B", C.c_int),
+        ("N", C.c_int), ("R", C.c_int), ("K", C.c_int),
+        ("first_slot", C.c_int), ("detrend", C.c_int),
+        ("taper", C.c_void_p), ("time_table", C.c_void_p),
+        ("acc", C.c_void_p),
+        ("ws", C.c_void_p), ("ws_bytes", C.c_size_t),
+    ]
+
+
 SDY_GRAM_MAX_MEMBERS = 64
 
 
@@ -644,6 +679,11 @@ SIGNATURES = {
     "sdy_time_quantile_append_host": (C.c_int, [C.POINTER(SdyTimeQuantileAppendArgs)]),
     "sdy_time_quantile_select": (C.c_int, [C.POINTER(SdyTimeQuantileSelectArgs), C.c_void_p]),
     "sdy_time_quantile_select_host": (C.c_int, [C.POINTER(SdyTimeQuantileSelectArgs)]),
+    "sdy_spacetime_append": (C.c_int, [C.POINTER(SdySpacetimeAppendArgs), C.c_void_p]),
+    "sdy_spacetime_append_host": (C.c_int, [C.POINTER(SdySpacetimeAppendArgs)]),
+    "sdy_spacetime_segment_power": (C.c_int, [C.POINTER(SdySpacetimeSegmentPowerArgs), C.c_void_p]),
+    "sdy_spacetime_segment_power_host": (C.c_int, [C.POINTER(SdySpacetimeSegmentPowerArgs)]),
+    "sdy_spacetime_workspace_bytes": (C.c_size_t, [C.c_int] * 6),
     "sdy_fss_accumulate": (C.c_int, [C.POINTER(SdyFssArgs), C.c_void_p]),
     "sdy_fss_accumulate_host": (C.c_int, [C.POINTER(SdyFssArgs)]),
     "sdy_fss_encode": (C.c_int, [C.POINTER(SdyFssArgs), C.c_void_p]),

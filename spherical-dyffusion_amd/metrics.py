@@ -22,6 +22,7 @@ from .events import Events, EventVerificationAggregator
 from .fss import FractionsSkillAggregator
 from .spells import EventSpellAggregator
 from .quantiles import TimeQuantileAggregator
+from .spacetime import SpaceTimeSpectra, SpaceTimeSpectrumAggregator
 from .field_scores import FieldScoreAggregator
 from .regions import RegionalMeanAggregator, Regions
 from .spectrum import KineticEnergySpectrumAggregator, PowerSpectrumAggregator
@@ -626,7 +627,14 @@ class InferenceAggregator:
     of `time_quantile_variables`, `None`: every generated variable): per grid point the quantiles along time of gen (members
     pooled) and of the target, read with `get_time_quantile_data()`, and `quantile_gen`, `quantile_bias`, `quantile_rmse`,
     `quantile_target` and `defined_fraction` under `<label>/time_quantiles/<metric>/q<q>/<variable>`.  It keeps every counted
-    time of every trajectory (4 bytes each): name the variables.  The default `None` adds nothing."""
+    time of every trajectory (4 bytes each): name the variables.  The default `None` adds nothing.
+
+    `space_time_spectra=<sdy_amd.SpaceTimeSpectra>` adds `space_time_spectra` (`sdy_amd.SpaceTimeSpectrumAggregator` on the
+    denormalised data of the specification's variables): the wavenumber-frequency power of gen (members pooled) and of the
+    target in an equatorial band, symmetric and antisymmetric about the equator, read with `get_space_time_spectrum_data()`,
+    and `power_gen`, `power_target` and `power_ratio` per band (and `east_west_ratio_gen` / `east_west_ratio_target`) under
+    `<label>/space_time_spectra/...`.  Its windows must arrive in run order.  The default `None` adds nothing: the default key
+    set of the logs does not change."""
 
     accepts_sample_weights = True
 
@@ -640,7 +648,8 @@ class InferenceAggregator:
                  rank_histogram_pool_times: bool = False, time_variability_data: bool = False,
                  regions: Optional[Regions] = None, events: Optional[Events] = None, event_pool_times: bool = False,
                  event_frequency_maps: bool = False, field_scores: bool = False, climatology=None,
-                 event_neighbourhoods: Optional[Sequence[int]] = None, wind_pairs=None, event_spells: bool = False,
+                 event_neighbourhoods: Optional[Sequence[int]] = None, wind_pairs=None,
+                 space_time_spectra: Optional[SpaceTimeSpectra] = None, event_spells: bool = False,
                  time_quantiles: Optional[Sequence[float]] = None,
                  time_quantile_variables: Optional[Sequence[str]] = None):
         if log_video or enable_extended_videos or log_zonal_mean_images:
@@ -704,6 +713,9 @@ class InferenceAggregator:
             self._aggregators["time_quantiles"] = TimeQuantileAggregator(
                 time_quantiles, area_weights, n_timesteps=n_timesteps, variables=time_quantile_variables, target="denorm",
                 dist=dist, metadata=metadata)
+        if space_time_spectra is not None:
+            self._aggregators["space_time_spectra"] = SpaceTimeSpectrumAggregator(space_time_spectra, dist=dist,
+                                                                                  target="denorm", metadata=metadata)
 
     @torch.no_grad()
     def record_batch(self, loss, target_data, gen_data, target_data_norm, gen_data_norm, i_time_start: int = 0,
@@ -767,6 +779,10 @@ class InferenceAggregator:
     def get_time_quantile_data(self):
         """`TimeQuantileAggregator.get_data()` of the run (`time_quantiles=...`)."""
         return self._aggregators["time_quantiles"].get_data()
+
+    def get_space_time_spectrum_data(self):
+        """`SpaceTimeSpectrumAggregator.get_data()` of the run (`space_time_spectra=...`)."""
+        return self._aggregators["space_time_spectra"].get_data()
 
     def get_field_scores(self):
         """`FieldScoreAggregator.get_series()` of the run (`field_scores=True`)."""
