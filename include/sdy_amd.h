@@ -751,6 +751,45 @@ typedef struct sdy_window {
   int n0, n1, T;
 } sdy_window;
 
+/* Where the counted times of a window land in accumulators that keep one slot per lead time: embedded as `slots` in the
+ * structures below that have them.
+ *   t0:         the first counted time of the window: 1 when the window starts a run (its first time is the initial
+ *               condition), else 0; t0 == T counts nothing: SDY_OK, nothing is launched
+ *   pool_times: 0: window time t lands in slot t_start + t of n_slots; non-zero: every time lands in slot 0, n_slots must be 1
+ *               and t_start is not looked at
+ * Every entry point refuses, before anything is launched, with SDY_ERR_ARG: a non-positive n_slots, t0 outside 0..T; not
+ * pooled: t_start < 0, t_start + T > n_slots; pooled: n_slots != 1. */
+typedef struct sdy_lead_slots {
+  int t0;
+  int t_start, n_slots;
+  int pool_times;
+} sdy_lead_slots;
+
+/* The threshold events of the variables of a call: embedded as `thr` in the structures below that test values against them.
+ * Every variable of a call has the same n_events = E events.  Event e of variable v is a threshold c and a direction: a value
+ * x is in the event when x > c, or (bit e of below[v] set) when x < c; both strict, a NaN x is never in it.  A point (sample,
+ * time, lat, lon) is COUNTED for an event when neither its target nor its threshold is NaN; a NaN member is simply not in the
+ * event.  The thresholds are device memory the caller builds once; nothing is copied per call, no address is formed from a
+ * value read from device memory:
+ *   scalars:   dev float, contiguous (nvars, E): the threshold of event e of variable v where bit e of is_map[v] is clear
+ *              (read once per block, not per point; not looked at where the bit is set).  A NaN counts nothing.
+ *   maps:      dev float, contiguous (n_maps, H*W) threshold maps; may be NULL when no is_map bit below E is set.  The map
+ *              events of variable v take the planes map_first[v], map_first[v] + 1, .. in event order; a row of a map is
+ *              loaded once per unit of 4 (or 1) longitudes, not once per member.
+ * Every entry point refuses, before anything is launched, with SDY_ERR_ARG: n_events outside 1..SDY_EVENT_MAX, NULL scalars, a
+ * map event with maps == NULL, map_first[v] < 0 or its planes past n_maps; with SDY_ERR_UNSUPPORTED: n_maps*H*W >= 2^40.  The
+ * _host twins take HOST pointers.  One definition for the kernels and the _host twins: csrc/events.h. */
+#define SDY_EVENT_MAX 8
+typedef struct sdy_event_thresholds {
+  int n_events;
+  int n_maps;
+  unsigned char below[SDY_MAX_VARS];
+  unsigned char is_map[SDY_MAX_VARS];
+  int map_first[SDY_MAX_VARS];
+  const float* scalars;
+  const float* maps;
+} sdy_event_thresholds;
+
 /* Per-grid-point video statistics of the inference aggregators (VideoAggregator with its extended statistics,
  * src/ace_inference/core/aggregator/inference/video.py): one launch adds ONE window of all variables to float64 accumulators
  * that stay on the device.
@@ -1105,20 +1144,9 @@ int sdy_region_series_host(const sdy_region_series_args* args);
 size_t sdy_region_series_workspace_bytes(int nvars, int n_regions, int n1, int T, int HW);   /* 0 for an argument out of range */
 
 /* Threshold events of an ensemble: the counts behind Brier score, reliability diagram, ROC curve and exceedance-frequency maps
- * (no counterpart in the reference).  window: see sdy_window, plane = H*W: n0 = M members, n1 samples.  Every variable of a
- * call has the same n_events = E events.  Event e of variable v is a threshold c and a direction: a value x is in the event
- * when x > c, or (bit e of below[v] set) when x < c; both strict, a NaN x is never in it.  A point (sample, time, lat, lon) is
- * COUNTED for an event when neither its target nor its threshold is NaN; a NaN member is simply not in the event.  Per counted
- * point k = the number of members in the event (0 .. M) and o = 1 if the target is in it, else 0.  Integers only.
- * Thresholds (device memory the caller builds once; nothing is copied per call, no address is formed from a value read from
- * device memory):
- *   scalars:   dev float, contiguous (nvars, E): the threshold of event e of variable v where bit e of is_map[v] is clear
- *              (read once per block, not per point; not looked at where the bit is set).  A NaN counts nothing.
- *   maps:      dev float, contiguous (n_maps, H*W) threshold maps; may be NULL when no is_map bit below E is set.  The map
- *              events of variable v take the planes map_first[v], map_first[v] + 1, .. in event order; a row of a map is
- *              loaded once per unit of 4 (or 1) longitudes, not once per member.
- *   t0, pool_times, t_start, n_slots: as for the rank histograms below: the first time of a run is not counted; t0 == T
- *              is SDY_OK and launches nothing
+ * (no counterpart in the reference).  window: see sdy_window, plane = H*W: n0 = M members, n1 samples.  slots: see
+ * sdy_lead_slots.  thresholds: see sdy_event_thresholds.  Per counted point k = the number of members in the event (0 .. M)
+ * and o = 1 if the target is in it, else 0.  Integers only.
  * sdy_event_table_accumulate:  acc = table, dev double, contiguous (nvars, n_slots, E, H, 2, M + 1), zeroed by the caller:
  *   table[v, slot, e, lat, o, k] += the counted points of the row's W longitudes, n1 samples (and, pooled, T - t0 times) with
  *   that (o, k).  One group of lanes owns the accumulator row (v, slot, lat): its E x 2 x (M + 1) bins are 32-bit words in LDS
@@ -1132,29 +1160,19 @@ size_t sdy_region_series_workspace_bytes(int nvars, int n_regions, int n1, int T
  * No global atomics, no second pass; calls on the same accumulators must be ordered on a stream.  Every count is bit-identical
  * to the _host twin's, in any layout, batch and run.  16-byte loads when W, every stride and every pointer (maps included)
  * allow them.
- * SDY_ERR_ARG, before anything is launched: what sdy_window refuses; NULL args / acc / scalars, acc not 8-byte aligned,
- * n_events outside 1..SDY_EVENT_MAX, a non-positive H / W / n_slots, t0 outside 0..T; not pooled: t_start < 0, t_start + T >
- * n_slots; pooled: n_slots != 1; a map event with maps == NULL, map_first[v] < 0 or its planes past n_maps.
- * SDY_ERR_UNSUPPORTED: n0 > SDY_EVENT_MAX_MEMBERS; n_maps*H*W >= 2^40; table: the points of one row in one call (n1*W, pooled:
- * n1*W*T) >= 2^32 (the row's 32-bit words), n_slots*H >= 2^40, nvars*n_slots*E*H*2*(n0+1) >= 2^50, one row's bins over 64 KB
- * of LDS; frequency: n0*n1*T >= 2^31 (the 32-bit registers of a point), nvars*E*3*H*W >= 2^50.
+ * SDY_ERR_ARG, before anything is launched: what sdy_window, sdy_lead_slots and sdy_event_thresholds refuse; NULL args / acc,
+ * acc not 8-byte aligned, a non-positive H / W.
+ * SDY_ERR_UNSUPPORTED: what sdy_event_thresholds refuses; n0 > SDY_EVENT_MAX_MEMBERS; table: the points of one row in one call
+ * (n1*W, pooled: n1*W*T) >= 2^32 (the row's 32-bit words), n_slots*H >= 2^40, nvars*n_slots*E*H*2*(n0+1) >= 2^50, one row's
+ * bins over 64 KB of LDS; frequency: n0*n1*T >= 2^31 (the 32-bit registers of a point), nvars*E*3*H*W >= 2^50.
  * The _host twins: the same structure with HOST pointers and the same checks; the arithmetic is the header the kernels
  * compile (csrc/events.h). */
-#define SDY_EVENT_MAX 8
 #define SDY_EVENT_MAX_MEMBERS 64
 typedef struct sdy_event_args {
   sdy_window win;
   int H, W;
-  int t0;
-  int t_start, n_slots;
-  int pool_times;
-  int n_events;
-  int n_maps;
-  unsigned char below[SDY_MAX_VARS];
-  unsigned char is_map[SDY_MAX_VARS];
-  int map_first[SDY_MAX_VARS];
-  const float* scalars;
-  const float* maps;
+  sdy_lead_slots slots;
+  sdy_event_thresholds thr;
   double* acc;
 } sdy_event_args;
 int sdy_event_table_accumulate(const sdy_event_args* args, void* stream);
@@ -1163,9 +1181,8 @@ int sdy_event_frequency_accumulate(const sdy_event_args* args, void* stream);
 int sdy_event_frequency_accumulate_host(const sdy_event_args* args);
 
 /* Neighbourhood verification of threshold events: the integer sums behind the fractions skill score (no counterpart in the
- * reference).  window: see sdy_window, plane = H*W: n0 = M members, n1 samples.  Events, "in the event", "counted",
- * thresholds (scalars / maps / below / is_map / map_first / n_maps) and t0 / t_start / n_slots / pool_times: exactly as for
- * sdy_event_args above.  One definition for the kernels and the _host twin: csrc/fss.h (integers and comparisons only).
+ * reference).  window: see sdy_window, plane = H*W: n0 = M members, n1 samples.  slots: see sdy_lead_slots.  thresholds: see
+ * sdy_event_thresholds.  One definition for the kernels and the _host twin: csrc/fss.h (integers and comparisons only).
  * Per (variable v, sample s, time t, event e) and grid point q: c(q) = 1 when q is counted, else 0; k(q) = the members in the
  * event, o(q) = 1 when the target is in it; k = o = 0 where c = 0.  The neighbourhood of radius r >= 0 of a centre (lat, lon):
  * the points (lat', (lon + d) mod W) with |lat' - lat| <= r, 0 <= lat' < H and |d| <= r -- longitude wraps, latitude is clipped
@@ -1187,11 +1204,11 @@ int sdy_event_frequency_accumulate_host(const sdy_event_args* args);
  * ordered on a stream.  sdy_fss_accumulate is the two in order.  Every sum is an integer: the same bits in any layout, batch,
  * band size, grouping of variables and run, and equal to the _host twin's.  One call's sums are exact (checked below); across
  * calls the float64 accumulators are exact below 2^53 and round above it: not checked.
- * SDY_ERR_ARG, before anything is launched: what sdy_window refuses; NULL args / acc / scalars / ws, acc or ws not 8-byte
- * aligned, n_events outside 1..SDY_EVENT_MAX, a non-positive H / W / n_slots, t0 outside 0..T; not pooled: t_start < 0,
- * t_start + T > n_slots; pooled: n_slots != 1; a map event with maps == NULL, map_first[v] < 0 or its planes past n_maps;
+ * SDY_ERR_ARG, before anything is launched: what sdy_window, sdy_lead_slots and sdy_event_thresholds refuse; NULL args / acc /
+ * ws, acc or ws not 8-byte aligned, a non-positive H / W;
  * n_radii outside 1..SDY_FSS_MAX_RADII, a negative radius, radii not strictly ascending, 2r + 1 > W; ws_bytes too small.
- * SDY_ERR_UNSUPPORTED: n0 > SDY_EVENT_MAX_MEMBERS; n0 (2 r_max + 1)^2 > 65535 (K fits 16 bits, K^2 32); n_maps*H*W >= 2^40; the
+ * SDY_ERR_UNSUPPORTED: n0 > SDY_EVENT_MAX_MEMBERS; n0 (2 r_max + 1)^2 > 65535 (K fits 16 bits, K^2 32); what
+ * sdy_event_thresholds refuses; the
  * largest row sum of one call, n1 W (pooled: x (T - t0)) (n0 n_max)^2 with n_max = (2 r_max + 1) min(H, 2 r_max + 1), >= 2^53;
  * n_slots*H >= 2^40, nvars*n_slots*E*n_radii*H*6 or the codes of the workspace >= 2^50; 2 r_max + 1 rows of W 32-bit sums and
  * one of W + 2 r_max over 64 KB of LDS; more than 2^24 - 1 (counted time, band of latitudes) blocks per variable and event.
@@ -1200,16 +1217,8 @@ int sdy_event_frequency_accumulate_host(const sdy_event_args* args);
 typedef struct sdy_fss_args {
   sdy_window win;
   int H, W;
-  int t0;
-  int t_start, n_slots;
-  int pool_times;
-  int n_events;
-  int n_maps;
-  unsigned char below[SDY_MAX_VARS];
-  unsigned char is_map[SDY_MAX_VARS];
-  int map_first[SDY_MAX_VARS];
-  const float* scalars;
-  const float* maps;
+  sdy_lead_slots slots;
+  sdy_event_thresholds thr;
   int n_radii;
   int radii[SDY_FSS_MAX_RADII];
   double* acc;
@@ -1223,14 +1232,14 @@ int sdy_fss_sum(const sdy_fss_args* args, void* stream);      /* the second: ws 
 size_t sdy_fss_workspace_bytes(int nvars, int n_events, int n1, int T, int H, int W);   /* 0 for an argument out of range */
 
 /* Spell durations of threshold events: how long an event lasts along a trajectory -- consecutive dry days, warm spells (no
- * counterpart in the reference).  window: see sdy_window, plane = H*W: n0 = M members, n1 samples.  Events, "in the event" and
- * the thresholds (scalars / maps / below / is_map / map_first / n_maps) are those of sdy_event_args above; the fields carry the
- * same names.  One definition for the kernel and the _host twin: csrc/spells.h (integers and comparisons only).
+ * counterpart in the reference).  window: see sdy_window, plane = H*W: n0 = M members, n1 samples.  thresholds: see
+ * sdy_event_thresholds.  One definition for the kernel and the _host twin: csrc/spells.h (integers and comparisons only).
  *   struct_size: sizeof of this structure.  It stands in for the sdy_abi_check handshake, whose list this structure is not
  *              part of: a call with another value is refused (SDY_ERR_ARG).
  * A trajectory is one member of one sample, or one sample's target, at one grid point: row r of rows = n0*n1 + n1, the
  * generated ones first (member r / n1, sample r % n1), then the targets.  Its counted times are the window times t0 .. T - 1
- * of every call, in call order; t0 == T is SDY_OK and launches nothing.  A value is in event e as for sdy_event_args; a NaN
+ * of every call, in call order; t0 == T is SDY_OK and launches nothing.  A value is in event e as sdy_event_thresholds says; a
+ * NaN
  * value never is, for the target too, so it ends a spell.  A spell is a maximal run of consecutive counted times in the event.
  *   state:     dev, 32-bit unsigned words, contiguous (nvars, E, 4, rows, H*W), 8-byte aligned, zeroed by the caller before
  *              the first window and carried from call to call: word 0 = run, the length of the spell open after the last
@@ -1248,10 +1257,10 @@ size_t sdy_fss_workspace_bytes(int nvars, int n_events, int n1, int T, int H, in
  * to durations with plain load / add / store.  No global atomics, no second pass; calls on the same state must be ordered on a
  * stream.  Bit-identical to the _host twin.  16-byte accesses when W, every stride and every pointer (maps and state included)
  * allow them.
- * SDY_ERR_ARG, before anything is launched: what sdy_window refuses; NULL args, another struct_size, NULL state / durations /
- * scalars, state or durations not 8-byte aligned, n_events outside 1..SDY_EVENT_MAX, a non-positive H / W, t0 outside 0..T, a
- * map event with maps == NULL, map_first[v] < 0 or its planes past n_maps.
- * SDY_ERR_UNSUPPORTED: n0 > SDY_EVENT_MAX_MEMBERS; n_maps*H*W >= 2^40; (n0*n1 + n1)*W*T >= 2^32 (a row's 32-bit LDS words) or
+ * SDY_ERR_ARG, before anything is launched: what sdy_window and sdy_event_thresholds refuse; NULL args, another struct_size,
+ * NULL state / durations, state or durations not 8-byte aligned, a non-positive H / W, t0 outside 0..T.
+ * SDY_ERR_UNSUPPORTED: what sdy_event_thresholds refuses; n0 > SDY_EVENT_MAX_MEMBERS; (n0*n1 + n1)*W*T >= 2^32 (a row's 32-bit
+ * LDS words) or
  * (n0*n1 + n1)*W > 2^32 - 256 (its 32-bit work items);
  * nvars*E*4*rows*H*W or nvars*E*2*H*16 >= 2^50.
  * The _host twin: the same structure with HOST pointers and the same checks. */
@@ -1262,13 +1271,7 @@ struct sdy_event_spell_args {
   sdy_window win;
   int H, W;
   int t0;
-  int n_events;
-  int n_maps;
-  unsigned char below[SDY_MAX_VARS];
-  unsigned char is_map[SDY_MAX_VARS];
-  int map_first[SDY_MAX_VARS];
-  const float* scalars;
-  const float* maps;
+  sdy_event_thresholds thr;
   unsigned* state;
   double* durations;
 };
@@ -1462,10 +1465,7 @@ size_t sdy_member_gram_workspace_bytes(int nvars, int n0, int n1, int T, int HW)
  * For the target y and the members g_0 .. g_{M-1} of a grid point (variable v, sample s, window time t, lat, lon):
  *   rank = #{m : g_m < y}, 0 .. M.  A point whose target is NaN is counted nowhere; a NaN member is not below (the comparison
  *   is false).  The point is a tie when y is not NaN and some g_m == y; ties do not change the rank and are counted apart.
- *   t0:         the first counted time of the window: 1 when the window starts a run (its first time is the initial
- *               condition), else 0; t0 == T counts nothing: SDY_OK, nothing is launched
- *   pool_times: 0: window time t lands in slot t_start + t of n_slots; non-zero: every time lands in slot 0, n_slots must be 1
- *               and t_start is not looked at
+ *   slots:      see sdy_lead_slots
  *   counts:     dev double, contiguous (nvars, n_slots, H, M + 1), zeroed by the caller before the first call:
  *                 counts[v, slot, lat, rank] += the counted points of the row's W longitudes, n1 samples (and, pooled, T - t0
  *                 times) with that rank
@@ -1475,8 +1475,7 @@ size_t sdy_member_gram_workspace_bytes(int nvars, int n0, int n1, int T, int HW)
  * accumulators must be ordered on a stream.  Integers below 2^53 add exactly in any order: every count is bit-identical to
  * the _host twin's, in any layout, batch and run.  16-byte loads when W, every stride and every pointer allow them.
  * SDY_ERR_ARG, before anything is launched: NULL args / gen[v] / target[v] / counts / ties, an accumulator not 8-byte aligned,
- * nvars outside 1..SDY_MAX_VARS, a non-positive n0 / n1 / T / H / W / n_slots, a negative stride, t0 outside 0..T; not pooled:
- * t_start < 0, t_start + T > n_slots; pooled: n_slots != 1.
+ * nvars outside 1..SDY_MAX_VARS, a non-positive n0 / n1 / T / H / W, a negative stride; what sdy_lead_slots refuses.
  * SDY_ERR_UNSUPPORTED: n0 > SDY_RANK_HIST_MAX_MEMBERS, T*H*W > 2^30, n0*n1 >= 2^31, the points of one row in one call (n1*W,
  * pooled: n1*W*T) >= 2^32 (the row's 32-bit words), n_slots*H >= 2^40, nvars*n_slots*H*(n0+1) >= 2^50 (flat accumulator
  * indices are 64-bit).
@@ -1486,9 +1485,7 @@ size_t sdy_member_gram_workspace_bytes(int nvars, int n0, int n1, int T, int HW)
 typedef struct sdy_rank_hist_args {
   sdy_window win;
   int H, W;
-  int t0;
-  int t_start, n_slots;
-  int pool_times;
+  sdy_lead_slots slots;
   double *counts, *ties;
 } sdy_rank_hist_args;
 int sdy_rank_hist_accumulate(const sdy_rank_hist_args* args, void* stream);

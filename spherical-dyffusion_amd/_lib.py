@@ -231,6 +231,12 @@ class SdyWindow(C.Structure):
     ]
 
 
+class SdyLeadSlots(C.Structure):
+    """sdy_lead_slots: embedded as `slots` in the structures below that keep one accumulator slot per lead time (filled by
+    `windows.fill_slots`); its fields also read and write as the embedding structure's own."""
+    _fields_ = [("t0", C.c_int), ("t_start", C.c_int), ("n_slots", C.c_int), ("pool_times", C.c_int)]
+
+
 class SdyVideoArgs(C.Structure):
     _anonymous_ = ("win",)
     _fields_ = [
@@ -285,9 +291,17 @@ class SdySpectrumArgs(C.Structure):
     ]
 
 
-class SdyVectorSpectrumArgs(C.Structure):
-    """`sdy_vector_spectrum_args`.  It carries its own size (`struct_size`, filled in here) and is therefore not part of
+class _SizedStructure(C.Structure):
+    """An argument structure that carries its own size (`struct_size`, filled in here) and is therefore not part of
     `ABI_STRUCTS`: the library refuses a structure of another size at every call."""
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_size = C.sizeof(type(self))
+
+
+class SdyVectorSpectrumArgs(_SizedStructure):
+    """`sdy_vector_spectrum_args`."""
     _fields_ = [
         ("struct_size", C.c_size_t),
         ("gen_d", C.c_void_p), ("gen_m", C.c_void_p), ("target_d", C.c_void_p), ("target_m", C.c_void_p),
@@ -302,10 +316,6 @@ class SdyVectorSpectrumArgs(C.Structure):
         ("gen_rot", C.c_void_p), ("gen_div", C.c_void_p), ("target_rot", C.c_void_p), ("target_div", C.c_void_p),
         ("err_rot", C.c_void_p), ("err_div", C.c_void_p),
     ]
-
-    def __init__(self, *args, **kw):
-        super().__init__(*args, **kw)
-        self.struct_size = C.sizeof(type(self))
 
 
 class SdyVariabilityArgs(C.Structure):
@@ -362,18 +372,24 @@ SDY_EVENT_MAX = 8
 SDY_EVENT_MAX_MEMBERS = 64
 
 
-class SdyEventArgs(C.Structure):
-    _anonymous_ = ("win",)
+class SdyEventThresholds(C.Structure):
+    """sdy_event_thresholds: embedded as `thr` in the structures below that test values against the events of the variables
+    (filled by `EventAccumulator._fill`); its fields also read and write as the embedding structure's own."""
     _fields_ = [
-        ("win", SdyWindow), ("H", C.c_int), ("W", C.c_int),
-        ("t0", C.c_int),
-        ("t_start", C.c_int), ("n_slots", C.c_int),
-        ("pool_times", C.c_int),
         ("n_events", C.c_int),
         ("n_maps", C.c_int),
         ("below", C.c_ubyte * SDY_MAX_VARS), ("is_map", C.c_ubyte * SDY_MAX_VARS),
         ("map_first", C.c_int * SDY_MAX_VARS),
         ("scalars", C.c_void_p), ("maps", C.c_void_p),
+    ]
+
+
+class SdyEventArgs(C.Structure):
+    _anonymous_ = ("win", "slots", "thr")
+    _fields_ = [
+        ("win", SdyWindow), ("H", C.c_int), ("W", C.c_int),
+        ("slots", SdyLeadSlots),
+        ("thr", SdyEventThresholds),
         ("acc", C.c_void_p),
     ]
 
@@ -382,17 +398,11 @@ SDY_FSS_MAX_RADII = 4
 
 
 class SdyFssArgs(C.Structure):
-    _anonymous_ = ("win",)
+    _anonymous_ = ("win", "slots", "thr")
     _fields_ = [
         ("win", SdyWindow), ("H", C.c_int), ("W", C.c_int),
-        ("t0", C.c_int),
-        ("t_start", C.c_int), ("n_slots", C.c_int),
-        ("pool_times", C.c_int),
-        ("n_events", C.c_int),
-        ("n_maps", C.c_int),
-        ("below", C.c_ubyte * SDY_MAX_VARS), ("is_map", C.c_ubyte * SDY_MAX_VARS),
-        ("map_first", C.c_int * SDY_MAX_VARS),
-        ("scalars", C.c_void_p), ("maps", C.c_void_p),
+        ("slots", SdyLeadSlots),
+        ("thr", SdyEventThresholds),
         ("n_radii", C.c_int), ("radii", C.c_int * SDY_FSS_MAX_RADII),
         ("acc", C.c_void_p),
         ("ws", C.c_void_p), ("ws_bytes", C.c_size_t),
@@ -402,39 +412,20 @@ class SdyFssArgs(C.Structure):
 SDY_SPELL_BINS = 16
 
 
-class SdyEventSpellArgs(C.Structure):
-    """`sdy_event_spell_args`: the window and the threshold fields of `SdyEventArgs` under the same names
-    (`EventAccumulator._fill` takes it), then the state and the duration histograms.  It carries its own size (`struct_size`,
-    filled in here) and is therefore not part of `ABI_STRUCTS`: the library refuses a structure of another size at every
-    call."""
-    _anonymous_ = ("win",)
+class SdyEventSpellArgs(_SizedStructure):
+    """`sdy_event_spell_args`: the window and the thresholds of `SdyEventArgs`, no slots, then the state and the duration
+    histograms."""
+    _anonymous_ = ("win", "thr")
     _fields_ = [
         ("struct_size", C.c_size_t),
         ("win", SdyWindow), ("H", C.c_int), ("W", C.c_int),
         ("t0", C.c_int),
-        ("n_events", C.c_int),
-        ("n_maps", C.c_int),
-        ("below", C.c_ubyte * SDY_MAX_VARS), ("is_map", C.c_ubyte * SDY_MAX_VARS),
-        ("map_first", C.c_int * SDY_MAX_VARS),
-        ("scalars", C.c_void_p), ("maps", C.c_void_p),
+        ("thr", SdyEventThresholds),
         ("state", C.c_void_p), ("durations", C.c_void_p),
     ]
 
-    def __init__(self, *args, **kw):
-        super().__init__(*args, **kw)
-        self.struct_size = C.sizeof(type(self))
-
 
 SDY_MAX_QUANTILES = 8
-
-
-class _SizedStructure(C.Structure):
-    """An argument structure that carries its own size (`struct_size`, filled in here) and is therefore not part of
-    `ABI_STRUCTS`: the library refuses a structure of another size at every call."""
-
-    def __init__(self, *args, **kw):
-        super().__init__(*args, **kw)
-        self.struct_size = C.sizeof(type(self))
 
 
 class SdyTimeQuantileAppendArgs(_SizedStructure):
@@ -514,12 +505,10 @@ SDY_RANK_HIST_MAX_MEMBERS = 64
 
 
 class SdyRankHistArgs(C.Structure):
-    _anonymous_ = ("win",)
+    _anonymous_ = ("win", "slots")
     _fields_ = [
         ("win", SdyWindow), ("H", C.c_int), ("W", C.c_int),
-        ("t0", C.c_int),
-        ("t_start", C.c_int), ("n_slots", C.c_int),
-        ("pool_times", C.c_int),
+        ("slots", SdyLeadSlots),
         ("counts", C.c_void_p), ("ties", C.c_void_p),
     ]
 

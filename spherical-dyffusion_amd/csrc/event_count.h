@@ -1,8 +1,7 @@
-// What the kernels that test an ensemble's values against the thresholds of its events share (event_verif.hip, fss.hip): the
-// per-thread registers of a variable's events, the signed thresholds of a unit of grid points and the count of the members in
-// each event.  `Args` is an argument structure with the threshold fields of sdy_event_args (scalars, maps, map_first).  The
-// event count is a template argument: every array here is indexed at compile time only and stays in registers.  The
-// arithmetic of a point is events.h.
+// What the kernels that test an ensemble's values against the thresholds of its events share (event_verif.hip, fss.hip,
+// spells.hip): the per-thread registers of a variable's events, the signed thresholds of a unit of grid points, the count of
+// the members in each event and the dispatch over event count and load width.  The event count is a template argument: every
+// array here is indexed at compile time only and stays in registers.  The arithmetic of a point is events.h.
 #pragma once
 #include "common.h"
 #include "events.h"
@@ -12,19 +11,6 @@
 // of a unit take the registers that the second half of 8 loads would
 template <int EC>
 constexpr int kInFlight = EC > 4 ? 4 : 8;
-
-// (wave-uniform 64-bit base) + (32-bit byte offset per lane), see rank_hist.hip
-typedef float __attribute__((address_space(1))) gfloat;
-template <int W4>
-__device__ __forceinline__ Vec<W4> ld_u(const float* ubase, unsigned off_b);
-template <>
-__device__ __forceinline__ f32x4 ld_u<4>(const float* ubase, unsigned off_b) { return sdy_ld16s(ubase, off_b); }
-template <>
-__device__ __forceinline__ float ld_u<1>(const float* ubase, unsigned off_b) {
-  sdy_gcptr_t b = (sdy_gcptr_t)ubase;
-  asm volatile("" : "+s"(b), "+v"(off_b));
-  return *reinterpret_cast<const gfloat*>(b + off_b);
-}
 
 // What a thread keeps per event of variable v, set once before its first unit: the sign that folds the direction into the
 // operands (sdy_ev_signed, events.h), the signed scalar threshold, and the plane of a map threshold.  All three are
@@ -36,8 +22,8 @@ struct EventRegs {
   float scalar[EC];
   int plane[EC];
 };
-template <int EC, class Args>
-__device__ __forceinline__ void event_regs(const Args& a, int v, unsigned is_map, unsigned below, EventRegs<EC>& r) {
+template <int EC>
+__device__ __forceinline__ void event_regs(const sdy_event_thresholds& a, int v, unsigned is_map, unsigned below, EventRegs<EC>& r) {
 #pragma unroll
   for (int e = 0; e < EC; ++e) {
     r.sign[e] = sdy_ev_sign((below >> e) & 1u);
@@ -49,8 +35,8 @@ __device__ __forceinline__ void event_regs(const Args& a, int v, unsigned is_map
 
 // The signed thresholds of the W4 points from point `at` of a plane on, all EC events: a map event loads its row once per unit,
 // a scalar event costs no load.  is_map is wave-uniform: the branch does not diverge.
-template <int W4, int EC, class Args>
-__device__ __forceinline__ void thresholds(const Args& a, unsigned is_map, const EventRegs<EC>& r, long plane, unsigned at,
+template <int W4, int EC>
+__device__ __forceinline__ void thresholds(const sdy_event_thresholds& a, unsigned is_map, const EventRegs<EC>& r, long plane, unsigned at,
                                            float (&c)[EC][W4]) {
   // (through a vector register and back: the EC bit tests are made here, once per unit, as scalar compares; hoisted out of
   // the kernel's loops they would be kept as EC lane masks in pairs of scalar registers)
@@ -108,5 +94,21 @@ __device__ __forceinline__ void count_members(const float* g, long gs0, int M, u
 #pragma unroll
           for (int q = 0; q < W4; ++q) count_if_above(k[e][q], sdy_ev_signed(comp(x[j], q), r.sign[e]), c[e][q]);
       }
+  }
+}
+
+// Launch<4 or 1, E>::go(args...) for the run-time load width and event count E = 1 .. SDY_EVENT_MAX (the entry points' checks)
+template <template <int, int> class Launch, class... Args>
+void dispatch(bool vec, int E, Args... args) {
+  switch (E) {
+#define SDY_EV_CASE(N)                \
+  case N:                             \
+    if (vec)                          \
+      Launch<4, N>::go(args...);      \
+    else                              \
+      Launch<1, N>::go(args...);      \
+    break;
+    SDY_EV_CASE(1) SDY_EV_CASE(2) SDY_EV_CASE(3) SDY_EV_CASE(4) SDY_EV_CASE(5) SDY_EV_CASE(6) SDY_EV_CASE(7) SDY_EV_CASE(8)
+#undef SDY_EV_CASE
   }
 }

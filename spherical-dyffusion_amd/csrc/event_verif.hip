@@ -12,6 +12,7 @@
 // and stay in registers (no private segment).  The arithmetic of a point is events.h.
 #include "common.h"
 #include "event_count.h"
+#include "event_thresholds.h"
 #include "events.h"
 #include "window.h"
 
@@ -21,29 +22,7 @@ constexpr int kThreads = 256;
 constexpr int kBlocksPerLaunch = 4096;  // over all variables; a variable with more rows / points strides over them
 constexpr int kMinBlocksPerVar = 32;
 constexpr int kMaxMembers = SDY_EVENT_MAX_MEMBERS;
-constexpr int kMaxEvents = SDY_EVENT_MAX;
-constexpr int kMinGroup = 4;            // lanes of the narrowest group
 constexpr int kLdsBytes = 64 * 1024;    // of a block's rows
-
-// lanes per accumulator row, the rule of rank_hist.hip: the narrowest group that covers a row of at most 16 units in one pass,
-// else the group of 16, 32 or 64 lanes that leaves the fewest lane slots idle (the wider one of equals)
-int lane_group(int units) {
-  if (units <= 16) {
-    int G = kMinGroup;
-    while (G < units) G <<= 1;
-    return G;
-  }
-  int best = 16;
-  long best_slots = 16L * ((units + 15) / 16);
-  for (int G = 32; G <= 64; G <<= 1) {
-    const long slots = (long)G * ((units + G - 1) / G);
-    if (slots <= best_slots) {
-      best = G;
-      best_slots = slots;
-    }
-  }
-  return best;
-}
 
 long row_words(int E, int M) { return (long)E * 2 * (M + 1); }
 long row_bytes_lds(int E, int M) { return row_words(E, M) * 4; }
@@ -61,12 +40,12 @@ __global__ __launch_bounds__(kThreads) void event_table_kernel(const sdy_event_a
   const int v = blockIdx.y;
   const int lig = threadIdx.x & (G - 1), group = threadIdx.x / G, rows_per_block = blockDim.x / G;
   const int units = a.W / W4, M = a.win.n0, n1 = a.win.n1, T = a.win.T, H = a.H, bins = M + 1, words = EC * 2 * bins;
-  const bool pool = a.pool_times != 0;
+  const bool pool = a.slots.pool_times != 0;
   const unsigned plane = (unsigned)H * (unsigned)a.W;
-  const unsigned below = a.below[v], is_map = a.is_map[v];
+  const unsigned below = a.thr.below[v], is_map = a.thr.is_map[v];
   const long gs0 = a.win.gs0, gs1 = a.win.gs1, ts1 = a.win.ts1;
   EventRegs<EC> r;
-  event_regs<EC>(a, v, is_map, below, r);
+  event_regs<EC>(a.thr, v, is_map, below, r);
   unsigned* mine = s_rows + group * words;      // [e][o][k]
   for (int w = lig; w < words; w += G) mine[w] = 0u;
   for (unsigned base = blockIdx.x * rows_per_block; base < n_rows; base += gridDim.x * rows_per_block) {
@@ -76,11 +55,11 @@ __global__ __launch_bounds__(kThreads) void event_table_kernel(const sdy_event_a
     const bool active = row < n_rows;
     const unsigned tt = row / (unsigned)H, lat = row - tt * (unsigned)H;
     if (active) {
-      const int t_begin = a.t0 + (pool ? 0 : (int)tt), t_end = pool ? T : t_begin + 1;
+      const int t_begin = a.slots.t0 + (pool ? 0 : (int)tt), t_end = pool ? T : t_begin + 1;
       for (int u = lig; u < units; u += G) {
         const unsigned in_plane = lat * (unsigned)a.W + (unsigned)(u * W4);             // < plane
         float c[EC][W4];
-        thresholds<W4, EC>(a, is_map, r, plane, in_plane, c);
+        thresholds<W4, EC>(a.thr, is_map, r, plane, in_plane, c);
         int valid[W4];                                                     // the points of the unit whose target is not NaN
 #pragma unroll
         for (int q = 0; q < W4; ++q) valid[q] = 0;
@@ -123,12 +102,14 @@ __global__ __launch_bounds__(kThreads) void event_table_kernel(const sdy_event_a
     }
     __syncthreads();
     if (active) {
-      const long slot = pool ? 0 : (long)a.t_start + a.t0 + (long)tt;   // < n_slots
+      // sdy_lead_slot(a.slots, t0 + tt) < n_slots, spelled out: through the helper the compiler allocates the kernels of 6 to 8
+      // events two more scalar registers (and one more vector register with 7)
+      const long slot = pool ? 0 : (long)a.slots.t_start + a.slots.t0 + (long)tt;
       for (int w = lig; w < words; w += G) {
         const unsigned n = mine[w];
         mine[w] = 0u;
         const int e = w / (2 * bins), ok = w - e * (2 * bins);          // ok = o * (M + 1) + k
-        a.acc[sdy_ev_table_at(v, a.n_slots, slot, EC, e, H, lat, M, 0, ok)] += (double)n;
+        a.acc[sdy_ev_table_at(v, a.slots.n_slots, slot, EC, e, H, lat, M, 0, ok)] += (double)n;
       }
     }
   }
@@ -142,14 +123,14 @@ __global__ __launch_bounds__(kThreads) void event_frequency_kernel(const sdy_eve
   const int v = blockIdx.y;
   const int M = a.win.n0, n1 = a.win.n1, T = a.win.T;
   const unsigned plane = (unsigned)a.H * (unsigned)a.W;
-  const unsigned below = a.below[v], is_map = a.is_map[v];
+  const unsigned below = a.thr.below[v], is_map = a.thr.is_map[v];
   const long gs0 = a.win.gs0, gs1 = a.win.gs1, ts1 = a.win.ts1;
   EventRegs<EC> r;
-  event_regs<EC>(a, v, is_map, below, r);
+  event_regs<EC>(a.thr, v, is_map, below, r);
   for (unsigned idx = blockIdx.x * kThreads + threadIdx.x; idx < n_items; idx += gridDim.x * kThreads) {
     const unsigned p = idx * W4;
     float c[EC][W4];
-    thresholds<W4, EC>(a, is_map, r, plane, p, c);
+    thresholds<W4, EC>(a.thr, is_map, r, plane, p, c);
     int hits[EC][W4], obs[EC][W4], valid[W4];
 #pragma unroll
     for (int q = 0; q < W4; ++q) valid[q] = 0;
@@ -160,7 +141,7 @@ __global__ __launch_bounds__(kThreads) void event_frequency_kernel(const sdy_eve
     for (int s = 0; s < n1; ++s) {
       const float* tg = a.win.target[v] + (long)s * ts1;
       const float* g = a.win.gen[v] + (long)s * gs1;
-      for (int t = a.t0; t < T; ++t) {
+      for (int t = a.slots.t0; t < T; ++t) {
         const unsigned off_b = ((unsigned)t * plane + p) * 4u;
         const Vec<W4> y = ld_u<W4>(tg, off_b);
         int k[EC][W4];
@@ -204,32 +185,19 @@ int check(const sdy_event_args* a, bool table) {
   if (!a) return SDY_ERR_ARG;
   if (a->H < 1 || a->W < 1) return SDY_ERR_ARG;
   SDY_TRY(sdy_window_check(&a->win, (long)a->H * a->W));
-  if (!a->acc || !a->scalars || ((uintptr_t)a->acc & 7) || ((uintptr_t)a->scalars & 3)) return SDY_ERR_ARG;
-  if (a->n_events < 1 || a->n_events > kMaxEvents) return SDY_ERR_ARG;
-  if (a->n_slots < 1 || a->t0 < 0 || a->t0 > a->win.T) return SDY_ERR_ARG;
-  if (a->pool_times) {
-    if (a->n_slots != 1) return SDY_ERR_ARG;
-  } else if (a->t_start < 0 || (long)a->t_start + (long)a->win.T > (long)a->n_slots) {
-    // window times t_start .. t_start + T - 1 must all exist (in 64 bits: no wrap)
-    return SDY_ERR_ARG;
-  }
+  if (!a->acc || ((uintptr_t)a->acc & 7)) return SDY_ERR_ARG;
+  SDY_TRY(sdy_lead_slots_check(&a->slots, a->win.T));
   const long plane = (long)a->H * a->W;                                   // <= 2^30
-  for (int v = 0; v < a->win.nvars; ++v) {
-    const unsigned is_map = a->is_map[v] & ((1u << a->n_events) - 1u);
-    if (!is_map) continue;
-    if (!a->maps || ((uintptr_t)a->maps & 3) || a->n_maps < 1 || a->map_first[v] < 0 ||
-        (long)a->map_first[v] + __builtin_popcount(is_map) > (long)a->n_maps)
-      return SDY_ERR_ARG;
-    if ((long)a->n_maps * plane >= (1L << 40)) return SDY_ERR_UNSUPPORTED;
-  }
+  SDY_TRY(sdy_event_thresholds_check(&a->thr, a->win.nvars));
+  SDY_TRY(sdy_event_thresholds_supported(&a->thr, a->win.nvars, plane));
   if (a->win.n0 > kMaxMembers) return SDY_ERR_UNSUPPORTED;
-  const int E = a->n_events, M = a->win.n0;
+  const int E = a->thr.n_events, M = a->win.n0;
   if (table) {
     // the 32-bit LDS words of a row: one launch adds at most the row's points to a bin
-    const long per_row = (long)a->win.n1 * a->W * (a->pool_times ? (long)a->win.T : 1L);      // < 2^31 * 2^30
+    const long per_row = (long)a->win.n1 * a->W * (a->slots.pool_times ? (long)a->win.T : 1L);      // < 2^31 * 2^30
     if (per_row >= (1L << 32)) return SDY_ERR_UNSUPPORTED;
     // 64-bit flat accumulator indices: n_slots * H < 2^62, and nvars <= 96 rows of E * 2 * (M + 1) <= 1040 bins stay below 2^57
-    const long rows = (long)a->n_slots * a->H;
+    const long rows = (long)a->slots.n_slots * a->H;
     if (rows >= (1L << 40) || (long)a->win.nvars * rows * row_words(E, M) >= (1L << 50)) return SDY_ERR_UNSUPPORTED;
     if (row_bytes_lds(E, M) > kLdsBytes) return SDY_ERR_UNSUPPORTED;      // (not reached within the two maxima: 4160 bytes)
   } else {
@@ -241,28 +209,7 @@ int check(const sdy_event_args* a, bool table) {
 }
 
 bool vec4(const sdy_event_args* a, long inner) {
-  return sdy_window_vec4(&a->win, inner) && (((long)a->H * a->W) & 3) == 0 && ((uintptr_t)a->maps & 15) == 0;
-}
-
-// the threshold of event e of variable v at grid point p, host side
-float host_threshold(const sdy_event_args* a, int v, int e, long plane, long p) {
-  if ((a->is_map[v] >> e) & 1u) return a->maps[(long)sdy_ev_map_plane(a->map_first[v], a->is_map[v], e) * plane + p];
-  return a->scalars[v * a->n_events + e];
-}
-
-template <template <int, int> class Launch, class... Args>
-void dispatch(bool vec, int E, Args... args) {
-  switch (E) {
-#define SDY_EV_CASE(N)                \
-  case N:                             \
-    if (vec)                          \
-      Launch<4, N>::go(args...);      \
-    else                              \
-      Launch<1, N>::go(args...);      \
-    break;
-    SDY_EV_CASE(1) SDY_EV_CASE(2) SDY_EV_CASE(3) SDY_EV_CASE(4) SDY_EV_CASE(5) SDY_EV_CASE(6) SDY_EV_CASE(7) SDY_EV_CASE(8)
-#undef SDY_EV_CASE
-  }
+  return sdy_window_vec4(&a->win, inner) && (((long)a->H * a->W) & 3) == 0 && sdy_event_thresholds_vec4(&a->thr);
 }
 
 template <int W4, int EC>
@@ -285,24 +232,24 @@ extern "C" int sdy_event_table_accumulate_host(const sdy_event_args* a) {
   SDY_TRY(check(a, true));
   const sdy_window& w = a->win;
   const long plane = (long)a->H * a->W;
-  const int M = w.n0, E = a->n_events;
+  const int M = w.n0, E = a->thr.n_events;
   for (int v = 0; v < w.nvars; ++v)
     for (long s = 0; s < w.n1; ++s)
-      for (long t = a->t0; t < w.T; ++t)
+      for (long t = a->slots.t0; t < w.T; ++t)
         for (long lat = 0; lat < a->H; ++lat) {
-          const long slot = a->pool_times ? 0 : a->t_start + t;
+          const long slot = sdy_lead_slot(a->slots, t);
           const long in_row = t * plane + lat * a->W;
           const float* tg = w.target[v] + s * w.ts1 + in_row;
           const float* g = w.gen[v] + s * w.gs1 + in_row;
           for (long p = 0; p < a->W; ++p)
             for (int e = 0; e < E; ++e) {
-              const float c = host_threshold(a, v, e, plane, lat * a->W + p);
-              const bool below = (a->below[v] >> e) & 1u;
+              const float c = sdy_event_threshold_host(&a->thr, v, e, plane, lat * a->W + p);
+              const bool below = (a->thr.below[v] >> e) & 1u;
               if (!sdy_ev_counted(tg[p], c)) continue;
               int k = 0;
               for (long i0 = 0; i0 < M; ++i0) k += sdy_ev_in(g[i0 * w.gs0 + p], c, below) ? 1 : 0;
               const int o = sdy_ev_in(tg[p], c, below) ? 1 : 0;
-              a->acc[sdy_ev_table_at(v, a->n_slots, slot, E, e, a->H, lat, M, o, k)] += 1.0;
+              a->acc[sdy_ev_table_at(v, a->slots.n_slots, slot, E, e, a->H, lat, M, o, k)] += 1.0;
             }
         }
   return SDY_OK;
@@ -310,19 +257,19 @@ extern "C" int sdy_event_table_accumulate_host(const sdy_event_args* a) {
 
 extern "C" int sdy_event_table_accumulate(const sdy_event_args* a, void* stream) {
   SDY_TRY(check(a, true));
-  if (a->win.T - a->t0 == 0) return SDY_OK;        // a window that holds the initial condition only
+  if (a->win.T - a->slots.t0 == 0) return SDY_OK;        // a window that holds the initial condition only
   const bool vec = vec4(a, a->W);
   const int G = lane_group(vec ? a->W / 4 : a->W);
-  const unsigned n_rows = (unsigned)((a->pool_times ? 1L : (long)(a->win.T - a->t0)) * a->H);      // <= T * H <= 2^30
+  const unsigned n_rows = (unsigned)((a->slots.pool_times ? 1L : (long)(a->win.T - a->slots.t0)) * a->H);      // <= T * H <= 2^30
   // rows of a block: what kThreads lanes cover, capped by the LDS the rows' bins take (at least one: check())
-  const long row_bytes = row_bytes_lds(a->n_events, a->win.n0);
+  const long row_bytes = row_bytes_lds(a->thr.n_events, a->win.n0);
   long rows_per_block = kThreads / G;
   if (rows_per_block * row_bytes > kLdsBytes) rows_per_block = kLdsBytes / row_bytes;
   const size_t lds = (size_t)(rows_per_block * row_bytes);
   if (rows_per_block < 1 || lds > (size_t)kLdsBytes) return SDY_ERR_UNSUPPORTED;
   const dim3 grid(sdy_grid_cap((n_rows + rows_per_block - 1) / rows_per_block, a->win.nvars, kBlocksPerLaunch, kMinBlocksPerVar),
                   a->win.nvars);
-  dispatch<LaunchTable>(vec, a->n_events, *a, grid, (int)(rows_per_block * G), lds, (hipStream_t)stream, G, n_rows);
+  dispatch<LaunchTable>(vec, a->thr.n_events, *a, grid, (int)(rows_per_block * G), lds, (hipStream_t)stream, G, n_rows);
   return sdy_launch_status();
 }
 
@@ -330,16 +277,16 @@ extern "C" int sdy_event_frequency_accumulate_host(const sdy_event_args* a) {
   SDY_TRY(check(a, false));
   const sdy_window& w = a->win;
   const long plane = (long)a->H * a->W;
-  const int M = w.n0, E = a->n_events;
+  const int M = w.n0, E = a->thr.n_events;
   for (int v = 0; v < w.nvars; ++v)
     for (long s = 0; s < w.n1; ++s)
-      for (long t = a->t0; t < w.T; ++t) {
+      for (long t = a->slots.t0; t < w.T; ++t) {
         const float* tg = w.target[v] + s * w.ts1 + t * plane;
         const float* g = w.gen[v] + s * w.gs1 + t * plane;
         for (long p = 0; p < plane; ++p)
           for (int e = 0; e < E; ++e) {
-            const float c = host_threshold(a, v, e, plane, p);
-            const bool below = (a->below[v] >> e) & 1u;
+            const float c = sdy_event_threshold_host(&a->thr, v, e, plane, p);
+            const bool below = (a->thr.below[v] >> e) & 1u;
             if (!sdy_ev_counted(tg[p], c)) continue;
             int k = 0;
             for (long i0 = 0; i0 < M; ++i0) k += sdy_ev_in(g[i0 * w.gs0 + p], c, below) ? 1 : 0;
@@ -353,12 +300,12 @@ extern "C" int sdy_event_frequency_accumulate_host(const sdy_event_args* a) {
 
 extern "C" int sdy_event_frequency_accumulate(const sdy_event_args* a, void* stream) {
   SDY_TRY(check(a, false));
-  if (a->win.T - a->t0 == 0) return SDY_OK;
+  if (a->win.T - a->slots.t0 == 0) return SDY_OK;
   const long plane = (long)a->H * a->W;
   const bool vec = vec4(a, plane);
   const unsigned n_items = (unsigned)(vec ? plane / 4 : plane);                                    // <= 2^30
   const dim3 grid(sdy_grid_cap(((unsigned long)n_items + kThreads - 1) / kThreads, a->win.nvars, kBlocksPerLaunch, kMinBlocksPerVar),
                   a->win.nvars);
-  dispatch<LaunchFrequency>(vec, a->n_events, *a, grid, (hipStream_t)stream, n_items);
+  dispatch<LaunchFrequency>(vec, a->thr.n_events, *a, grid, (hipStream_t)stream, n_items);
   return sdy_launch_status();
 }

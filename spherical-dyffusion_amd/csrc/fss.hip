@@ -14,6 +14,7 @@
 // (event_count.h): nothing lands in scratch.  The arithmetic of a point and of a centre is events.h and fss.h.
 #include "common.h"
 #include "event_count.h"
+#include "event_thresholds.h"
 #include "events.h"
 #include "fss.h"
 #include "window.h"
@@ -51,19 +52,19 @@ __global__ __launch_bounds__(kThreads) void fss_encode_kernel(const sdy_fss_args
   const int v = blockIdx.y;
   const int M = a.win.n0, n1 = a.win.n1, T = a.win.T;
   const unsigned plane = (unsigned)a.H * (unsigned)a.W;
-  const unsigned below = a.below[v], is_map = a.is_map[v];
+  const unsigned below = a.thr.below[v], is_map = a.thr.is_map[v];
   const long gs0 = a.win.gs0, gs1 = a.win.gs1, ts1 = a.win.ts1;
   unsigned short* codes = static_cast<unsigned short*>(a.ws);
   EventRegs<EC> r;
-  event_regs<EC>(a, v, is_map, below, r);
+  event_regs<EC>(a.thr, v, is_map, below, r);
   for (unsigned idx = blockIdx.x * kThreads + threadIdx.x; idx < n_items; idx += gridDim.x * kThreads) {
     const unsigned p = idx * W4;
     float c[EC][W4];
-    thresholds<W4, EC>(a, is_map, r, plane, p, c);
+    thresholds<W4, EC>(a.thr, is_map, r, plane, p, c);
     for (int s = 0; s < n1; ++s) {
       const float* tg = a.win.target[v] + (long)s * ts1;
       const float* g = a.win.gen[v] + (long)s * gs1;
-      for (int t = a.t0; t < T; ++t) {
+      for (int t = a.slots.t0; t < T; ++t) {
         const unsigned off_b = ((unsigned)t * plane + p) * 4u;
         const Vec<W4> y = ld_u<W4>(tg, off_b);
         int k[EC][W4];
@@ -138,14 +139,14 @@ __device__ __forceinline__ int radius(const sdy_fss_args& a, int j) {
 // to rows < band + 2 r; box sums: M (2 r_max + 1)^2 <= 65535; a row sum < 2^53; slot < n_slots; flat accumulator indices < 2^50.
 __global__ __launch_bounds__(kThreads) void fss_sum_kernel(const sdy_fss_args a, int band, int chunk_rows, unsigned n_bands) {
   extern __shared__ unsigned long long s_fss[];
-  const int H = a.H, W = a.W, E = a.n_events, R = a.n_radii, n1 = a.win.n1, T = a.win.T;
+  const int H = a.H, W = a.W, E = a.thr.n_events, R = a.n_radii, n1 = a.win.n1, T = a.win.T;
   const int r_max = radius(a, R - 1), v = blockIdx.y, e = blockIdx.z;
   unsigned long long* s_sum = s_fss;                                          // [band][6]
   unsigned* s_hs = reinterpret_cast<unsigned*>(s_sum + band * SDY_FSS_TERMS);  // [band + 2 r_max][W]
   unsigned* s_pk = s_hs + (band + 2 * r_max) * W;                              // [chunk_rows][W + 2 r]
   const unsigned short* codes = static_cast<const unsigned short*>(a.ws);
   const long plane = (long)H * W;
-  const bool pool = a.pool_times != 0;
+  const bool pool = a.slots.pool_times != 0;
   const int tid = threadIdx.x, per_row = kThreads / band, my_row = tid / per_row, lir = tid - my_row * per_row;
   // point tid of a pass as (row, lon), and the step to point tid + kThreads: no division inside the loops
   const int row0 = tid / W, lon0 = tid - row0 * W;
@@ -154,10 +155,10 @@ __global__ __launch_bounds__(kThreads) void fss_sum_kernel(const sdy_fss_args a,
   asm volatile("" : "+v"(row_step), "+v"(lon_step), "+v"(lon_stride));
   const int tt = (int)(blockIdx.x / n_bands), b = (int)(blockIdx.x - (unsigned)tt * n_bands);
   const int lat0 = b * band, lat = lat0 + my_row;
-  const int t_begin = a.t0 + (pool ? 0 : tt), t_end = pool ? T : t_begin + 1;
-  const long slot = pool ? 0 : (long)a.t_start + t_begin;                   // < n_slots
+  const int t_begin = a.slots.t0 + (pool ? 0 : tt), t_end = pool ? T : t_begin + 1;
+  const long slot = sdy_lead_slot(a.slots, t_begin);                        // < n_slots
   // the band's first accumulator row of radius 0 (in vector registers: it is not looked at before the sums are done)
-  double* out0 = a.acc + sdy_fss_at(v, a.n_slots, slot, E, e, R, 0, H, lat0);
+  double* out0 = a.acc + sdy_fss_at(v, a.slots.n_slots, slot, E, e, R, 0, H, lat0);
   asm volatile("" : "+v"(out0));
   for (int j = 0; j < R; ++j) {
     const int r = radius(a, j), padded = W + 2 * r;
@@ -244,28 +245,16 @@ int check(const sdy_fss_args* a, bool device, SumPlan* plan) {
   if (!a) return SDY_ERR_ARG;
   if (a->H < 1 || a->W < 1) return SDY_ERR_ARG;
   SDY_TRY(sdy_window_check(&a->win, (long)a->H * a->W));
-  if (!a->acc || !a->scalars || ((uintptr_t)a->acc & 7) || ((uintptr_t)a->scalars & 3)) return SDY_ERR_ARG;
-  if (a->n_events < 1 || a->n_events > SDY_EVENT_MAX) return SDY_ERR_ARG;
-  if (a->n_slots < 1 || a->t0 < 0 || a->t0 > a->win.T) return SDY_ERR_ARG;
-  if (a->pool_times) {
-    if (a->n_slots != 1) return SDY_ERR_ARG;
-  } else if (a->t_start < 0 || (long)a->t_start + (long)a->win.T > (long)a->n_slots) {
-    return SDY_ERR_ARG;
-  }
+  if (!a->acc || ((uintptr_t)a->acc & 7)) return SDY_ERR_ARG;
+  SDY_TRY(sdy_lead_slots_check(&a->slots, a->win.T));
   if (a->n_radii < 1 || a->n_radii > SDY_FSS_MAX_RADII) return SDY_ERR_ARG;
   for (int j = 0; j < a->n_radii; ++j) {
     if (a->radii[j] < 0 || (j > 0 && a->radii[j] <= a->radii[j - 1])) return SDY_ERR_ARG;
     if (2L * a->radii[j] + 1 > (long)a->W) return SDY_ERR_ARG;
   }
   const long plane = (long)a->H * a->W;                                   // <= 2^30
-  const int E = a->n_events, M = a->win.n0, R = a->n_radii;
-  for (int v = 0; v < a->win.nvars; ++v) {
-    const unsigned is_map = a->is_map[v] & ((1u << E) - 1u);
-    if (!is_map) continue;
-    if (!a->maps || ((uintptr_t)a->maps & 3) || a->n_maps < 1 || a->map_first[v] < 0 ||
-        (long)a->map_first[v] + __builtin_popcount(is_map) > (long)a->n_maps)
-      return SDY_ERR_ARG;
-  }
+  SDY_TRY(sdy_event_thresholds_check(&a->thr, a->win.nvars));
+  const int E = a->thr.n_events, M = a->win.n0, R = a->n_radii;
   if (device || a->ws) {
     // (a workspace whose codes pass 2^50 has no size: sdy_fss_workspace_bytes is 0, and the call is refused below)
     if (!a->ws || ((uintptr_t)a->ws & 7)) return SDY_ERR_ARG;
@@ -274,31 +263,25 @@ int check(const sdy_fss_args* a, bool device, SumPlan* plan) {
   if (M > SDY_EVENT_MAX_MEMBERS) return SDY_ERR_UNSUPPORTED;
   const long r_max = a->radii[R - 1], side = 2 * r_max + 1;               // side <= W < 2^31
   if (side > 255 || (long)M * side * side > 65535) return SDY_ERR_UNSUPPORTED;        // (255: no side above it can pass)
-  for (int v = 0; v < a->win.nvars; ++v)
-    if ((a->is_map[v] & ((1u << E) - 1u)) && (long)a->n_maps * plane >= (1L << 40)) return SDY_ERR_UNSUPPORTED;
+  SDY_TRY(sdy_event_thresholds_supported(&a->thr, a->win.nvars, plane));
   // the 64-bit row sums and one call's float64 additions: the largest term, (M n_max)^2 < 2^32, times the centres of a row,
   // n1 * W * T < 2^61
   const long n_max = side * (a->H < side ? a->H : side), term = (M * n_max) * (M * n_max);
-  const long centres = (long)a->win.n1 * a->W * (a->pool_times ? (long)(a->win.T - a->t0) : 1L);
+  const long centres = (long)a->win.n1 * a->W * (a->slots.pool_times ? (long)(a->win.T - a->slots.t0) : 1L);
   if (centres > ((1L << 53) - 1) / term) return SDY_ERR_UNSUPPORTED;
-  const long rows = (long)a->n_slots * a->H;
+  const long rows = (long)a->slots.n_slots * a->H;
   if (rows >= (1L << 40) || (long)a->win.nvars * rows * E * R * SDY_FSS_TERMS >= (1L << 50)) return SDY_ERR_UNSUPPORTED;
   if ((double)a->win.nvars * E * a->win.n1 * a->win.T * plane >= 0x1p50) return SDY_ERR_UNSUPPORTED;     // the codes
   SumPlan mine;
   if (!plan_sum(a->H, a->W, (int)r_max, &mine)) return SDY_ERR_UNSUPPORTED;
-  if ((a->pool_times ? 1L : (long)(a->win.T - a->t0)) * mine.n_bands > kMaxSumItems) return SDY_ERR_UNSUPPORTED;
+  if ((a->slots.pool_times ? 1L : (long)(a->win.T - a->slots.t0)) * mine.n_bands > kMaxSumItems) return SDY_ERR_UNSUPPORTED;
   if (plan) *plan = mine;
   return SDY_OK;
 }
 
 bool vec4(const sdy_fss_args* a) {
   const long plane = (long)a->H * a->W;
-  return sdy_window_vec4(&a->win, plane) && ((uintptr_t)a->maps & 15) == 0;
-}
-
-float host_threshold(const sdy_fss_args* a, int v, int e, long plane, long p) {
-  if ((a->is_map[v] >> e) & 1u) return a->maps[(long)sdy_ev_map_plane(a->map_first[v], a->is_map[v], e) * plane + p];
-  return a->scalars[v * a->n_events + e];
+  return sdy_window_vec4(&a->win, plane) && sdy_event_thresholds_vec4(&a->thr);
 }
 
 template <int W4, int EC>
@@ -314,23 +297,13 @@ int launch_encode(const sdy_fss_args* a, hipStream_t stream) {
   const unsigned n_items = (unsigned)(vec ? plane / 4 : plane);                                     // <= 2^30
   const dim3 grid(sdy_grid_cap(((unsigned long)n_items + kThreads - 1) / kThreads, a->win.nvars, kBlocksPerLaunch, kMinBlocksPerVar),
                   a->win.nvars);
-  switch (a->n_events) {
-#define SDY_FSS_CASE(N)                                   \
-  case N:                                                 \
-    if (vec)                                              \
-      LaunchEncode<4, N>::go(*a, grid, stream, n_items);  \
-    else                                                  \
-      LaunchEncode<1, N>::go(*a, grid, stream, n_items);  \
-    break;
-    SDY_FSS_CASE(1) SDY_FSS_CASE(2) SDY_FSS_CASE(3) SDY_FSS_CASE(4) SDY_FSS_CASE(5) SDY_FSS_CASE(6) SDY_FSS_CASE(7) SDY_FSS_CASE(8)
-#undef SDY_FSS_CASE
-  }
+  dispatch<LaunchEncode>(vec, a->thr.n_events, *a, grid, stream, n_items);
   return sdy_launch_status();
 }
 
 int launch_sum(const sdy_fss_args* a, const SumPlan& plan, hipStream_t stream) {
-  const unsigned n_tt = a->pool_times ? 1u : (unsigned)(a->win.T - a->t0);
-  const dim3 grid(n_tt * (unsigned)plan.n_bands, a->win.nvars, a->n_events);      // x <= kMaxSumItems: check()
+  const unsigned n_tt = a->slots.pool_times ? 1u : (unsigned)(a->win.T - a->slots.t0);
+  const dim3 grid(n_tt * (unsigned)plan.n_bands, a->win.nvars, a->thr.n_events);  // x <= kMaxSumItems: check()
   hipLaunchKernelGGL(fss_sum_kernel, grid, dim3(kThreads), plan.lds, stream, *a, plan.band, plan.chunk_rows, (unsigned)plan.n_bands);
   return sdy_launch_status();
 }
@@ -348,19 +321,19 @@ extern "C" size_t sdy_fss_workspace_bytes(int nvars, int n_events, int n1, int T
 extern "C" int sdy_fss_accumulate_host(const sdy_fss_args* a) {
   SDY_TRY(check(a, false, nullptr));
   const sdy_window& w = a->win;
-  const int H = a->H, W = a->W, M = w.n0, E = a->n_events, R = a->n_radii;
+  const int H = a->H, W = a->W, M = w.n0, E = a->thr.n_events, R = a->n_radii;
   const long plane = (long)H * W;
   std::vector<unsigned> k(plane), o(plane), c(plane), hk(plane), ho(plane), hc(plane);
   for (int v = 0; v < w.nvars; ++v)
     for (long s = 0; s < w.n1; ++s)
-      for (long t = a->t0; t < w.T; ++t)
+      for (long t = a->slots.t0; t < w.T; ++t)
         for (int e = 0; e < E; ++e) {
-          const long slot = a->pool_times ? 0 : a->t_start + t;
+          const long slot = sdy_lead_slot(a->slots, t);
           const float* tg = w.target[v] + s * w.ts1 + t * plane;
           const float* g = w.gen[v] + s * w.gs1 + t * plane;
-          const bool below = (a->below[v] >> e) & 1u;
+          const bool below = (a->thr.below[v] >> e) & 1u;
           for (long p = 0; p < plane; ++p) {
-            const float thr = host_threshold(a, v, e, plane, p);
+            const float thr = sdy_event_threshold_host(&a->thr, v, e, plane, p);
             unsigned members = 0;
             for (long i0 = 0; i0 < M; ++i0) members += sdy_ev_in(g[i0 * w.gs0 + p], thr, below) ? 1u : 0u;
             const unsigned code = sdy_fss_code(members, sdy_ev_in(tg[p], thr, below) ? 1u : 0u, sdy_ev_counted(tg[p], thr) ? 1u : 0u);
@@ -388,7 +361,7 @@ extern "C" int sdy_fss_accumulate_host(const sdy_fss_args* a) {
                   K += hk[(long)row * W + lon], O += ho[(long)row * W + lon], C += hc[(long)row * W + lon];
                 sdy_fss_add_centre(sum, K, O, C, n);
               }
-              double* out = a->acc + sdy_fss_at(v, a->n_slots, slot, E, e, R, j, H, lat);
+              double* out = a->acc + sdy_fss_at(v, a->slots.n_slots, slot, E, e, R, j, H, lat);
               for (int q = 0; q < SDY_FSS_TERMS; ++q) out[q] += (double)sum[q];
             }
           }
@@ -398,21 +371,21 @@ extern "C" int sdy_fss_accumulate_host(const sdy_fss_args* a) {
 
 extern "C" int sdy_fss_encode(const sdy_fss_args* a, void* stream) {
   SDY_TRY(check(a, true, nullptr));
-  if (a->win.T - a->t0 == 0) return SDY_OK;        // a window that holds the initial condition only
+  if (a->win.T - a->slots.t0 == 0) return SDY_OK;        // a window that holds the initial condition only
   return launch_encode(a, (hipStream_t)stream);
 }
 
 extern "C" int sdy_fss_sum(const sdy_fss_args* a, void* stream) {
   SumPlan plan;
   SDY_TRY(check(a, true, &plan));
-  if (a->win.T - a->t0 == 0) return SDY_OK;
+  if (a->win.T - a->slots.t0 == 0) return SDY_OK;
   return launch_sum(a, plan, (hipStream_t)stream);
 }
 
 extern "C" int sdy_fss_accumulate(const sdy_fss_args* a, void* stream) {
   SumPlan plan;
   SDY_TRY(check(a, true, &plan));
-  if (a->win.T - a->t0 == 0) return SDY_OK;
+  if (a->win.T - a->slots.t0 == 0) return SDY_OK;
   SDY_TRY(launch_encode(a, (hipStream_t)stream));
   return launch_sum(a, plan, (hipStream_t)stream);
 }

@@ -7,6 +7,7 @@
 // integers below 2^53 add exactly, so every count has the same bits in any layout, batch or run.  The arithmetic of a grid
 // point is rank_hist.h.
 #include "common.h"
+#include "event_thresholds.h"
 #include "rank_hist.h"
 #include "window.h"
 
@@ -20,45 +21,8 @@ constexpr int kMinBlocksPerVar = 32;
 // flight count for more than the waves.
 constexpr int kMembersInFlight = 8;
 constexpr int kMaxMembers = SDY_RANK_HIST_MAX_MEMBERS;
-constexpr int kMinGroup = 4;            // lanes of the narrowest group: at most kThreads / kMinGroup rows per block
+constexpr int kMinGroup = kMinLaneGroup;  // lanes of the narrowest group: at most kThreads / kMinGroup rows per block
 constexpr int kRowWords = kMaxMembers + 2;
-
-// Lanes per accumulator row, a power of two in kMinGroup .. 64 (units: the 16-byte or 4-byte loads of one latitude row).  A
-// row of at most 16 units takes one pass of the narrowest group that covers it.  A longer row takes the group of 16, 32 or 64
-// lanes that leaves the fewest lane slots idle over its passes, the wider one of equals (longer contiguous runs per load):
-// 90 units (360 longitudes) -> 32 lanes x 3 passes, 90 of 96 slots busy, where one wave per row has 90 of 128.
-int lane_group(int units) {
-  if (units <= 16) {
-    int G = kMinGroup;
-    while (G < units) G <<= 1;
-    return G;
-  }
-  int best = 16;
-  long best_slots = 16L * ((units + 15) / 16);
-  for (int G = 32; G <= 64; G <<= 1) {
-    const long slots = (long)G * ((units + G - 1) / G);
-    if (slots <= best_slots) {
-      best = G;
-      best_slots = slots;
-    }
-  }
-  return best;
-}
-
-// A load of W4 floats as (wave-uniform 64-bit base) + (32-bit byte offset per lane), the SADDR form of global_load (see
-// sdy_ld16s, common.h): a member's base is scalar arithmetic, and a thread keeps one offset for the target and every member
-// of a unit instead of one 64-bit address per load in flight.
-typedef float __attribute__((address_space(1))) gfloat;
-template <int W4>
-__device__ __forceinline__ Vec<W4> ld_u(const float* ubase, unsigned off_b);
-template <>
-__device__ __forceinline__ f32x4 ld_u<4>(const float* ubase, unsigned off_b) { return sdy_ld16s(ubase, off_b); }
-template <>
-__device__ __forceinline__ float ld_u<1>(const float* ubase, unsigned off_b) {
-  sdy_gcptr_t b = (sdy_gcptr_t)ubase;
-  asm volatile("" : "+s"(b), "+v"(off_b));
-  return *reinterpret_cast<const gfloat*>(b + off_b);
-}
 
 // G lanes share accumulator row `row` of variable blockIdx.y: row = tt * H + lat, where tt numbers the counted times of the
 // window (one row per latitude when the times are pooled).  Each lane takes every G-th unit (4 longitudes or 1) of the
@@ -73,7 +37,7 @@ __global__ __launch_bounds__(kThreads) void rank_hist_kernel(const sdy_rank_hist
   const int v = blockIdx.y;
   const int lig = threadIdx.x & (G - 1), group = threadIdx.x / G, rows_per_block = kThreads / G;
   const int units = a.W / W4, M = a.win.n0, n1 = a.win.n1, T = a.win.T, H = a.H, words = M + 2;
-  const bool pool = a.pool_times != 0;
+  const bool pool = a.slots.pool_times != 0;
   const unsigned plane = (unsigned)H * (unsigned)a.W;
   const long gs0 = a.win.gs0, gs1 = a.win.gs1, ts1 = a.win.ts1;
   unsigned* mine = s_rows + group * words;      // [0, M]: the bins, [M + 1]: the ties
@@ -85,7 +49,7 @@ __global__ __launch_bounds__(kThreads) void rank_hist_kernel(const sdy_rank_hist
     const bool active = row < n_rows;
     const unsigned tt = row / (unsigned)H, lat = row - tt * (unsigned)H;
     if (active) {
-      const int t_begin = a.t0 + (pool ? 0 : (int)tt), t_end = pool ? T : t_begin + 1;
+      const int t_begin = a.slots.t0 + (pool ? 0 : (int)tt), t_end = pool ? T : t_begin + 1;
       unsigned tied = 0u;
       for (int s = 0; s < n1; ++s) {
         const float* tg = a.win.target[v] + (long)s * ts1;               // wave-uniform, as is every member's base below
@@ -135,8 +99,7 @@ __global__ __launch_bounds__(kThreads) void rank_hist_kernel(const sdy_rank_hist
     }
     __syncthreads();
     if (active) {
-      const long slot = pool ? 0 : (long)a.t_start + a.t0 + (long)tt;   // < n_slots
-      const long r = sdy_rh_row(v, a.n_slots, slot, H, lat);
+      const long r = sdy_rh_row(v, a.slots.n_slots, sdy_lead_slot(a.slots, (long)a.slots.t0 + (long)tt), H, lat);
       double* counts = a.counts + r * (M + 1);
       for (int k = lig; k < words; k += G) {
         const unsigned n = mine[k];
@@ -153,22 +116,16 @@ __global__ __launch_bounds__(kThreads) void rank_hist_kernel(const sdy_rank_hist
 // everything that bounds an address or a counter, for the device and the host entry point alike
 int check(const sdy_rank_hist_args* a) {
   if (!a) return SDY_ERR_ARG;
-  if (a->H < 1 || a->W < 1 || a->n_slots < 1) return SDY_ERR_ARG;
-  if (a->t0 < 0 || a->t0 > a->win.T) return SDY_ERR_ARG;
-  if (a->pool_times) {
-    if (a->n_slots != 1) return SDY_ERR_ARG;
-  } else if (a->t_start < 0 || (long)a->t_start + (long)a->win.T > (long)a->n_slots) {
-    // window times t_start .. t_start + T - 1 must all exist (in 64 bits: no wrap)
-    return SDY_ERR_ARG;
-  }
+  if (a->H < 1 || a->W < 1) return SDY_ERR_ARG;
+  SDY_TRY(sdy_lead_slots_check(&a->slots, a->win.T));
   if (!a->counts || !a->ties || (((uintptr_t)a->counts | (uintptr_t)a->ties) & 7)) return SDY_ERR_ARG;
   SDY_TRY(sdy_window_check(&a->win, (long)a->H * a->W));
   if (a->win.n0 > kMaxMembers) return SDY_ERR_UNSUPPORTED;
   // the 32-bit LDS words of a row: one launch adds at most the row's points to a bin
-  const long per_row = (long)a->win.n1 * a->W * (a->pool_times ? (long)a->win.T : 1L);      // < 2^31 * 2^30
+  const long per_row = (long)a->win.n1 * a->W * (a->slots.pool_times ? (long)a->win.T : 1L);      // < 2^31 * 2^30
   if (per_row >= (1L << 32)) return SDY_ERR_UNSUPPORTED;
   // 64-bit flat accumulator indices: n_slots * H < 2^62, and nvars <= 96 rows of M + 1 <= 65 bins stay below 2^53 then
-  const long rows = (long)a->n_slots * a->H;
+  const long rows = (long)a->slots.n_slots * a->H;
   if (rows >= (1L << 40) || (long)a->win.nvars * rows * (a->win.n0 + 1) >= (1L << 50)) return SDY_ERR_UNSUPPORTED;
   return SDY_OK;
 }
@@ -182,10 +139,9 @@ extern "C" int sdy_rank_hist_accumulate_host(const sdy_rank_hist_args* a) {
   const int M = w.n0;
   for (int v = 0; v < w.nvars; ++v)
     for (long s = 0; s < w.n1; ++s)
-      for (long t = a->t0; t < w.T; ++t)
+      for (long t = a->slots.t0; t < w.T; ++t)
         for (long lat = 0; lat < a->H; ++lat) {
-          const long slot = a->pool_times ? 0 : a->t_start + t;
-          const long r = sdy_rh_row(v, a->n_slots, slot, a->H, lat);
+          const long r = sdy_rh_row(v, a->slots.n_slots, sdy_lead_slot(a->slots, t), a->H, lat);
           const long in_row = t * plane + lat * a->W;
           const float* tg = w.target[v] + s * w.ts1 + in_row;
           const float* g = w.gen[v] + s * w.gs1 + in_row;
@@ -203,10 +159,10 @@ extern "C" int sdy_rank_hist_accumulate_host(const sdy_rank_hist_args* a) {
 
 extern "C" int sdy_rank_hist_accumulate(const sdy_rank_hist_args* a, void* stream) {
   SDY_TRY(check(a));
-  if (a->win.T - a->t0 == 0) return SDY_OK;        // a window that holds the initial condition only
+  if (a->win.T - a->slots.t0 == 0) return SDY_OK;        // a window that holds the initial condition only
   const bool vec = sdy_window_vec4(&a->win, a->W);
   const int G = lane_group(vec ? a->W / 4 : a->W);
-  const unsigned n_rows = (unsigned)((a->pool_times ? 1L : (long)(a->win.T - a->t0)) * a->H);      // <= T * H <= 2^30
+  const unsigned n_rows = (unsigned)((a->slots.pool_times ? 1L : (long)(a->win.T - a->slots.t0)) * a->H);      // <= T * H <= 2^30
   const unsigned long rows_per_block = kThreads / G;
   const dim3 grid(sdy_grid_cap((n_rows + rows_per_block - 1) / rows_per_block, a->win.nvars, kBlocksPerLaunch, kMinBlocksPerVar),
                   a->win.nvars);

@@ -13,6 +13,7 @@
 // pass finds them in cache), so that the state of a pass stays within 64 registers.  The arithmetic is spells.h and events.h.
 #include "common.h"
 #include "event_count.h"
+#include "event_thresholds.h"
 #include "spells.h"
 #include "window.h"
 
@@ -22,13 +23,12 @@ constexpr int kThreads = 256;
 constexpr int kBlocksPerLaunch = 16384;  // over all variables; a variable with more rows strides over them
 constexpr int kMinBlocksPerVar = 32;
 constexpr int kMaxMembers = SDY_EVENT_MAX_MEMBERS;
-constexpr int kMaxEvents = SDY_EVENT_MAX;
 // independent time loads a thread issues before it consumes the first: with more than 4 events (two passes) the second half of 8
 // loads would take the scalar registers of its time indices from a kernel that has none to spare
 template <int EC>
 constexpr int kTimesInFlight = EC > 4 ? 4 : 8;
 constexpr int kEventsPerPass = 4;
-constexpr int kRowWordsMax = kMaxEvents * 2 * SDY_SPELL_BINS;
+constexpr int kRowWordsMax = SDY_EVENT_MAX * 2 * SDY_SPELL_BINS;
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 template <int W4>
@@ -60,11 +60,11 @@ __device__ __forceinline__ void spell_item(const sdy_event_spell_args& a, int v,
     sign[e] = sdy_ev_sign((below >> ee) & 1u);
     asm volatile("" : "+v"(sign[e]));      // wave-uniform, kept in a vector register on purpose (event_count.h)
     if ((bits >> ee) & 1u) {               // wave-uniform: no divergence
-      const Vec<W4> m = ld<W4>(a.maps + ((long)sdy_ev_map_plane(a.map_first[v], is_map, ee) * plane + in_plane));
+      const Vec<W4> m = ld<W4>(a.thr.maps + ((long)sdy_ev_map_plane(a.thr.map_first[v], is_map, ee) * plane + in_plane));
 #pragma unroll
       for (int q = 0; q < W4; ++q) c[e][q] = sdy_ev_signed(comp(m, q), sign[e]);
     } else {
-      float s = sdy_ev_signed(a.scalars[v * E + ee], sign[e]);
+      float s = sdy_ev_signed(a.thr.scalars[v * E + ee], sign[e]);
       asm volatile("" : "+v"(s));
 #pragma unroll
       for (int q = 0; q < W4; ++q) c[e][q] = s;
@@ -136,7 +136,7 @@ __global__ __launch_bounds__(kThreads) void spell_kernel(const sdy_event_spell_a
   const unsigned gen_rows = (unsigned)a.win.n0 * (unsigned)n1;        // < 2^31
   const unsigned rows = gen_rows + (unsigned)n1;
   const unsigned n_items = rows * units;                              // < 2^32
-  const unsigned below = a.below[v], is_map = a.is_map[v];
+  const unsigned below = a.thr.below[v], is_map = a.thr.is_map[v];
   for (int w = threadIdx.x; w < words; w += kThreads) s_bins[w] = 0u;
   for (int lat = blockIdx.x; lat < H; lat += gridDim.x) {
     // the row's words are zero: set above, or by the thread that read them behind the previous row
@@ -173,43 +173,34 @@ int check(const sdy_event_spell_args* a) {
   if (!a || a->struct_size != sizeof(sdy_event_spell_args)) return SDY_ERR_ARG;
   if (a->H < 1 || a->W < 1) return SDY_ERR_ARG;
   SDY_TRY(sdy_window_check(&a->win, (long)a->H * a->W));
-  if (!a->state || !a->durations || !a->scalars) return SDY_ERR_ARG;
-  if (((uintptr_t)a->state & 7) || ((uintptr_t)a->durations & 7) || ((uintptr_t)a->scalars & 3)) return SDY_ERR_ARG;
-  if (a->n_events < 1 || a->n_events > kMaxEvents) return SDY_ERR_ARG;
+  if (!a->state || !a->durations || ((uintptr_t)a->state & 7) || ((uintptr_t)a->durations & 7)) return SDY_ERR_ARG;
   if (a->t0 < 0 || a->t0 > a->win.T) return SDY_ERR_ARG;
   const long plane = (long)a->H * a->W;                                   // <= 2^30
-  for (int v = 0; v < a->win.nvars; ++v) {
-    const unsigned is_map = a->is_map[v] & ((1u << a->n_events) - 1u);
-    if (!is_map) continue;
-    if (!a->maps || ((uintptr_t)a->maps & 3) || a->n_maps < 1 || a->map_first[v] < 0 ||
-        (long)a->map_first[v] + __builtin_popcount(is_map) > (long)a->n_maps)
-      return SDY_ERR_ARG;
-    if ((long)a->n_maps * plane >= (1L << 40)) return SDY_ERR_UNSUPPORTED;
-  }
+  SDY_TRY(sdy_event_thresholds_check(&a->thr, a->win.nvars));
+  SDY_TRY(sdy_event_thresholds_supported(&a->thr, a->win.nvars, plane));
   if (a->win.n0 > kMaxMembers) return SDY_ERR_UNSUPPORTED;
   // the 32-bit LDS words of a row and its 32-bit work items: one launch ends at most rows * W * T spells in a row
   const long rows = sdy_spell_rows(a->win.n0, a->win.n1);                 // <= 65 * 2^31
   // (a lane's item number goes up by kThreads until it leaves the row's items: room for one step past them)
   if (rows >= (1L << 32) || rows * a->W + kThreads > (1L << 32) || rows * a->W * a->win.T >= (1L << 32)) return SDY_ERR_UNSUPPORTED;
   // 64-bit flat indices: rows * plane < 2^62, nvars * E * 4 <= 3072 < 2^12
-  const long E = a->n_events;
+  const long E = a->thr.n_events;
   if (rows * plane >= (1L << 50) || (long)a->win.nvars * E * SDY_SPELL_WORDS * rows * plane >= (1L << 50)) return SDY_ERR_UNSUPPORTED;
   if ((long)a->win.nvars * E * 2 * a->H * SDY_SPELL_BINS >= (1L << 50)) return SDY_ERR_UNSUPPORTED;
   return SDY_OK;
 }
 
 bool vec4(const sdy_event_spell_args* a) {
-  return sdy_window_vec4(&a->win, a->W) && (((long)a->H * a->W) & 3) == 0 && ((uintptr_t)a->maps & 15) == 0 &&
+  return sdy_window_vec4(&a->win, a->W) && (((long)a->H * a->W) & 3) == 0 && sdy_event_thresholds_vec4(&a->thr) &&
          ((uintptr_t)a->state & 15) == 0;
 }
 
-template <int EC>
-void launch(const sdy_event_spell_args& a, bool vec, dim3 grid, hipStream_t stream) {
-  if (vec)
-    hipLaunchKernelGGL((spell_kernel<4, EC>), grid, dim3(kThreads), 0, stream, a);
-  else
-    hipLaunchKernelGGL((spell_kernel<1, EC>), grid, dim3(kThreads), 0, stream, a);
-}
+template <int W4, int EC>
+struct Launch {
+  static void go(const sdy_event_spell_args& a, dim3 grid, hipStream_t stream) {
+    hipLaunchKernelGGL((spell_kernel<W4, EC>), grid, dim3(kThreads), 0, stream, a);
+  }
+};
 
 }  // namespace
 
@@ -217,17 +208,15 @@ extern "C" int sdy_event_spell_accumulate_host(const sdy_event_spell_args* a) {
   SDY_TRY(check(a));
   const sdy_window& w = a->win;
   const long plane = (long)a->H * a->W, rows = sdy_spell_rows(w.n0, w.n1), gen_rows = (long)w.n0 * w.n1;
-  const int E = a->n_events;
+  const int E = a->thr.n_events;
   for (int v = 0; v < w.nvars; ++v)
     for (int e = 0; e < E; ++e) {
-      const bool below = (a->below[v] >> e) & 1u;
-      const bool is_map = (a->is_map[v] >> e) & 1u;
-      const float* map = is_map ? a->maps + (long)sdy_ev_map_plane(a->map_first[v], a->is_map[v], e) * plane : nullptr;
+      const bool below = (a->thr.below[v] >> e) & 1u;
       for (long r = 0; r < rows; ++r) {
         const int side = r < gen_rows ? 0 : 1;
         const float* src = side == 0 ? w.gen[v] + (r / w.n1) * w.gs0 + (r % w.n1) * w.gs1 : w.target[v] + (r - gen_rows) * w.ts1;
         for (long p = 0; p < plane; ++p) {
-          const float c = is_map ? map[p] : a->scalars[v * E + e];
+          const float c = sdy_event_threshold_host(&a->thr, v, e, plane, p);
           unsigned* st[SDY_SPELL_WORDS];
           for (int k = 0; k < SDY_SPELL_WORDS; ++k) st[k] = a->state + sdy_spell_state_at(v, E, e, k, rows, r, plane, p);
           for (long t = a->t0; t < w.T; ++t) {
@@ -244,18 +233,7 @@ extern "C" int sdy_event_spell_accumulate_host(const sdy_event_spell_args* a) {
 extern "C" int sdy_event_spell_accumulate(const sdy_event_spell_args* a, void* stream) {
   SDY_TRY(check(a));
   if (a->win.T - a->t0 == 0) return SDY_OK;        // a window that holds the initial condition only
-  const bool vec = vec4(a);
   const dim3 grid(sdy_grid_cap((unsigned long)a->H, a->win.nvars, kBlocksPerLaunch, kMinBlocksPerVar), a->win.nvars);
-  const hipStream_t s = (hipStream_t)stream;
-  switch (a->n_events) {
-    case 1: launch<1>(*a, vec, grid, s); break;
-    case 2: launch<2>(*a, vec, grid, s); break;
-    case 3: launch<3>(*a, vec, grid, s); break;
-    case 4: launch<4>(*a, vec, grid, s); break;
-    case 5: launch<5>(*a, vec, grid, s); break;
-    case 6: launch<6>(*a, vec, grid, s); break;
-    case 7: launch<7>(*a, vec, grid, s); break;
-    case 8: launch<8>(*a, vec, grid, s); break;
-  }
+  dispatch<Launch>(vec4(a), a->thr.n_events, *a, grid, (hipStream_t)stream);
   return sdy_launch_status();
 }

@@ -1,7 +1,7 @@
 // What the field aggregators that read a window in place share (field_stats.hip, member_mean.hip, rank_hist.hip,
 // event_verif.hip, fss.hip, spells.hip, variability.hip, region_series.hip, member_gram.hip; coarsen.hip takes the grid cap):
-// the 16-byte / 4-byte load helpers, the checks and the alignment test of an sdy_window (include/sdy_amd.h) and the grid cap
-// of a launch that covers all variables.
+// the 16-byte / 4-byte load helpers, the checks and the alignment test of an sdy_window (include/sdy_amd.h), the grid cap
+// of a launch that covers all variables and the lanes that share an accumulator row.
 #pragma once
 #include "common.h"
 
@@ -11,6 +11,21 @@ template <int W>
 __device__ __forceinline__ Vec<W> ld(const float* p) { return *reinterpret_cast<const Vec<W>*>(p); }
 __device__ __forceinline__ float comp(float v, int) { return v; }
 __device__ __forceinline__ float comp(f32x4 v, int c) { return v[c]; }
+
+// A load of W4 floats as (wave-uniform 64-bit base) + (32-bit byte offset per lane), the SADDR form of global_load (see
+// sdy_ld16s, common.h): a member's base is scalar arithmetic, and a thread keeps one offset for the target and every member
+// of a unit instead of one 64-bit address per load in flight.
+typedef float __attribute__((address_space(1))) gfloat;
+template <int W4>
+__device__ __forceinline__ Vec<W4> ld_u(const float* ubase, unsigned off_b);
+template <>
+__device__ __forceinline__ f32x4 ld_u<4>(const float* ubase, unsigned off_b) { return sdy_ld16s(ubase, off_b); }
+template <>
+__device__ __forceinline__ float ld_u<1>(const float* ubase, unsigned off_b) {
+  sdy_gcptr_t b = (sdy_gcptr_t)ubase;
+  asm volatile("" : "+s"(b), "+v"(off_b));
+  return *reinterpret_cast<const gfloat*>(b + off_b);
+}
 
 // everything of a window that bounds an address, for the device and the host entry points alike; plane = the grid points of
 // one time (sdy_window's contract)
@@ -37,4 +52,28 @@ inline bool sdy_window_vec4(const sdy_window* w, long inner) {
 inline unsigned sdy_grid_cap(unsigned long blocks, int nvars, int blocks_per_launch, int min_per_var) {
   const unsigned long cap = blocks_per_launch / nvars > min_per_var ? blocks_per_launch / nvars : min_per_var;
   return (unsigned)(blocks < cap ? blocks : cap);
+}
+
+// Lanes per accumulator row of the kernels whose lane groups own one (rank_hist.hip, event_verif.hip), a power of two in
+// kMinLaneGroup .. 64 (units: the 16-byte or 4-byte loads of one latitude row).  A row of at most 16 units takes one pass of the
+// narrowest group that covers it.  A longer row takes the group of 16, 32 or 64 lanes that leaves the fewest lane slots idle
+// over its passes, the wider one of equals (longer contiguous runs per load): 90 units (360 longitudes) -> 32 lanes x 3
+// passes, 90 of 96 slots busy, where one wave per row has 90 of 128.
+constexpr int kMinLaneGroup = 4;
+inline int lane_group(int units) {
+  if (units <= 16) {
+    int G = kMinLaneGroup;
+    while (G < units) G <<= 1;
+    return G;
+  }
+  int best = 16;
+  long best_slots = 16L * ((units + 15) / 16);
+  for (int G = 32; G <= 64; G <<= 1) {
+    const long slots = (long)G * ((units + G - 1) / G);
+    if (slots <= best_slots) {
+      best = G;
+      best_slots = slots;
+    }
+  }
+  return best;
 }

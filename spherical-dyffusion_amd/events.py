@@ -20,7 +20,7 @@ from typing import Dict, List, NamedTuple, Optional, Sequence
 import torch
 
 from ._lib import SDY_EVENT_MAX, SDY_EVENT_MAX_MEMBERS, SdyEventArgs, check, current_stream, lib
-from .windows import FieldAccumulator, WindowLayout, fill_window, runs, whole_ics_message, window_layouts
+from .windows import FieldAccumulator, WindowLayout, fill_slots, fill_window, runs, whole_ics_message, window_layouts
 
 #: what `EventVerificationAggregator.get_logs` reports per variable and event, in this order
 LOG_METRICS = ("brier_score", "brier_skill_score", "brier_reliability", "brier_resolution", "base_rate", "forecast_rate",
@@ -139,8 +139,7 @@ class _EventLayout(WindowLayout):
 class EventAccumulator(FieldAccumulator):
     """What `EventVerificationAggregator`, `sdy_amd.FractionsSkillAggregator` and `sdy_amd.EventSpellAggregator` share: the
     events of the variables and their thresholds on the device, the row-constant area weights, the slots, and everything a
-    window is checked for before anything changes.  The threshold fields of `SdyEventArgs`, `SdyFssArgs` and
-    `SdyEventSpellArgs` have the same names: `_fill` takes any of them."""
+    window is checked for before anything changes."""
 
     accepts_sample_weights = True      # (to see, and refuse, a ragged share)
 
@@ -201,22 +200,27 @@ class EventAccumulator(FieldAccumulator):
         self._maps = torch.cat(maps).to(device) if maps else None
 
     def _fill(self, a, lay, first: int, last: int, t0: int, i_time_start: int) -> None:
-        """Variables first .. last - 1 of a window (one run: equal extents and event count) into the window, the slots and the
-        thresholds of an argument structure; the accumulator is the caller's."""
+        """Variables first .. last - 1 of a window (one run: equal extents and event count) into the window, the slots (of a
+        structure that has them) and the thresholds of an argument structure; the accumulator is the caller's."""
         fill_window(a.win, lay, first, last)
         l = lay[first]
-        a.H, a.W, a.t0, a.n_events = l.H, l.W, t0, l.n_events
-        a.t_start, a.n_slots, a.pool_times = (0 if self._pool_times else i_time_start), self._n_slots, self._pool_times
-        a.scalars = self._scalars.data_ptr() + 4 * self._scalar_at[first]
+        a.H, a.W = l.H, l.W
+        if hasattr(a, "slots"):
+            fill_slots(a.slots, t0, i_time_start, self._n_slots, self._pool_times)
+        else:
+            a.t0 = t0
+        thr = a.thr
+        thr.n_events = l.n_events
+        thr.scalars = self._scalars.data_ptr() + 4 * self._scalar_at[first]
         n_maps = 0
         for j in range(first, last):
             bits = [(e.below, e.map is not None) for e in self._events[self._names[j]]]
-            a.below[j - first] = sum(1 << i for i, (b, _) in enumerate(bits) if b)
-            a.is_map[j - first] = sum(1 << i for i, (_, m) in enumerate(bits) if m)
-            a.map_first[j - first] = (self._map_at[j] - self._map_at[first]) // (l.H * l.W)      # (a run has one grid)
+            thr.below[j - first] = sum(1 << i for i, (b, _) in enumerate(bits) if b)
+            thr.is_map[j - first] = sum(1 << i for i, (_, m) in enumerate(bits) if m)
+            thr.map_first[j - first] = (self._map_at[j] - self._map_at[first]) // (l.H * l.W)      # (a run has one grid)
             n_maps += sum(m for _, m in bits)
-        a.n_maps = n_maps
-        a.maps = self._maps.data_ptr() + 4 * self._map_at[first] if n_maps else None
+        thr.n_maps = n_maps
+        thr.maps = self._maps.data_ptr() + 4 * self._map_at[first] if n_maps else None
 
     def _begin(self, target_data, gen_data, i_time_start: int, sample_weights):
         """Everything a window is checked for, the accumulators and the thresholds at the first accepted one -> (layouts, t0,

@@ -10,7 +10,7 @@ from typing import Dict, Optional, Sequence
 import torch
 
 from ._lib import SDY_RANK_HIST_MAX_MEMBERS, SdyRankHistArgs, check, current_stream, lib
-from .windows import FieldAccumulator, WindowLayout, fill_window, runs, whole_ics_message, window_layouts
+from .windows import FieldAccumulator, WindowLayout, fill_slots, fill_window, runs, whole_ics_message, window_layouts
 
 
 class RankHistogramAggregator(FieldAccumulator):
@@ -96,8 +96,8 @@ class RankHistogramAggregator(FieldAccumulator):
             for first, last in runs(lay, lambda l: l.extents):
                 a = SdyRankHistArgs()
                 fill_window(a.win, lay, first, last)
-                a.H, a.W, a.t0 = lay[first].H, lay[first].W, t0
-                a.t_start, a.n_slots, a.pool_times = (0 if self._pool_times else i_time_start), self._n_slots, self._pool_times
+                a.H, a.W = lay[first].H, lay[first].W
+                fill_slots(a.slots, t0, i_time_start, self._n_slots, self._pool_times)
                 a.counts, a.ties = self._at("counts", first), self._at("ties", first)
                 check(lib.sdy_rank_hist_accumulate(C.byref(a), current_stream()), "sdy_rank_hist_accumulate")
         for t in range(i_time_start + t0, i_time_start + T):

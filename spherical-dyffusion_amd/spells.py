@@ -267,13 +267,13 @@ def spell_statistics(x: torch.Tensor, threshold, below: bool = False) -> Dict[st
     a = SdyEventSpellArgs()
     a.nvars, a.gen[0], a.target[0] = 1, ptr(x), ptr(x)
     a.n0, a.n1, a.T, a.gs0, a.gs1, a.ts1 = 1, 1, T, 0, 0, 0
-    a.H, a.W, a.t0, a.n_events = H, W, 0, 1
-    a.below[0] = int(bool(below))
+    a.H, a.W, a.t0 = H, W, 0
+    a.thr.n_events, a.thr.below[0] = 1, int(bool(below))
     if thr.dim() == 2:
-        a.is_map[0], a.map_first[0], a.n_maps, a.maps = 1, 0, 1, ptr(thr)
+        a.thr.is_map[0], a.thr.map_first[0], a.thr.n_maps, a.thr.maps = 1, 0, 1, ptr(thr)
     else:
         scalars.fill_(float(thr))
-    a.scalars, a.state, a.durations = ptr(scalars), ptr(state), ptr(durations)
+    a.thr.scalars, a.state, a.durations = ptr(scalars), ptr(state), ptr(durations)
     with torch.cuda.device(x.device):
         check(lib.sdy_event_spell_accumulate(C.byref(a), current_stream()), "sdy_event_spell_accumulate")
     out = state[:, 0].to(torch.float64)

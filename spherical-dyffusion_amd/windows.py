@@ -163,6 +163,12 @@ def fill_window(win: SdyWindow, layouts: Sequence[WindowLayout], first: int, las
     win.n0, win.n1, win.T, win.gs0, win.gs1, win.ts1 = l.n0, l.n1, l.T, l.gs0, l.gs1, l.ts1
 
 
+def fill_slots(slots, t0: int, i_time_start: int, n_slots: int, pool_times: bool) -> None:
+    """Where a window that starts at time `i_time_start` of a run lands, into the `sdy_lead_slots` of an argument structure;
+    t0: its first counted time."""
+    slots.t0, slots.t_start, slots.n_slots, slots.pool_times = t0, (0 if pool_times else i_time_start), n_slots, pool_times
+
+
 def check_same_job(names: Sequence[str], jobs: Sequence[tuple], first_names: Sequence[str], first_jobs: Sequence[tuple],
                    what: str = "sample count") -> None:
     """A later window must hold the first window's variables, in its order, with its `jobs` (per variable what the aggregator

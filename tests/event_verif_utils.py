@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 import rank_hist_utils as ru
-from window_utils import fill_window, vp
+from window_utils import fill_slots, fill_window, vp
 
 TOL = 1e-11
 
@@ -150,28 +150,34 @@ def _runs(case):
         first = last
 
 
+def fill_thresholds(thr, case, names):
+    """The `sdy_event_thresholds` of an argument structure for the variables `names` (equal event count); -> keep-alive list."""
+    E = len(case["events"][names[0]])
+    scalars, maps = np.full((len(names), E), np.nan, np.float32), []
+    for j, k in enumerate(names):
+        thr.map_first[j] = len(maps)
+        for e, (_, direction, c) in enumerate(case["events"][k]):
+            thr.below[j] |= (1 << e) if direction == "below" else 0
+            if isinstance(c, np.ndarray):
+                thr.is_map[j] |= 1 << e
+                maps.append(np.asarray(c, np.float32))
+            else:
+                scalars[j, e] = c
+    maps = np.ascontiguousarray(np.stack(maps)) if maps else None
+    thr.n_events, thr.n_maps = E, (0 if maps is None else len(maps))
+    thr.scalars, thr.maps = vp(scalars), (None if maps is None else vp(maps))
+    return [scalars, maps]
+
+
 def args(case, target, gen, names, t0, t_start, n_slots, pool, acc):
     """SdyEventArgs over contiguous numpy arrays for the variables `names` (equal event count); -> (args, keep-alive list)."""
     from sdy_amd._lib import SdyEventArgs
 
     a = SdyEventArgs()
     keep, (H, W) = fill_window(a.win, target, gen, names)
-    E = len(case["events"][names[0]])
-    scalars, maps = np.full((len(names), E), np.nan, np.float32), []
-    for j, k in enumerate(names):
-        a.map_first[j] = len(maps)
-        for e, (_, direction, thr) in enumerate(case["events"][k]):
-            a.below[j] |= (1 << e) if direction == "below" else 0
-            if isinstance(thr, np.ndarray):
-                a.is_map[j] |= 1 << e
-                maps.append(np.asarray(thr, np.float32))
-            else:
-                scalars[j, e] = thr
-    maps = np.ascontiguousarray(np.stack(maps)) if maps else None
-    a.H, a.W, a.t0, a.t_start, a.n_slots, a.pool_times, a.n_events = H, W, t0, t_start, n_slots, int(pool), E
-    a.n_maps = 0 if maps is None else len(maps)
-    a.scalars, a.maps, a.acc = vp(scalars), (None if maps is None else vp(maps)), vp(acc)
-    return a, keep + [scalars, maps, acc]
+    a.H, a.W, a.acc = H, W, vp(acc)
+    fill_slots(a.slots, t0, t_start, n_slots, pool)
+    return a, keep + fill_thresholds(a.thr, case, names) + [acc]
 
 
 def host(case, pool=False, windows=None):

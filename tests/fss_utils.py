@@ -12,7 +12,8 @@ import ctypes as C
 import numpy as np
 
 import rank_hist_utils as ru
-from window_utils import fill_window, vp
+from event_verif_utils import fill_thresholds
+from window_utils import fill_slots, fill_window, vp
 
 TOL = 1e-12
 TERMS = ("count", "sum_k", "sum_o", "sum_kk", "sum_ko", "sum_oo")
@@ -208,27 +209,15 @@ def args(case, target, gen, names, t0, t_start, n_slots, pool, acc, ws=None):
 
     a = SdyFssArgs()
     keep, (H, W) = fill_window(a.win, target, gen, names)
-    E = len(case["events"][names[0]])
-    scalars, maps = np.full((len(names), E), np.nan, np.float32), []
-    for j, k in enumerate(names):
-        a.map_first[j] = len(maps)
-        for e, (_, direction, thr) in enumerate(case["events"][k]):
-            a.below[j] |= (1 << e) if direction == "below" else 0
-            if isinstance(thr, np.ndarray):
-                a.is_map[j] |= 1 << e
-                maps.append(np.asarray(thr, np.float32))
-            else:
-                scalars[j, e] = thr
-    maps = np.ascontiguousarray(np.stack(maps)) if maps else None
-    a.H, a.W, a.t0, a.t_start, a.n_slots, a.pool_times, a.n_events = H, W, t0, t_start, n_slots, int(pool), E
-    a.n_maps = 0 if maps is None else len(maps)
-    a.scalars, a.maps, a.acc = vp(scalars), (None if maps is None else vp(maps)), vp(acc)
+    a.H, a.W, a.acc = H, W, vp(acc)
+    fill_slots(a.slots, t0, t_start, n_slots, pool)
+    keep += fill_thresholds(a.thr, case, names)
     a.n_radii = len(case["radii"])
     for j, r in enumerate(case["radii"]):
         a.radii[j] = r
     if ws is not None:
         a.ws, a.ws_bytes = vp(ws), ws.nbytes
-    return a, keep + [scalars, maps, acc, ws]
+    return a, keep + [acc, ws]
 
 
 def host(case, pool=False, windows=None):

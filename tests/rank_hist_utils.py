@@ -10,7 +10,7 @@ import ctypes as C
 
 import numpy as np
 
-from window_utils import fill_window, vp
+from window_utils import fill_slots, fill_window, vp
 
 REL = 1e-12
 
@@ -110,7 +110,8 @@ def args(target, gen, names, t0, t_start, n_slots, pool, counts, ties):
 
     a = SdyRankHistArgs()
     keep, (H, W) = fill_window(a.win, target, gen, names)
-    a.H, a.W, a.t0, a.t_start, a.n_slots, a.pool_times = H, W, t0, t_start, n_slots, int(pool)
+    a.H, a.W = H, W
+    fill_slots(a.slots, t0, t_start, n_slots, pool)
     a.counts, a.ties = vp(counts), vp(ties)
     return a, keep
 

@@ -15,6 +15,7 @@ import ctypes as C
 
 import numpy as np
 
+from event_verif_utils import fill_thresholds
 from window_utils import fill_window, vp
 
 SMALL = ("m5_b2_6x8", "m5_b2_6x10", "m25_b1_4x360", "m1_b2_6x8", "nan_m5_b2_6x8", "e8_m5_b1_6x8", "known_m5_b2_6x8")
@@ -218,22 +219,8 @@ def args(case, target, gen, names, t0, state, durations):
 
     a = SdyEventSpellArgs()
     keep, (H, W) = fill_window(a.win, target, gen, names)
-    E = len(case["events"][names[0]])
-    scalars, maps = np.full((len(names), E), np.nan, np.float32), []
-    for j, k in enumerate(names):
-        a.map_first[j] = len(maps)
-        for e, (_, direction, thr) in enumerate(case["events"][k]):
-            a.below[j] |= (1 << e) if direction == "below" else 0
-            if isinstance(thr, np.ndarray):
-                a.is_map[j] |= 1 << e
-                maps.append(np.asarray(thr, np.float32))
-            else:
-                scalars[j, e] = thr
-    maps = np.ascontiguousarray(np.stack(maps)) if maps else None
-    a.H, a.W, a.t0, a.n_events = H, W, t0, E
-    a.n_maps = 0 if maps is None else len(maps)
-    a.scalars, a.maps, a.state, a.durations = vp(scalars), (None if maps is None else vp(maps)), vp(state), vp(durations)
-    return a, keep + [scalars, maps, state, durations]
+    a.H, a.W, a.t0, a.state, a.durations = H, W, t0, vp(state), vp(durations)
+    return a, keep + fill_thresholds(a.thr, case, names) + [state, durations]
 
 
 def host(case, windows=None):

@@ -1,5 +1,5 @@
-"""The numpy counterpart of sdy_amd.windows.fill_window, for the _host twins: shared by tests/field_stats_utils.py and
-tests/member_mean_utils.py."""
+"""The numpy counterparts of sdy_amd.windows.fill_window and fill_slots, for the _host twins: shared by the *_utils.py of the
+aggregators that read a window in place."""
 import ctypes as C
 
 import numpy as np
@@ -22,3 +22,8 @@ def fill_window(win, target, gen, names):
     win.n0, win.n1, win.T = (g.shape[0] if g.ndim == 5 else 1), S, T
     win.gs0, win.gs1, win.ts1 = (S * T * H * W if g.ndim == 5 else 0), T * H * W, T * H * W
     return keep, (H, W)
+
+
+def fill_slots(slots, t0, t_start, n_slots, pool):
+    """The `sdy_lead_slots` of an argument structure."""
+    slots.t0, slots.t_start, slots.n_slots, slots.pool_times = t0, t_start, n_slots, int(pool)
