@@ -899,23 +899,44 @@ int sdy_member_map_stats(const sdy_member_stats_args* args, void* stream);
 int sdy_member_map_stats_host(const sdy_member_stats_args* args);
 size_t sdy_member_stats_workspace_bytes(int nvars, int M, int n1, int HW);   /* 0 for arguments outside the supported range */
 
-/* Per-degree power spectra of generated, target and error fields (no counterpart in the reference, whose only measure of
- * blurring is weighted_grad_mag_percent_diff): one launch adds ONE window of all listed variables to float64 accumulators that
- * stay on the device.  For the coefficients a[l][m] of one field (RealSHT: norm "ortho", csphase, m <= l)
- *   P(l) = |a[l,0]|^2 + 2 * sum_{m = 1 .. min(l, mtr - 1)} |a[l,m]|^2,   l < lmax
- * so that sum_l P(l) is the integral of the squared field over the sphere for a band-limited field on the Legendre-Gauss grid.
- *   gen, target: dev float, coefficients in the internal layout above as sdy_legendre_fwd writes them for ONE image (B = 1):
- *              Cs[l][m][ri][field], m < mtr, gen_fields / target_fields fields per plane (the C of the transform, padding
- *              included).  Entries with m > l and fields that the decoding below does not name are never read.
- *              gen field of (variable v, member i0, sample i1, window time t) = v*gen_var_stride + t*gen_time_stride + i0*n1 + i1
+/* The rows of one window in the coefficient tensors of the two sides, and where their times land: embedded as `rows` in
+ * sdy_spectrum_args and sdy_vector_spectrum_args below, checked by one function (csrc/coef_rows.h).  A coefficient tensor is
+ * in the internal layout above as sdy_legendre_fwd / sdy_vector_legendre_fwd write it for ONE image (B = 1):
+ * Cs[l][m][ri][field], m < mtr, gen_fields / target_fields fields per plane (the C of the transform, padding included).
+ * Entries with m > l and fields that the decoding does not name are never read.
+ *   field decoding: gen field of (variable v, member i0, sample i1, window time t) = v*gen_var_stride + t*gen_time_stride + i0*n1 + i1
  *              target field of (v, i1, t)                                     = v*target_var_stride + t*target_time_stride + i1
  *              (the rows of one (variable, time) are consecutive fields: a run of 4 x rows bytes per plane)
  *   gen_scale, target_scale: dev float [gen_fields] / [target_fields], or NULL for 1: what a field's stored coefficients are
  *              to be multiplied with, in float64 before anything else (exact for a power of two).  The split-fp16 Legendre
  *              analysis stages SDY_ACT_SX x |Xf| as fp16, so a field in physical units (a pressure in Pa) has to be handed to
  *              sdy_rfft_lon scaled down (its per-field a, with d = 0) and its scale undone here.
- *   accumulators: dev double, contiguous (nvars, n_timesteps, lmax) each, zeroed by the caller before the first call; window
- *              time t lands at time t_start + t.  gen_power and target_power are required, err_power may be NULL:
+ *   times:     the accumulators of the embedding structure are dev double, contiguous (nvars, n_timesteps, lmax) each, zeroed
+ *              by the caller before the first call; window time t < T lands at time t_start + t.
+ * SDY_ERR_ARG: a non-positive lmax, mtr, field count, nvars, n0, n1, T or n_timesteps; mtr > lmax; a negative stride;
+ * t_start < 0; t_start + T > n_timesteps; a buffer whose field count does not reach the last row of the last time of the last
+ * variable.
+ * SDY_ERR_UNSUPPORTED: n0*n1 >= 2^31 - 256 (row numbers are 32-bit), T or nvars > 65535 (grid extents), lmax*mtr*2*fields >=
+ * 2^40 for either side, nvars*n_timesteps*lmax >= 2^40 (flat indices are 64-bit). */
+typedef struct sdy_coef_rows {
+  const float* gen_scale;
+  const float* target_scale;
+  int lmax, mtr;
+  int gen_fields, target_fields;
+  int gen_var_stride, gen_time_stride;
+  int target_var_stride, target_time_stride;
+  int nvars, n0, n1, T;
+  int t_start, n_timesteps;
+} sdy_coef_rows;            /* 72 bytes */
+
+/* Per-degree power spectra of generated, target and error fields (no counterpart in the reference, whose only measure of
+ * blurring is weighted_grad_mag_percent_diff): one launch adds ONE window of all listed variables to float64 accumulators that
+ * stay on the device.  For the coefficients a[l][m] of one field (RealSHT: norm "ortho", csphase, m <= l)
+ *   P(l) = |a[l,0]|^2 + 2 * sum_{m = 1 .. min(l, mtr - 1)} |a[l,m]|^2,   l < lmax
+ * so that sum_l P(l) is the integral of the squared field over the sphere for a band-limited field on the Legendre-Gauss grid.
+ *   gen, target: dev float, the coefficients of the two sides as sdy_legendre_fwd writes them (see sdy_coef_rows).
+ *   rows:      see sdy_coef_rows: the field decoding, the scales, and where times land.
+ *   accumulators: see sdy_coef_rows.  gen_power and target_power are required, err_power may be NULL:
  *                gen_power    += mean over the n0*n1 generated rows of P of the row
  *                target_power += mean over the n1 target rows of P of the row
  *                err_power    += mean over the n0*n1 rows of P of (gen row (i0, i1) - target row i1), from the coefficient
@@ -926,24 +947,14 @@ size_t sdy_member_stats_workspace_bytes(int nvars, int M, int n1, int HW);   /* 
  * calls that touch the same times must be ordered on a stream.  A row's P(l) depends on its own coefficients only, whatever
  * else the call holds; device and host twin give the same bits.  16-byte loads of a buffer whose pointer is 16-byte aligned
  * and whose field count and two strides are multiples of 4; 4-byte loads otherwise (same values).
- * SDY_ERR_ARG, before anything is launched: NULL args / gen / target / gen_power / target_power; a non-positive lmax, mtr,
- * field count, nvars, n0, n1, T or n_timesteps; mtr > lmax; a negative stride; t_start < 0; t_start + T > n_timesteps; a
- * buffer whose field count does not reach the last row of the last time of the last variable.
- * SDY_ERR_UNSUPPORTED: n0*n1 >= 2^31 - 256 (row numbers are 32-bit), T or nvars > 65535 (grid extents), lmax*mtr*2*fields >=
- * 2^40 for either buffer, nvars*n_timesteps*lmax >= 2^40 (flat indices are 64-bit).
+ * SDY_ERR_ARG, before anything is launched: NULL args / gen / target / gen_power / target_power; what sdy_coef_rows refuses.
+ * SDY_ERR_UNSUPPORTED: what sdy_coef_rows refuses.
  * The _host twin: the same structure with HOST pointers and the same checks; the arithmetic is the header the kernel compiles
  * (csrc/spectrum.h), so the semantics can be pinned without a device. */
 typedef struct sdy_spectrum_args {
   const float* gen;
   const float* target;
-  const float* gen_scale;
-  const float* target_scale;
-  int lmax, mtr;
-  int gen_fields, target_fields;
-  int gen_var_stride, gen_time_stride;
-  int target_var_stride, target_time_stride;
-  int nvars, n0, n1, T;
-  int t_start, n_timesteps;
+  sdy_coef_rows rows;
   double *gen_power, *target_power, *err_power;
 } sdy_spectrum_args;
 int sdy_degree_power(const sdy_spectrum_args* args, void* stream);
@@ -982,14 +993,16 @@ void sdy_vsht_plan_destroy(sdy_vsht_plan* vplan);
  * SDY_ERR_ALIGN for an odd C. */
 int sdy_vector_legendre_fwd(const sdy_vsht_plan* vplan, const float* Xf, float* Cs_d, float* Cs_m, int B, int C, void* stream);
 
-/* One launch adds ONE window of all listed wind pairs to float64 accumulators that stay on the device; everything is as for
- * sdy_degree_power above except what follows.
+/* One launch adds ONE window of all listed wind pairs to float64 accumulators that stay on the device.
  *   struct_size: sizeof of this structure.  It stands in for the sdy_abi_check handshake, whose list this structure is not
- *              part of: a call with another value is refused (SDY_ERR_ARG).
+ *              part of: a call with another value is refused (SDY_ERR_ARG).  The size did not change when `rows` replaced
+ *              the loose fields (168 bytes before and after, but the v offsets moved from bytes 72 / 76 to 112 / 116 and the
+ *              ten integers behind them up by 8), so struct_size does NOT tell a caller compiled against the earlier header
+ *              from a current one: recompile C callers with this header.
  *   gen_d, gen_m, target_d, target_m: dev float, Cs_d and Cs_m of sdy_vector_legendre_fwd for ONE image per side.  The u rows
- *              and the v rows of a side are two runs of one field batch: the field decoding of sdy_degree_power names the u
+ *              and the v rows of a side are two runs of one field batch: the field decoding of sdy_coef_rows names the u
  *              field of a row (nvars counts pairs), and its v field lies gen_v_offset / target_v_offset fields further.
- *   gen_scale, target_scale: as above, per field (u and v fields have their own).
+ *   rows:      see sdy_coef_rows; gen_scale and target_scale per field (u and v fields have their own).
  *   accumulators: dev double, contiguous (nvars, n_timesteps, lmax) each.  gen_rot, gen_div, target_rot, target_div are
  *              required; err_rot and err_div are both given or both NULL.  Each adds the mean over the rows of E_rot / E_div
  *              of the row; the error of generated row (i0, i1) is taken of s_gen - s_target and t_gen - t_target against
@@ -999,21 +1012,15 @@ int sdy_vector_legendre_fwd(const sdy_vsht_plan* vplan, const float* Xf, float* 
  * sdy_degree_power (csrc/vector_spectrum.h, csrc/spectrum.h).  Device and host twin give the same bits.  16-byte loads where
  * the two pointers of a side are 16-byte aligned and its field count, v offset and two strides are multiples of 4 (a group's
  * last quad of fields is then loaded whole and the fields past its last row are discarded: they lie inside the plane).
- * SDY_ERR_ARG additionally for a negative v offset or one that carries the last row past its buffer; SDY_ERR_UNSUPPORTED as for
- * sdy_degree_power.  The _host twin takes HOST pointers. */
+ * SDY_ERR_ARG, before anything is launched: NULL args, another struct_size, a NULL coefficient tensor or required
+ * accumulator, one error accumulator without the other; what sdy_coef_rows refuses; a negative v offset or one that carries the
+ * last row past its buffer.  SDY_ERR_UNSUPPORTED: what sdy_coef_rows refuses.  The _host twin takes HOST pointers. */
 typedef struct sdy_vector_spectrum_args sdy_vector_spectrum_args;
 struct sdy_vector_spectrum_args {
   size_t struct_size;
   const float *gen_d, *gen_m, *target_d, *target_m;
-  const float* gen_scale;
-  const float* target_scale;
-  int lmax, mtr;
-  int gen_fields, target_fields;
+  sdy_coef_rows rows;
   int gen_v_offset, target_v_offset;
-  int gen_var_stride, gen_time_stride;
-  int target_var_stride, target_time_stride;
-  int nvars, n0, n1, T;
-  int t_start, n_timesteps;
   double *gen_rot, *gen_div, *target_rot, *target_div, *err_rot, *err_div;
 };
 int sdy_vector_degree_power(const sdy_vector_spectrum_args* args, void* stream);

@@ -278,15 +278,25 @@ class SdyMemberStatsArgs(C.Structure):
     ]
 
 
-class SdySpectrumArgs(C.Structure):
+class SdyCoefRows(C.Structure):
+    """sdy_coef_rows: embedded as `rows` in the two spectrum structures below (filled by `spectrum._fill_rows`); its fields also
+    read and write as the embedding structure's own (`a.lmax` is `a.rows.lmax`)."""
     _fields_ = [
-        ("gen", C.c_void_p), ("target", C.c_void_p), ("gen_scale", C.c_void_p), ("target_scale", C.c_void_p),
+        ("gen_scale", C.c_void_p), ("target_scale", C.c_void_p),
         ("lmax", C.c_int), ("mtr", C.c_int),
         ("gen_fields", C.c_int), ("target_fields", C.c_int),
         ("gen_var_stride", C.c_int), ("gen_time_stride", C.c_int),
         ("target_var_stride", C.c_int), ("target_time_stride", C.c_int),
         ("nvars", C.c_int), ("n0", C.c_int), ("n1", C.c_int), ("T", C.c_int),
         ("t_start", C.c_int), ("n_timesteps", C.c_int),
+    ]
+
+
+class SdySpectrumArgs(C.Structure):
+    _anonymous_ = ("rows",)
+    _fields_ = [
+        ("gen", C.c_void_p), ("target", C.c_void_p),
+        ("rows", SdyCoefRows),
         ("gen_power", C.c_void_p), ("target_power", C.c_void_p), ("err_power", C.c_void_p),
     ]
 
@@ -302,17 +312,12 @@ class _SizedStructure(C.Structure):
 
 class SdyVectorSpectrumArgs(_SizedStructure):
     """`sdy_vector_spectrum_args`."""
+    _anonymous_ = ("rows",)
     _fields_ = [
         ("struct_size", C.c_size_t),
         ("gen_d", C.c_void_p), ("gen_m", C.c_void_p), ("target_d", C.c_void_p), ("target_m", C.c_void_p),
-        ("gen_scale", C.c_void_p), ("target_scale", C.c_void_p),
-        ("lmax", C.c_int), ("mtr", C.c_int),
-        ("gen_fields", C.c_int), ("target_fields", C.c_int),
+        ("rows", SdyCoefRows),
         ("gen_v_offset", C.c_int), ("target_v_offset", C.c_int),
-        ("gen_var_stride", C.c_int), ("gen_time_stride", C.c_int),
-        ("target_var_stride", C.c_int), ("target_time_stride", C.c_int),
-        ("nvars", C.c_int), ("n0", C.c_int), ("n1", C.c_int), ("T", C.c_int),
-        ("t_start", C.c_int), ("n_timesteps", C.c_int),
         ("gen_rot", C.c_void_p), ("gen_div", C.c_void_p), ("target_rot", C.c_void_p), ("target_div", C.c_void_p),
         ("err_rot", C.c_void_p), ("err_div", C.c_void_p),
     ]

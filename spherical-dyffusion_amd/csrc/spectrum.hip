@@ -12,16 +12,14 @@
 // order of a row's sum (orders ascending) is what ties a lane to a row; a wave that spans several times of a plane would fill
 // its lanes without changing that order and is the next step.
 #include "common.h"
+#include "coef_rows.h"
 #include "spectrum.h"
 
 namespace {
 
-constexpr int kLanes = SDY_SP_SLOTS / 4;   // one wave
-static_assert(kLanes == 64, "a wave holds the slots, four per lane");
-
-struct Quad { float v[4]; };
-
-// rows r0 .. r0 + 3 of a run that starts at p[0] and holds `rows` rows; rows past the end read as 0 and are never loaded
+// rows r0 .. r0 + 3 of a run that starts at p[0] and holds `rows` rows; rows past the end read as 0 and are never loaded.
+// (vector_spectrum.hip has a branch-free ld_quad of its own: there a branch per row multiplied the kernel's code past the
+// instruction cache; here the branch keeps a quad past the end from being loaded at all.)
 template <bool VEC>
 __device__ __forceinline__ Quad ld_quad(const float* p, int r0, int rows) {
   Quad q;
@@ -35,24 +33,19 @@ __device__ __forceinline__ Quad ld_quad(const float* p, int r0, int rows) {
   return q;
 }
 
-__device__ __forceinline__ double wave_butterfly(double x) {
-#pragma clang fp contract(off)
-  for (int m = 1; m < kLanes; m <<= 1) x = x + __shfl_xor(x, m);
-  return x;
-}
-
 // blockIdx = (degree l, window time t, variable v); 64 threads
 template <bool VEC_G, bool VEC_T, bool ERR>
 __global__ __launch_bounds__(kLanes) void degree_power_kernel(const sdy_spectrum_args a) {
   const int l = blockIdx.x, t = blockIdx.y, v = blockIdx.z, lane = threadIdx.x;
-  const int mlast = l < a.mtr - 1 ? l : a.mtr - 1;
-  const int R = a.n0 * a.n1, n1 = a.n1;
-  const long Fg = a.gen_fields, Ft = a.target_fields;
-  // first field of the element's rows (entry point: every row's field is inside its buffer), and the planes of (l, m = 0)
-  const long gf0 = (long)v * a.gen_var_stride + (long)t * a.gen_time_stride;
-  const long tf0 = (long)v * a.target_var_stride + (long)t * a.target_time_stride;
-  const float* g = a.gen + (long)l * a.mtr * 2 * Fg + gf0;
-  const float* tg = a.target + (long)l * a.mtr * 2 * Ft + tf0;
+  // sdy_coef_rows_element(a.rows, v, t, l), spelled out: with the helper, in every form tried, the compiler orders the loads of
+  // the kernel's arguments differently and the kernel comes out as other code than it had before the descriptor
+  const int mlast = l < a.rows.mtr - 1 ? l : a.rows.mtr - 1;
+  const int R = a.rows.n0 * a.rows.n1, n1 = a.rows.n1;
+  const long Fg = a.rows.gen_fields, Ft = a.rows.target_fields;
+  const long gf0 = (long)v * a.rows.gen_var_stride + (long)t * a.rows.gen_time_stride;
+  const long tf0 = (long)v * a.rows.target_var_stride + (long)t * a.rows.target_time_stride;
+  const float* g = a.gen + (long)l * a.rows.mtr * 2 * Fg + gf0;
+  const float* tg = a.target + (long)l * a.rows.mtr * 2 * Ft + tf0;
 
   double gs[4] = {0.0, 0.0, 0.0, 0.0}, es[4] = {0.0, 0.0, 0.0, 0.0};
   for (int r0 = 4 * lane; r0 < R; r0 += SDY_SP_SLOTS) {
@@ -61,8 +54,8 @@ __global__ __launch_bounds__(kLanes) void degree_power_kernel(const sdy_spectrum
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       i1[c] = (r0 + c) % n1;
-      gsc[c] = (a.gen_scale && r0 + c < R) ? (double)a.gen_scale[gf0 + r0 + c] : 1.0;
-      tsc[c] = (ERR && a.target_scale) ? (double)a.target_scale[tf0 + i1[c]] : 1.0;
+      gsc[c] = (a.rows.gen_scale && r0 + c < R) ? (double)a.rows.gen_scale[gf0 + r0 + c] : 1.0;
+      tsc[c] = (ERR && a.rows.target_scale) ? (double)a.rows.target_scale[tf0 + i1[c]] : 1.0;
     }
     double p[4] = {0.0, 0.0, 0.0, 0.0}, e[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll 2
@@ -88,7 +81,7 @@ __global__ __launch_bounds__(kLanes) void degree_power_kernel(const sdy_spectrum
   for (int r0 = 4 * lane; r0 < n1; r0 += SDY_SP_SLOTS) {
     double p[4] = {0.0, 0.0, 0.0, 0.0}, tsc[4];
 #pragma unroll
-    for (int c = 0; c < 4; ++c) tsc[c] = (a.target_scale && r0 + c < n1) ? (double)a.target_scale[tf0 + r0 + c] : 1.0;
+    for (int c = 0; c < 4; ++c) tsc[c] = (a.rows.target_scale && r0 + c < n1) ? (double)a.rows.target_scale[tf0 + r0 + c] : 1.0;
 #pragma unroll 2
     for (int m = 0; m <= mlast; ++m) {
       const Quad re = ld_quad<VEC_T>(tg + (long)(2 * m) * Ft, r0, n1);
@@ -105,105 +98,71 @@ __global__ __launch_bounds__(kLanes) void degree_power_kernel(const sdy_spectrum
   double esum = 0.0;
   if (ERR) esum = wave_butterfly(sdy_sp_fold4(es[0], es[1], es[2], es[3]));
   if (lane == 0) {
-    // accumulator element: variable v < nvars, time t_start + t < n_timesteps (entry point), degree l < lmax
-    const long at = ((long)v * a.n_timesteps + (a.t_start + (long)t)) * a.lmax + l;
+    const long at = ((long)v * a.rows.n_timesteps + (a.rows.t_start + (long)t)) * a.rows.lmax + l;   // the element's `at`
     a.gen_power[at] += sdy_sp_mean(gsum, R);
     a.target_power[at] += sdy_sp_mean(tsum, n1);
     if (ERR) a.err_power[at] += sdy_sp_mean(esum, R);
   }
 }
 
-// everything that bounds an address or an index, for the device and the host entry points alike
+template <bool VEC_G, bool VEC_T, bool ERR>
+struct Launch {
+  static void go(const sdy_spectrum_args& a, dim3 grid, hipStream_t s) {
+    hipLaunchKernelGGL((degree_power_kernel<VEC_G, VEC_T, ERR>), grid, dim3(kLanes), 0, s, a);
+  }
+};
+
+// the entry points' own checks in front of the descriptor's, for the device and the host entry points alike
 int check_spectrum(const sdy_spectrum_args* a) {
   if (!a) return SDY_ERR_ARG;
   if (!a->gen || !a->target || !a->gen_power || !a->target_power) return SDY_ERR_ARG;
-  if (a->lmax < 1 || a->mtr < 1 || a->gen_fields < 1 || a->target_fields < 1) return SDY_ERR_ARG;
-  if (a->nvars < 1 || a->n0 < 1 || a->n1 < 1 || a->T < 1 || a->n_timesteps < 1) return SDY_ERR_ARG;
-  if (a->mtr > a->lmax) return SDY_ERR_ARG;                 // mtr = min(mmax, lmax) of the plan that wrote the coefficients
-  if (a->gen_var_stride < 0 || a->gen_time_stride < 0 || a->target_var_stride < 0 || a->target_time_stride < 0)
-    return SDY_ERR_ARG;
-  // the time offset into the accumulators: window times t_start .. t_start + T - 1 must all exist (in 64 bits: no wrap)
-  if (a->t_start < 0 || (long)a->t_start + (long)a->T > (long)a->n_timesteps) return SDY_ERR_ARG;
-  // 32-bit row numbers, 16-bit grid extents for times and variables; flat indices are 64-bit
-  if ((long)a->n0 * a->n1 >= (1L << 31) - SDY_SP_SLOTS) return SDY_ERR_UNSUPPORTED;
-  if (a->T > 65535 || a->nvars > 65535) return SDY_ERR_UNSUPPORTED;
-  const long cs_rows = (long)a->lmax * a->mtr * 2;
-  if (cs_rows * a->gen_fields >= (1L << 40) || cs_rows * a->target_fields >= (1L << 40)) return SDY_ERR_UNSUPPORTED;
-  if ((long)a->nvars * a->n_timesteps >= (1L << 40) / a->lmax) return SDY_ERR_UNSUPPORTED;
-  // the last row of the last time of the last variable must be a field of its buffer
-  const long R = (long)a->n0 * a->n1;
-  const long g_last = (long)(a->nvars - 1) * a->gen_var_stride + (long)(a->T - 1) * a->gen_time_stride + R - 1;
-  const long t_last = (long)(a->nvars - 1) * a->target_var_stride + (long)(a->T - 1) * a->target_time_stride + a->n1 - 1;
-  if (g_last >= a->gen_fields || t_last >= a->target_fields) return SDY_ERR_ARG;
-  return SDY_OK;
-}
-
-bool aligned16(const float* p, int fields, int var_stride, int time_stride) {
-  return ((uintptr_t)p & 15) == 0 && ((fields | var_stride | time_stride) & 3) == 0;
-}
-
-template <bool VEC_G, bool VEC_T>
-void launch(const sdy_spectrum_args* a, hipStream_t s) {
-  const dim3 grid(a->lmax, a->T, a->nvars);
-  if (a->err_power)
-    hipLaunchKernelGGL((degree_power_kernel<VEC_G, VEC_T, true>), grid, dim3(kLanes), 0, s, *a);
-  else
-    hipLaunchKernelGGL((degree_power_kernel<VEC_G, VEC_T, false>), grid, dim3(kLanes), 0, s, *a);
+  return sdy_coef_rows_check(&a->rows, 0, 0);
 }
 
 }  // namespace
 
 extern "C" int sdy_degree_power_host(const sdy_spectrum_args* a) {
   SDY_TRY(check_spectrum(a));
-  const long Fg = a->gen_fields, Ft = a->target_fields;
-  const int R = a->n0 * a->n1, n1 = a->n1;
+  const sdy_coef_rows& r = a->rows;
+  const long Fg = r.gen_fields, Ft = r.target_fields;
+  const int R = r.n0 * r.n1, n1 = r.n1;
   double gs[SDY_SP_SLOTS], ts[SDY_SP_SLOTS], es[SDY_SP_SLOTS];
-  for (int v = 0; v < a->nvars; ++v)
-    for (int t = 0; t < a->T; ++t)
-      for (int l = 0; l < a->lmax; ++l) {
-        const int mlast = l < a->mtr - 1 ? l : a->mtr - 1;
-        const long gf0 = (long)v * a->gen_var_stride + (long)t * a->gen_time_stride;
-        const long tf0 = (long)v * a->target_var_stride + (long)t * a->target_time_stride;
-        const float* g = a->gen + (long)l * a->mtr * 2 * Fg + gf0;
-        const float* tg = a->target + (long)l * a->mtr * 2 * Ft + tf0;
-        for (int s = 0; s < SDY_SP_SLOTS; ++s) gs[s] = ts[s] = es[s] = 0.0;
-        for (int r = 0; r < R; ++r) {
-          const int i1 = r % n1;
-          const double gsc = a->gen_scale ? (double)a->gen_scale[gf0 + r] : 1.0;
-          const double tsc = a->target_scale ? (double)a->target_scale[tf0 + i1] : 1.0;
-          double p = 0.0, e = 0.0;
-          for (int m = 0; m <= mlast; ++m) {
-            const float re = g[(long)(2 * m) * Fg + r], im = g[(long)(2 * m + 1) * Fg + r];
-            p = sdy_sp_add(p, re, im, gsc, m);
-            if (a->err_power)
-              e = sdy_sp_add_err(e, re, im, gsc, tg[(long)(2 * m) * Ft + i1], tg[(long)(2 * m + 1) * Ft + i1], tsc, m);
-          }
-          gs[r % SDY_SP_SLOTS] += p;
-          es[r % SDY_SP_SLOTS] += e;
-        }
-        for (int r = 0; r < n1; ++r) {
-          const double tsc = a->target_scale ? (double)a->target_scale[tf0 + r] : 1.0;
-          double p = 0.0;
-          for (int m = 0; m <= mlast; ++m)
-            p = sdy_sp_add(p, tg[(long)(2 * m) * Ft + r], tg[(long)(2 * m + 1) * Ft + r], tsc, m);
-          ts[r % SDY_SP_SLOTS] += p;
-        }
-        const long at = ((long)v * a->n_timesteps + (a->t_start + (long)t)) * a->lmax + l;
-        a->gen_power[at] += sdy_sp_mean(sdy_sp_fold_slots(gs), R);
-        a->target_power[at] += sdy_sp_mean(sdy_sp_fold_slots(ts), n1);
-        if (a->err_power) a->err_power[at] += sdy_sp_mean(sdy_sp_fold_slots(es), R);
+  sdy_coef_rows_walk(r, [&](const sdy_coef_element el) {
+    const float *g = a->gen + el.gl, *tg = a->target + el.tl;
+    for (int s = 0; s < SDY_SP_SLOTS; ++s) gs[s] = ts[s] = es[s] = 0.0;
+    for (int row = 0; row < R; ++row) {
+      const int i1 = row % n1;
+      const double gsc = r.gen_scale ? (double)r.gen_scale[el.gf0 + row] : 1.0;
+      const double tsc = r.target_scale ? (double)r.target_scale[el.tf0 + i1] : 1.0;
+      double p = 0.0, e = 0.0;
+      for (int m = 0; m <= el.mlast; ++m) {
+        const float re = g[(long)(2 * m) * Fg + row], im = g[(long)(2 * m + 1) * Fg + row];
+        p = sdy_sp_add(p, re, im, gsc, m);
+        if (a->err_power)
+          e = sdy_sp_add_err(e, re, im, gsc, tg[(long)(2 * m) * Ft + i1], tg[(long)(2 * m + 1) * Ft + i1], tsc, m);
       }
+      gs[row % SDY_SP_SLOTS] += p;
+      es[row % SDY_SP_SLOTS] += e;
+    }
+    for (int row = 0; row < n1; ++row) {
+      const double tsc = r.target_scale ? (double)r.target_scale[el.tf0 + row] : 1.0;
+      double p = 0.0;
+      for (int m = 0; m <= el.mlast; ++m)
+        p = sdy_sp_add(p, tg[(long)(2 * m) * Ft + row], tg[(long)(2 * m + 1) * Ft + row], tsc, m);
+      ts[row % SDY_SP_SLOTS] += p;
+    }
+    sdy_coef_rows_add(a->gen_power, el.at, gs, R);
+    sdy_coef_rows_add(a->target_power, el.at, ts, n1);
+    if (a->err_power) sdy_coef_rows_add(a->err_power, el.at, es, R);
+  });
   return SDY_OK;
 }
 
 extern "C" int sdy_degree_power(const sdy_spectrum_args* a, void* stream) {
   SDY_TRY(check_spectrum(a));
-  const bool vg = aligned16(a->gen, a->gen_fields, a->gen_var_stride, a->gen_time_stride);
-  const bool vt = aligned16(a->target, a->target_fields, a->target_var_stride, a->target_time_stride);
-  const hipStream_t s = (hipStream_t)stream;
-  if (vg && vt) launch<true, true>(a, s);
-  else if (vg) launch<true, false>(a, s);
-  else if (vt) launch<false, true>(a, s);
-  else launch<false, false>(a, s);
+  const sdy_coef_rows& r = a->rows;
+  const bool vg = sdy_coef_rows_vec4(a->gen, nullptr, r.gen_fields, 0, r.gen_var_stride, r.gen_time_stride);
+  const bool vt = sdy_coef_rows_vec4(a->target, nullptr, r.target_fields, 0, r.target_var_stride, r.target_time_stride);
+  sdy_coef_rows_dispatch<Launch>(r, vg, vt, a->err_power != nullptr, *a, (hipStream_t)stream);
   return sdy_launch_status();
 }

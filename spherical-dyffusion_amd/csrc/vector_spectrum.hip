@@ -8,21 +8,18 @@
 // Per row and order a lane reads eight values of the generated side (re / im of four products) where the scalar spectra read
 // two, and with the error accumulators eight of the row's target row: four times the bytes of sdy_degree_power per row.
 #include "common.h"
+#include "coef_rows.h"
 #include "vector_spectrum.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int kLanes = SDY_SP_SLOTS / 4;   // one wave
-static_assert(kLanes == 64, "a wave holds the slots, four per lane");
-
-struct Quad { float v[4]; };
-
 // rows r0 .. r0 + 3 (r0 < rows, a multiple of four) of a run that starts at p[0] and holds `rows` rows; rows past the end read
 // as 0.  No branch: a load per quad (VEC: p + r0 is 16-byte aligned and the run's group of fields is padded to a multiple of
-// four inside its buffer -- aligned16 below -- so the whole quad is addressable) or per row with the row number clamped to the
-// run's last row, then a select.  (A branch per row multiplied the kernel's code past the instruction cache.)
+// four inside its buffer -- sdy_coef_rows_vec4 -- so the whole quad is addressable) or per row with the row number clamped to
+// the run's last row, then a select.  (A branch per row multiplied the kernel's code past the instruction cache: that is why
+// this is not spectrum.hip's ld_quad, which branches so as not to load a quad past the end.)
 template <bool VEC>
 __device__ __forceinline__ Quad ld_quad(const float* p, int r0, int rows) {
   Quad q;
@@ -38,12 +35,6 @@ __device__ __forceinline__ Quad ld_quad(const float* p, int r0, int rows) {
   return q;
 }
 
-__device__ __forceinline__ double wave_butterfly(double x) {
-#pragma clang fp contract(off)
-  for (int m = 1; m < kLanes; m <<= 1) x = x + __shfl_xor(x, m);
-  return x;
-}
-
 // the four planes (re / im of the u run, re / im of the v run) of one coefficient tensor at (l, m), rows r0 .. r0 + 3
 struct Planes { Quad u_re, u_im, v_re, v_im; };
 
@@ -57,14 +48,35 @@ __device__ __forceinline__ Planes ld_planes(const float* p, int m, long F, long 
   return x;
 }
 
+// What the kernel takes: the members of sdy_vector_spectrum_args with the v offsets between the field counts and the strides,
+// filled by Launch::go.  In the public order (v offsets behind the descriptor) the compiler merges the scalar argument loads
+// differently and shuffles 1400 lines of the kernel at equal registers; in this order the kernel's code is line for line what
+// it was before the descriptor, so its speed is not in question (NOTEBOOK.md 7zd).
+struct KernelArgs {
+  size_t struct_size;
+  const float *gen_d, *gen_m, *target_d, *target_m;
+  const float* gen_scale;
+  const float* target_scale;
+  int lmax, mtr;
+  int gen_fields, target_fields;
+  int gen_v_offset, target_v_offset;
+  int gen_var_stride, gen_time_stride;
+  int target_var_stride, target_time_stride;
+  int nvars, n0, n1, T;
+  int t_start, n_timesteps;
+  double *gen_rot, *gen_div, *target_rot, *target_div, *err_rot, *err_div;
+};
+
 // blockIdx = (degree l, window time t, pair v); 64 threads
 template <bool VEC_G, bool VEC_T, bool ERR>
-__global__ __launch_bounds__(kLanes) void vector_degree_power_kernel(const sdy_vector_spectrum_args a) {
+__global__ __launch_bounds__(kLanes) void vector_degree_power_kernel(const KernelArgs a) {
   const int l = blockIdx.x, t = blockIdx.y, v = blockIdx.z, lane = threadIdx.x;
+  // sdy_coef_rows_element(a.rows, v, t, l), spelled out as in degree_power_kernel: with the helper six of the eight
+  // instantiations take one more scalar register.  The fields are the u fields; every row's u and v field is inside its
+  // buffer (entry point).
   const int mlast = l < a.mtr - 1 ? l : a.mtr - 1;
   const int R = a.n0 * a.n1, n1 = a.n1;
   const long Fg = a.gen_fields, Ft = a.target_fields, gvo = a.gen_v_offset, tvo = a.target_v_offset;
-  // first u field of the element's rows (entry point: every row's u and v field is inside its buffer), the planes of (l, m = 0)
   const long gf0 = (long)v * a.gen_var_stride + (long)t * a.gen_time_stride;
   const long tf0 = (long)v * a.target_var_stride + (long)t * a.target_time_stride;
   const long gl = (long)l * a.mtr * 2 * Fg + gf0, tl = (long)l * a.mtr * 2 * Ft + tf0;
@@ -159,8 +171,7 @@ __global__ __launch_bounds__(kLanes) void vector_degree_power_kernel(const sdy_v
     e_div = wave_butterfly(sdy_sp_fold4(eds[0], eds[1], eds[2], eds[3]));
   }
   if (lane == 0) {
-    // accumulator element: pair v < nvars, time t_start + t < n_timesteps (entry point), degree l < lmax
-    const long at = ((long)v * a.n_timesteps + (a.t_start + (long)t)) * a.lmax + l;
+    const long at = ((long)v * a.n_timesteps + (a.t_start + (long)t)) * a.lmax + l;   // the element's `at`
     a.gen_rot[at] += sdy_sp_mean(g_rot, R);
     a.gen_div[at] += sdy_sp_mean(g_div, R);
     a.target_rot[at] += sdy_sp_mean(t_rot, n1);
@@ -172,45 +183,25 @@ __global__ __launch_bounds__(kLanes) void vector_degree_power_kernel(const sdy_v
   }
 }
 
-// everything that bounds an address or an index, for the device and the host entry points alike
+template <bool VEC_G, bool VEC_T, bool ERR>
+struct Launch {
+  static void go(const sdy_vector_spectrum_args& a, dim3 grid, hipStream_t s) {
+    const sdy_coef_rows& r = a.rows;
+    const KernelArgs k = {a.struct_size, a.gen_d, a.gen_m, a.target_d, a.target_m, r.gen_scale, r.target_scale, r.lmax, r.mtr,
+                          r.gen_fields, r.target_fields, a.gen_v_offset, a.target_v_offset, r.gen_var_stride, r.gen_time_stride,
+                          r.target_var_stride, r.target_time_stride, r.nvars, r.n0, r.n1, r.T, r.t_start, r.n_timesteps,
+                          a.gen_rot, a.gen_div, a.target_rot, a.target_div, a.err_rot, a.err_div};
+    hipLaunchKernelGGL((vector_degree_power_kernel<VEC_G, VEC_T, ERR>), grid, dim3(kLanes), 0, s, k);
+  }
+};
+
+// the entry points' own checks in front of the descriptor's, for the device and the host entry points alike
 int check_vector_spectrum(const sdy_vector_spectrum_args* a) {
   if (!a || a->struct_size != sizeof(sdy_vector_spectrum_args)) return SDY_ERR_ARG;
   if (!a->gen_d || !a->gen_m || !a->target_d || !a->target_m) return SDY_ERR_ARG;
   if (!a->gen_rot || !a->gen_div || !a->target_rot || !a->target_div) return SDY_ERR_ARG;
   if ((a->err_rot == nullptr) != (a->err_div == nullptr)) return SDY_ERR_ARG;
-  if (a->lmax < 1 || a->mtr < 1 || a->gen_fields < 1 || a->target_fields < 1) return SDY_ERR_ARG;
-  if (a->nvars < 1 || a->n0 < 1 || a->n1 < 1 || a->T < 1 || a->n_timesteps < 1) return SDY_ERR_ARG;
-  if (a->mtr > a->lmax) return SDY_ERR_ARG;                 // mtr = min(mmax, lmax) of the plan that wrote the coefficients
-  if (a->gen_var_stride < 0 || a->gen_time_stride < 0 || a->target_var_stride < 0 || a->target_time_stride < 0)
-    return SDY_ERR_ARG;
-  if (a->gen_v_offset < 0 || a->target_v_offset < 0) return SDY_ERR_ARG;
-  // the time offset into the accumulators: window times t_start .. t_start + T - 1 must all exist (in 64 bits: no wrap)
-  if (a->t_start < 0 || (long)a->t_start + (long)a->T > (long)a->n_timesteps) return SDY_ERR_ARG;
-  // 32-bit row numbers, 16-bit grid extents for times and pairs; flat indices are 64-bit
-  if ((long)a->n0 * a->n1 >= (1L << 31) - SDY_SP_SLOTS) return SDY_ERR_UNSUPPORTED;
-  if (a->T > 65535 || a->nvars > 65535) return SDY_ERR_UNSUPPORTED;
-  const long cs_rows = (long)a->lmax * a->mtr * 2;
-  if (cs_rows * a->gen_fields >= (1L << 40) || cs_rows * a->target_fields >= (1L << 40)) return SDY_ERR_UNSUPPORTED;
-  if ((long)a->nvars * a->n_timesteps >= (1L << 40) / a->lmax) return SDY_ERR_UNSUPPORTED;
-  // the last row of the last time of the last pair, in the u run and in the v run, must be a field of its buffer
-  const long R = (long)a->n0 * a->n1;
-  const long g_last = (long)(a->nvars - 1) * a->gen_var_stride + (long)(a->T - 1) * a->gen_time_stride + R - 1;
-  const long t_last = (long)(a->nvars - 1) * a->target_var_stride + (long)(a->T - 1) * a->target_time_stride + a->n1 - 1;
-  if (g_last + a->gen_v_offset >= a->gen_fields || t_last + a->target_v_offset >= a->target_fields) return SDY_ERR_ARG;
-  return SDY_OK;
-}
-
-bool aligned16(const float* p, const float* q, int fields, int v_offset, int var_stride, int time_stride) {
-  return (((uintptr_t)p | (uintptr_t)q) & 15) == 0 && ((fields | v_offset | var_stride | time_stride) & 3) == 0;
-}
-
-template <bool VEC_G, bool VEC_T>
-void launch(const sdy_vector_spectrum_args* a, hipStream_t s) {
-  const dim3 grid(a->lmax, a->T, a->nvars);
-  if (a->err_rot)
-    hipLaunchKernelGGL((vector_degree_power_kernel<VEC_G, VEC_T, true>), grid, dim3(kLanes), 0, s, *a);
-  else
-    hipLaunchKernelGGL((vector_degree_power_kernel<VEC_G, VEC_T, false>), grid, dim3(kLanes), 0, s, *a);
+  return sdy_coef_rows_check(&a->rows, a->gen_v_offset, a->target_v_offset);
 }
 
 // one row's eight values at order m of the two tensors p_d, p_m (already at (l, first u field)), row field r
@@ -224,75 +215,67 @@ inline sdy_vs_coef host_coef(const float* p_d, const float* p_m, int m, long F, 
 
 extern "C" int sdy_vector_degree_power_host(const sdy_vector_spectrum_args* a) {
   SDY_TRY(check_vector_spectrum(a));
-  const long Fg = a->gen_fields, Ft = a->target_fields, gvo = a->gen_v_offset, tvo = a->target_v_offset;
-  const int R = a->n0 * a->n1, n1 = a->n1;
+  const sdy_coef_rows& r = a->rows;
+  const long Fg = r.gen_fields, Ft = r.target_fields, gvo = a->gen_v_offset, tvo = a->target_v_offset;
+  const int R = r.n0 * r.n1, n1 = r.n1;
   const bool err = a->err_rot != nullptr;
   double rs[SDY_SP_SLOTS], ds[SDY_SP_SLOTS], trs[SDY_SP_SLOTS], tds[SDY_SP_SLOTS], ers[SDY_SP_SLOTS], eds[SDY_SP_SLOTS];
-  for (int v = 0; v < a->nvars; ++v)
-    for (int t = 0; t < a->T; ++t)
-      for (int l = 0; l < a->lmax; ++l) {
-        const int mlast = l < a->mtr - 1 ? l : a->mtr - 1;
-        const long gf0 = (long)v * a->gen_var_stride + (long)t * a->gen_time_stride;
-        const long tf0 = (long)v * a->target_var_stride + (long)t * a->target_time_stride;
-        const long gl = (long)l * a->mtr * 2 * Fg + gf0, tl = (long)l * a->mtr * 2 * Ft + tf0;
-        const float *gd = a->gen_d + gl, *gm = a->gen_m + gl, *td = a->target_d + tl, *tm = a->target_m + tl;
-        for (int s = 0; s < SDY_SP_SLOTS; ++s) rs[s] = ds[s] = trs[s] = tds[s] = ers[s] = eds[s] = 0.0;
-        for (int r = 0; r < R; ++r) {
-          const int i1 = r % n1;
-          const double gsu = a->gen_scale ? (double)a->gen_scale[gf0 + r] : 1.0;
-          const double gsv = a->gen_scale ? (double)a->gen_scale[gf0 + gvo + r] : 1.0;
-          const double tsu = a->target_scale ? (double)a->target_scale[tf0 + i1] : 1.0;
-          const double tsv = a->target_scale ? (double)a->target_scale[tf0 + tvo + i1] : 1.0;
-          double rot = 0.0, div = 0.0, erot = 0.0, ediv = 0.0;
-          for (int m = 0; m <= mlast; ++m) {
-            const sdy_vs_coef g = host_coef(gd, gm, m, Fg, gvo, r, gsu, gsv);
-            div = sdy_vs_add(div, g.s_re, g.s_im, m);
-            rot = sdy_vs_add(rot, g.t_re, g.t_im, m);
-            if (err) {
-              const sdy_vs_coef h = host_coef(td, tm, m, Ft, tvo, i1, tsu, tsv);
-              ediv = sdy_vs_add(ediv, g.s_re - h.s_re, g.s_im - h.s_im, m);
-              erot = sdy_vs_add(erot, g.t_re - h.t_re, g.t_im - h.t_im, m);
-            }
-          }
-          rs[r % SDY_SP_SLOTS] += rot;
-          ds[r % SDY_SP_SLOTS] += div;
-          ers[r % SDY_SP_SLOTS] += erot;
-          eds[r % SDY_SP_SLOTS] += ediv;
-        }
-        for (int r = 0; r < n1; ++r) {
-          const double tsu = a->target_scale ? (double)a->target_scale[tf0 + r] : 1.0;
-          const double tsv = a->target_scale ? (double)a->target_scale[tf0 + tvo + r] : 1.0;
-          double rot = 0.0, div = 0.0;
-          for (int m = 0; m <= mlast; ++m) {
-            const sdy_vs_coef h = host_coef(td, tm, m, Ft, tvo, r, tsu, tsv);
-            div = sdy_vs_add(div, h.s_re, h.s_im, m);
-            rot = sdy_vs_add(rot, h.t_re, h.t_im, m);
-          }
-          trs[r % SDY_SP_SLOTS] += rot;
-          tds[r % SDY_SP_SLOTS] += div;
-        }
-        const long at = ((long)v * a->n_timesteps + (a->t_start + (long)t)) * a->lmax + l;
-        a->gen_rot[at] += sdy_sp_mean(sdy_sp_fold_slots(rs), R);
-        a->gen_div[at] += sdy_sp_mean(sdy_sp_fold_slots(ds), R);
-        a->target_rot[at] += sdy_sp_mean(sdy_sp_fold_slots(trs), n1);
-        a->target_div[at] += sdy_sp_mean(sdy_sp_fold_slots(tds), n1);
+  sdy_coef_rows_walk(r, [&](const sdy_coef_element el) {
+    const long gf0 = el.gf0, tf0 = el.tf0;
+    const float *gd = a->gen_d + el.gl, *gm = a->gen_m + el.gl, *td = a->target_d + el.tl, *tm = a->target_m + el.tl;
+    for (int s = 0; s < SDY_SP_SLOTS; ++s) rs[s] = ds[s] = trs[s] = tds[s] = ers[s] = eds[s] = 0.0;
+    for (int row = 0; row < R; ++row) {
+      const int i1 = row % n1;
+      const double gsu = r.gen_scale ? (double)r.gen_scale[gf0 + row] : 1.0;
+      const double gsv = r.gen_scale ? (double)r.gen_scale[gf0 + gvo + row] : 1.0;
+      const double tsu = r.target_scale ? (double)r.target_scale[tf0 + i1] : 1.0;
+      const double tsv = r.target_scale ? (double)r.target_scale[tf0 + tvo + i1] : 1.0;
+      double rot = 0.0, div = 0.0, erot = 0.0, ediv = 0.0;
+      for (int m = 0; m <= el.mlast; ++m) {
+        const sdy_vs_coef g = host_coef(gd, gm, m, Fg, gvo, row, gsu, gsv);
+        div = sdy_vs_add(div, g.s_re, g.s_im, m);
+        rot = sdy_vs_add(rot, g.t_re, g.t_im, m);
         if (err) {
-          a->err_rot[at] += sdy_sp_mean(sdy_sp_fold_slots(ers), R);
-          a->err_div[at] += sdy_sp_mean(sdy_sp_fold_slots(eds), R);
+          const sdy_vs_coef h = host_coef(td, tm, m, Ft, tvo, i1, tsu, tsv);
+          ediv = sdy_vs_add(ediv, g.s_re - h.s_re, g.s_im - h.s_im, m);
+          erot = sdy_vs_add(erot, g.t_re - h.t_re, g.t_im - h.t_im, m);
         }
       }
+      rs[row % SDY_SP_SLOTS] += rot;
+      ds[row % SDY_SP_SLOTS] += div;
+      ers[row % SDY_SP_SLOTS] += erot;
+      eds[row % SDY_SP_SLOTS] += ediv;
+    }
+    for (int row = 0; row < n1; ++row) {
+      const double tsu = r.target_scale ? (double)r.target_scale[tf0 + row] : 1.0;
+      const double tsv = r.target_scale ? (double)r.target_scale[tf0 + tvo + row] : 1.0;
+      double rot = 0.0, div = 0.0;
+      for (int m = 0; m <= el.mlast; ++m) {
+        const sdy_vs_coef h = host_coef(td, tm, m, Ft, tvo, row, tsu, tsv);
+        div = sdy_vs_add(div, h.s_re, h.s_im, m);
+        rot = sdy_vs_add(rot, h.t_re, h.t_im, m);
+      }
+      trs[row % SDY_SP_SLOTS] += rot;
+      tds[row % SDY_SP_SLOTS] += div;
+    }
+    sdy_coef_rows_add(a->gen_rot, el.at, rs, R);
+    sdy_coef_rows_add(a->gen_div, el.at, ds, R);
+    sdy_coef_rows_add(a->target_rot, el.at, trs, n1);
+    sdy_coef_rows_add(a->target_div, el.at, tds, n1);
+    if (err) {
+      sdy_coef_rows_add(a->err_rot, el.at, ers, R);
+      sdy_coef_rows_add(a->err_div, el.at, eds, R);
+    }
+  });
   return SDY_OK;
 }
 
 extern "C" int sdy_vector_degree_power(const sdy_vector_spectrum_args* a, void* stream) {
   SDY_TRY(check_vector_spectrum(a));
-  const bool vg = aligned16(a->gen_d, a->gen_m, a->gen_fields, a->gen_v_offset, a->gen_var_stride, a->gen_time_stride);
-  const bool vt = aligned16(a->target_d, a->target_m, a->target_fields, a->target_v_offset, a->target_var_stride,
-                            a->target_time_stride);
-  const hipStream_t s = (hipStream_t)stream;
-  if (vg && vt) launch<true, true>(a, s);
-  else if (vg) launch<true, false>(a, s);
-  else if (vt) launch<false, true>(a, s);
-  else launch<false, false>(a, s);
+  const sdy_coef_rows& r = a->rows;
+  const bool vg = sdy_coef_rows_vec4(a->gen_d, a->gen_m, r.gen_fields, a->gen_v_offset, r.gen_var_stride, r.gen_time_stride);
+  const bool vt = sdy_coef_rows_vec4(a->target_d, a->target_m, r.target_fields, a->target_v_offset, r.target_var_stride,
+                                     r.target_time_stride);
+  sdy_coef_rows_dispatch<Launch>(r, vg, vt, a->err_rot != nullptr, *a, (hipStream_t)stream);
   return sdy_launch_status();
 }

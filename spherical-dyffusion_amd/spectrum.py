@@ -104,6 +104,136 @@ def _plan(H: int, W: int, lmax: Optional[int], mmax: Optional[int], grid: str, d
     return ShtPlan.get(H, W, lmax or H, mmax or W // 2 + 1, grid, idx, None)      # gemm_mode: the package default
 
 
+def _fill_rows(rows, plan, gen_scale, target_scale, gen_side, target_side, nvars: int, n0: int, n1: int, T: int, t_start: int,
+               n_timesteps: int) -> None:
+    """The `sdy_coef_rows` of an argument structure (include/sdy_amd.h).  plan: anything with `lmax` and `mtr`; the scales:
+    addresses or None; gen_side / target_side: (fields, var_stride, time_stride) of the side's coefficient tensors."""
+    rows.gen_scale, rows.target_scale = gen_scale, target_scale
+    rows.lmax, rows.mtr = plan.lmax, plan.mtr
+    rows.gen_fields, rows.gen_var_stride, rows.gen_time_stride = gen_side
+    rows.target_fields, rows.target_var_stride, rows.target_time_stride = target_side
+    rows.nvars, rows.n0, rows.n1, rows.T, rows.t_start, rows.n_timesteps = nvars, n0, n1, T, t_start, n_timesteps
+
+
+class _SpectrumAggregator(FieldAccumulator):
+    """What `PowerSpectrumAggregator` and `KineticEnergySpectrumAggregator` share: the transform's grid and truncation, the
+    grow-only workspace and its limit, the `(n_timesteps, lmax)` accumulators and `get_data`, the sizing of a chunk, and the
+    chunk itself -- pack the rows of both sides, transform, fill the `sdy_coef_rows`, ONE reduction launch.  A row has
+    `_COMPONENTS` fields (1: a scalar; 2: u and v); the fields of one component are one run of a side's field batch (the rows
+    of one (variable, time) consecutive, each such group padded with zero fields to a multiple of four), the next component's
+    an equal run behind it; a side is analysed into `_TENSORS` coefficient tensors."""
+
+    _STATS: Tuple[Tuple[str, str], ...] = ()      # (label of get_data, field of the argument structure)
+    _COMPONENTS = 1
+    _TENSORS = 1
+    _WORD = "variable"                            # what the refusals call one row of `_STATS` accumulators
+
+    def __init__(self, n_timesteps: int, grid: str, lmax: Optional[int], dist, metadata, max_bytes: Optional[int],
+                 max_workspace_bytes: Optional[int]):
+        super().__init__(n_timesteps, dist=dist, metadata=metadata, max_bytes=max_bytes)
+        self._grid = grid
+        self._lmax = None if lmax is None else int(lmax)
+        self._limit = DEFAULT_MAX_WORKSPACE_BYTES if max_workspace_bytes is None else int(max_workspace_bytes)
+        self._ws = _Workspace()
+
+    # -- to be provided: the transform of one side's field batch; the argument structure of one chunk
+    def _analyse(self, plan: ShtPlan, x: torch.Tensor, Xf: torch.Tensor, *rest) -> torch.Tensor:
+        """x (F, H, W) into the `_TENSORS` coefficient tensors (`rest`: they, then the zeros of the FFT); returns the scale."""
+        raise NotImplementedError
+
+    def _args(self, Cg: List[torch.Tensor], Ct: List[torch.Tensor], run_g: int, run_t: int):
+        """(argument structure with everything but `rows` and the accumulators, name of the entry point); run_g, run_t: the
+        fields of one component's run of the generated / the target side."""
+        raise NotImplementedError
+
+    def _statistics(self) -> Dict[str, float]:
+        return {stat: 0.0 for _, stat in self._STATS}
+
+    def _elements(self, stat: str, job: tuple) -> int:
+        return self._n_timesteps * self._degrees(job)
+
+    def _degrees(self, job: tuple) -> int:
+        _, H, _ = job
+        return self._lmax or H
+
+    @property
+    def workspace_bytes(self) -> int:
+        """Bytes of the workspace as it stands (it only grows)."""
+        return self._ws.bytes
+
+    def _per_chunk(self, l, device) -> int:
+        """How many variables (pairs) shaped like `l` one chunk takes."""
+        n0, n1, T, H, W = l.n0, l.n1, l.T, l.H, l.W
+        who, word = type(self).__name__, self._WORD
+        plan = _plan(H, W, self._lmax, None, self._grid, device)
+        per_x, per_cs = _floats_per_field(plan)
+        fg, ft = self._COMPONENTS * T * _round_up(n0 * n1, 4), self._COMPONENTS * T * _round_up(n1, 4)
+        if fg > _MAX_FIELDS or fg * H * W > (1 << 31) - 1:
+            raise ValueError(f"{who}: one {word} of a window is {fg} fields of {H} x {W}; one transform call takes at most "
+                             f"{_MAX_FIELDS} fields and 2^31 - 1 grid values")
+        per_one = 4 * (fg * per_x + self._TENSORS * (fg + ft) * per_cs + fg)
+        n = min(max(self._limit - _SLACK, 0) // per_one, _MAX_FIELDS // fg, ((1 << 31) - 1) // (fg * H * W))
+        if n < 1:
+            raise ValueError(f"{who}: one {word} of a window ({fg} + {ft} fields of {H} x {W}) needs {per_one} bytes of "
+                             f"workspace, more than max_workspace_bytes = {self._limit} allows")
+        return n
+
+    def _chunk(self, lays, first: int, last: int, t_start: int, device) -> None:
+        """Variables (pairs) first .. last - 1 (one shape) of `lays`, one list of layouts per component: pack, transform and
+        reduce both sides."""
+        l0 = lays[0][first]
+        n0, n1, T, H, W = l0.n0, l0.n1, l0.T, l0.H, l0.W
+        nv, R, k = last - first, n0 * n1, self._TENSORS
+        Rp, Sp = _round_up(R, 4), _round_up(n1, 4)
+        run_g, run_t = nv * T * Rp, nv * T * Sp                  # one component's run of a side; the next one's follows
+        Fg, Ft = len(lays) * run_g, len(lays) * run_t
+        plan = _plan(H, W, self._lmax, None, self._grid, device)
+        per_cs = plan.lmax * plan.mtr * 2
+        Fx = max(Fg, Ft)
+        xb, Xf, *Cs, zeros = self._ws.parts(device, Fx * H * W, Fx * plan.mtr * H * 2, *[Fg * per_cs] * k, *[Ft * per_cs] * k,
+                                            Fx)
+        Cg, Ct = Cs[:k], Cs[k:]
+        zeros.zero_()
+        scales = []
+        for side, F, rows, rows_p, C_side in (("gen", Fg, R, Rp, Cg), ("target", Ft, n1, Sp, Ct)):
+            x = xb[:F * H * W].view(len(lays), nv, T, rows_p, H, W)
+            if rows_p != rows:
+                x[:, :, :, rows:].zero_()
+            for c, lay in enumerate(lays):
+                for j in range(nv):
+                    l = lay[first + j]
+                    if side == "gen":
+                        src = torch.as_strided(l.gen, (n0, n1, T, H, W), (l.gs0, l.gs1, H * W, W, 1)).permute(2, 0, 1, 3, 4)
+                        x[c, j, :, :rows].view(T, n0, n1, H, W).copy_(src)
+                    else:
+                        src = torch.as_strided(l.target, (n1, T, H, W), (l.ts1, H * W, W, 1)).permute(1, 0, 2, 3)
+                        x[c, j, :, :rows].copy_(src)
+            scales.append(self._analyse(plan, x.view(F, H, W), Xf[:F * plan.mtr * H * 2], *C_side, zeros))
+        a, entry = self._args(Cg, Ct, run_g, run_t)
+        _fill_rows(a.rows, plan, ptr(scales[0]), ptr(scales[1]), (Fg, T * Rp, Rp), (Ft, T * Sp, Sp), nv, n0, n1, T, t_start,
+                   self._n_timesteps)
+        for stat in self._acc:
+            setattr(a, stat, self._at(stat, first))
+        check(getattr(lib, entry)(C.byref(a), current_stream()), entry)
+
+    def _run(self, lays, first: int, last: int, t_start: int) -> None:
+        """A run of same-shaped variables (pairs), in chunks that fit the workspace."""
+        device = lays[0][first].gen.device
+        step = self._per_chunk(lays[0][first], device)
+        for c0 in range(first, last, step):
+            self._chunk(lays, c0, min(c0 + step, last), t_start, device)
+
+    @torch.no_grad()
+    def get_data(self) -> Dict[str, Dict[str, torch.Tensor]]:
+        n = self._counts()[:, None]
+        red = self._dist.reduce_mean
+        data = {}
+        for i, name in enumerate(self._names):
+            shape = (self._n_timesteps, self._degrees(self._grids[i]))
+            data[name] = {label: red(self._view(stat, i, *shape) / n) for label, stat in self._STATS}
+        return data
+
+
 @torch.no_grad()
 def power_spectrum(x: torch.Tensor, grid: str = "equiangular", lmax: Optional[int] = None, mmax: Optional[int] = None,
                    max_workspace_bytes: Optional[int] = None) -> torch.Tensor:
@@ -141,17 +271,13 @@ def power_spectrum(x: torch.Tensor, grid: str = "equiangular", lmax: Optional[in
             unused = torch.zeros(k, plan.lmax, dtype=torch.float64, device=x.device)
             a = SdySpectrumArgs()
             a.gen = a.target = ptr(Cs)
-            a.gen_scale = a.target_scale = ptr(scale)
-            a.lmax, a.mtr, a.gen_fields, a.target_fields = plan.lmax, plan.mtr, F, F
-            a.gen_var_stride = a.target_var_stride = 0
-            a.gen_time_stride = a.target_time_stride = 1
-            a.nvars, a.n0, a.n1, a.T, a.t_start, a.n_timesteps = 1, 1, 1, k, 0, k
+            _fill_rows(a.rows, plan, ptr(scale), ptr(scale), (F, 0, 1), (F, 0, 1), 1, 1, 1, k, 0, k)
             a.gen_power, a.target_power, a.err_power = out[r0:r0 + k].data_ptr(), unused.data_ptr(), None
             check(lib.sdy_degree_power(C.byref(a), current_stream()), "sdy_degree_power")
     return out.view(*lead, plan.lmax)
 
 
-class PowerSpectrumAggregator(FieldAccumulator):
+class PowerSpectrumAggregator(_SpectrumAggregator):
     """Per-degree power spectra of the generated and the target fields and of their difference, per variable and lead time.
 
     Same `record_batch` as the other inference aggregators, on the denormalised dicts: gen `(samples, time, lat, lon)` or
@@ -176,100 +302,26 @@ class PowerSpectrumAggregator(FieldAccumulator):
     target row `sample` (the rule of `VideoAggregator`).  Ragged rank shares with `sample_weights` are not supported.
     The accumulators are allocated on the first batch (`max_bytes` as for the other field aggregators); they are tiny."""
 
+    _STATS = (("gen", "gen_power"), ("target", "target_power"), ("error", "err_power"))
+    _analyse = staticmethod(_analyse)
+
     def __init__(self, n_timesteps: int, grid: str = "equiangular", lmax: Optional[int] = None, dist=None, metadata=None,
                  max_bytes: Optional[int] = None, max_workspace_bytes: Optional[int] = None):
-        super().__init__(n_timesteps, dist=dist, metadata=metadata, max_bytes=max_bytes)
-        self._grid = grid
-        self._lmax = None if lmax is None else int(lmax)
-        self._limit = DEFAULT_MAX_WORKSPACE_BYTES if max_workspace_bytes is None else int(max_workspace_bytes)
-        self._ws = _Workspace()
+        super().__init__(n_timesteps, grid, lmax, dist, metadata, max_bytes, max_workspace_bytes)
 
-    def _statistics(self) -> Dict[str, float]:
-        return {"gen_power": 0.0, "target_power": 0.0, "err_power": 0.0}
-
-    def _elements(self, stat: str, job: tuple) -> int:
-        return self._n_timesteps * self._degrees(job)
-
-    def _degrees(self, job: tuple) -> int:
-        _, H, _ = job
-        return self._lmax or H
-
-    @property
-    def workspace_bytes(self) -> int:
-        """Bytes of the workspace as it stands (it only grows)."""
-        return self._ws.bytes
-
-    def _chunk(self, lay, first: int, last: int, t_start: int, device) -> None:
-        """Variables first .. last - 1 (one shape): pack, transform and reduce both sides."""
-        _, _, n0, n1, gs0, gs1, ts1, T, H, W = lay[first]
-        nv, R = last - first, n0 * n1
-        Rp, Sp = _round_up(R, 4), _round_up(n1, 4)
-        Fg, Ft = nv * T * Rp, nv * T * Sp
-        plan = _plan(H, W, self._lmax, None, self._grid, device)
-        per_cs = plan.lmax * plan.mtr * 2
-        Fx = max(Fg, Ft)
-        xb, Xf, Cg, Ct, zeros = self._ws.parts(device, Fx * H * W, Fx * plan.mtr * H * 2, Fg * per_cs, Ft * per_cs, Fx)
-        zeros.zero_()
-        scales = []
-        for side, F, rows, rows_p, Cs in (("gen", Fg, R, Rp, Cg), ("target", Ft, n1, Sp, Ct)):
-            x = xb[:F * H * W].view(nv, T, rows_p, H, W)
-            if rows_p != rows:
-                x[:, :, rows:].zero_()
-            for k in range(nv):
-                v = getattr(lay[first + k], side)
-                if side == "gen":
-                    src = torch.as_strided(v, (n0, n1, T, H, W), (gs0, gs1, H * W, W, 1)).permute(2, 0, 1, 3, 4)
-                    x[k, :, :rows].view(T, n0, n1, H, W).copy_(src)
-                else:
-                    src = torch.as_strided(v, (n1, T, H, W), (ts1, H * W, W, 1)).permute(1, 0, 2, 3)
-                    x[k, :, :rows].copy_(src)
-            scales.append(_analyse(plan, x.view(F, H, W), Xf[:F * plan.mtr * H * 2], Cs, zeros))
+    def _args(self, Cg, Ct, run_g, run_t):
         a = SdySpectrumArgs()
-        a.gen, a.target, a.gen_scale, a.target_scale = ptr(Cg), ptr(Ct), ptr(scales[0]), ptr(scales[1])
-        a.lmax, a.mtr, a.gen_fields, a.target_fields = plan.lmax, plan.mtr, Fg, Ft
-        a.gen_var_stride, a.gen_time_stride, a.target_var_stride, a.target_time_stride = T * Rp, Rp, T * Sp, Sp
-        a.nvars, a.n0, a.n1, a.T, a.t_start, a.n_timesteps = nv, n0, n1, T, t_start, self._n_timesteps
-        for stat in self._acc:
-            setattr(a, stat, self._at(stat, first))
-        check(lib.sdy_degree_power(C.byref(a), current_stream()), "sdy_degree_power")
-
-    def _vars_per_chunk(self, l, device) -> int:
-        _, _, n0, n1, _, _, _, T, H, W = l
-        plan = _plan(H, W, self._lmax, None, self._grid, device)
-        per_x, per_cs = _floats_per_field(plan)
-        fg, ft = T * _round_up(n0 * n1, 4), T * _round_up(n1, 4)
-        if fg > _MAX_FIELDS or fg * H * W > (1 << 31) - 1:
-            raise ValueError(f"PowerSpectrumAggregator: one variable of a window is {fg} fields of {H} x {W}; one transform "
-                             f"call takes at most {_MAX_FIELDS} fields and 2^31 - 1 grid values")
-        per_var = 4 * (fg * per_x + (fg + ft) * per_cs + fg)
-        n = min(max(self._limit - _SLACK, 0) // per_var, _MAX_FIELDS // fg, ((1 << 31) - 1) // (fg * H * W))
-        if n < 1:
-            raise ValueError(f"PowerSpectrumAggregator: one variable of a window ({fg} + {ft} fields of {H} x {W}) needs "
-                             f"{per_var} bytes of workspace, more than max_workspace_bytes = {self._limit} allows")
-        return n
+        a.gen, a.target = ptr(Cg[0]), ptr(Ct[0])
+        return a, "sdy_degree_power"
 
     def _launch(self, lay, first: int, last: int, t_start: int) -> None:
-        """A run of same-shaped variables (`FieldAccumulator._record`), in chunks that fit the workspace."""
-        device = lay[first].gen.device
-        step = self._vars_per_chunk(lay[first], device)
-        for c0 in range(first, last, step):
-            self._chunk(lay, c0, min(c0 + step, last), t_start, device)
+        """A run of same-shaped variables (`FieldAccumulator._record`)."""
+        self._run((lay,), first, last, t_start)
 
     @torch.no_grad()
     def record_batch(self, loss, target_data, gen_data, target_data_norm=None, gen_data_norm=None, i_time_start: int = 0):
         del loss, target_data_norm, gen_data_norm
         self._record(target_data, gen_data, i_time_start)
-
-    @torch.no_grad()
-    def get_data(self) -> Dict[str, Dict[str, torch.Tensor]]:
-        n = self._counts()[:, None]
-        red = self._dist.reduce_mean
-        data = {}
-        for i, name in enumerate(self._names):
-            shape = (self._n_timesteps, self._degrees(self._grids[i]))
-            data[name] = {label: red(self._view(stat, i, *shape) / n)
-                          for label, stat in (("gen", "gen_power"), ("target", "target_power"), ("error", "err_power"))}
-        return data
 
 
 # ---- winds: rotational and divergent kinetic-energy spectra ------------------------------------------------------------------
@@ -369,19 +421,15 @@ def kinetic_energy_spectrum(u: torch.Tensor, v: torch.Tensor, grid: str = "equia
             a = SdyVectorSpectrumArgs()
             a.gen_d = a.target_d = ptr(Cd)
             a.gen_m = a.target_m = ptr(Cm)
-            a.gen_scale = a.target_scale = ptr(scale)
-            a.lmax, a.mtr, a.gen_fields, a.target_fields = plan.lmax, plan.mtr, F, F
+            _fill_rows(a.rows, plan, ptr(scale), ptr(scale), (F, 0, 1), (F, 0, 1), 1, 1, 1, k, 0, k)
             a.gen_v_offset = a.target_v_offset = Fh
-            a.gen_var_stride = a.target_var_stride = 0
-            a.gen_time_stride = a.target_time_stride = 1
-            a.nvars, a.n0, a.n1, a.T, a.t_start, a.n_timesteps = 1, 1, 1, k, 0, k
             a.gen_rot, a.gen_div = rot[r0:r0 + k].data_ptr(), div[r0:r0 + k].data_ptr()
             a.target_rot, a.target_div, a.err_rot, a.err_div = unused[0].data_ptr(), unused[1].data_ptr(), None, None
             check(lib.sdy_vector_degree_power(C.byref(a), current_stream()), "sdy_vector_degree_power")
     return {"rot": rot.view(*lead, plan.lmax), "div": div.view(*lead, plan.lmax)}
 
 
-class KineticEnergySpectrumAggregator(FieldAccumulator):
+class KineticEnergySpectrumAggregator(_SpectrumAggregator):
     """Rotational and divergent kinetic-energy spectra of the generated and the target winds and of their difference, per wind
     pair and lead time (module docstring; no counterpart in the reference).
 
@@ -406,37 +454,28 @@ class KineticEnergySpectrumAggregator(FieldAccumulator):
     in shape or layout, or that names one variable twice."""
 
     _STATS = (("gen_rot", "gen_rot"), ("gen_div", "gen_div"), ("target_rot", "target_rot"), ("target_div", "target_div"),
-              ("error_rot", "err_rot"), ("error_div", "err_div"))          # label of get_data, field of the argument structure
+              ("error_rot", "err_rot"), ("error_div", "err_div"))
+    _COMPONENTS = 2                 # u and v
+    _TENSORS = 2                    # A_D and A_M
+    _WORD = "pair"
+    _analyse = staticmethod(_vector_analyse)
 
     def __init__(self, pairs: Mapping[str, Tuple[str, str]], n_timesteps: int, grid: str = "equiangular",
                  lmax: Optional[int] = None, dist=None, metadata=None, max_bytes: Optional[int] = None,
                  max_workspace_bytes: Optional[int] = None):
-        super().__init__(n_timesteps, dist=dist, metadata=metadata, max_bytes=max_bytes)
+        super().__init__(n_timesteps, grid, lmax, dist, metadata, max_bytes, max_workspace_bytes)
         self._pairs = {str(label): (str(uv[0]), str(uv[1])) for label, uv in dict(pairs).items()}
         if not self._pairs:
             raise ValueError("KineticEnergySpectrumAggregator: no wind pairs")
         for label, (un, vn) in self._pairs.items():
             if un == vn:
                 raise ValueError(f"wind pair {label!r} names {un!r} twice")
-        self._grid = grid
-        self._lmax = None if lmax is None else int(lmax)
-        self._limit = DEFAULT_MAX_WORKSPACE_BYTES if max_workspace_bytes is None else int(max_workspace_bytes)
-        self._ws = _Workspace()
 
-    def _statistics(self) -> Dict[str, float]:
-        return {stat: 0.0 for _, stat in self._STATS}
-
-    def _elements(self, stat: str, job: tuple) -> int:
-        return self._n_timesteps * self._degrees(job)
-
-    def _degrees(self, job: tuple) -> int:
-        _, H, _ = job
-        return self._lmax or H
-
-    @property
-    def workspace_bytes(self) -> int:
-        """Bytes of the workspace as it stands (it only grows)."""
-        return self._ws.bytes
+    def _args(self, Cg, Ct, run_g, run_t):
+        a = SdyVectorSpectrumArgs()
+        a.gen_d, a.gen_m, a.target_d, a.target_m = ptr(Cg[0]), ptr(Cg[1]), ptr(Ct[0]), ptr(Ct[1])
+        a.gen_v_offset, a.target_v_offset = run_g, run_t           # the u run of a side; its v run follows
+        return a, "sdy_vector_degree_power"
 
     def _layouts(self, target_data, gen_data):
         """The `WindowLayout`s of the u and of the v variables, pair by pair, everything checked."""
@@ -461,60 +500,6 @@ class KineticEnergySpectrumAggregator(FieldAccumulator):
     def _extents(l) -> tuple:
         return (l.n0, l.n1, l.T, l.H, l.W)
 
-    def _chunk(self, lay_u, lay_v, first: int, last: int, t_start: int, device) -> None:
-        """Pairs first .. last - 1 (one shape): pack, transform and reduce both sides."""
-        n0, n1, T, H, W = self._extents(lay_u[first])
-        nv, R = last - first, n0 * n1
-        Rp, Sp = _round_up(R, 4), _round_up(n1, 4)
-        half_g, half_t = nv * T * Rp, nv * T * Sp                # the u run of a side; its v run follows
-        Fg, Ft = 2 * half_g, 2 * half_t
-        plan = _plan(H, W, self._lmax, None, self._grid, device)
-        per_cs = plan.lmax * plan.mtr * 2
-        Fx = max(Fg, Ft)
-        xb, Xf, Cgd, Cgm, Ctd, Ctm, zeros = self._ws.parts(device, Fx * H * W, Fx * plan.mtr * H * 2, Fg * per_cs, Fg * per_cs,
-                                                           Ft * per_cs, Ft * per_cs, Fx)
-        zeros.zero_()
-        scales = []
-        for side, F, rows, rows_p, Cd, Cm in (("gen", Fg, R, Rp, Cgd, Cgm), ("target", Ft, n1, Sp, Ctd, Ctm)):
-            x = xb[:F * H * W].view(2, nv, T, rows_p, H, W)
-            if rows_p != rows:
-                x[:, :, :, rows:].zero_()
-            for c, lay in enumerate((lay_u, lay_v)):
-                for k in range(nv):
-                    l = lay[first + k]
-                    if side == "gen":
-                        src = torch.as_strided(l.gen, (n0, n1, T, H, W), (l.gs0, l.gs1, H * W, W, 1)).permute(2, 0, 1, 3, 4)
-                        x[c, k, :, :rows].view(T, n0, n1, H, W).copy_(src)
-                    else:
-                        src = torch.as_strided(l.target, (n1, T, H, W), (l.ts1, H * W, W, 1)).permute(1, 0, 2, 3)
-                        x[c, k, :, :rows].copy_(src)
-            scales.append(_vector_analyse(plan, x.view(F, H, W), Xf[:F * plan.mtr * H * 2], Cd, Cm, zeros))
-        a = SdyVectorSpectrumArgs()
-        a.gen_d, a.gen_m, a.target_d, a.target_m = ptr(Cgd), ptr(Cgm), ptr(Ctd), ptr(Ctm)
-        a.gen_scale, a.target_scale = ptr(scales[0]), ptr(scales[1])
-        a.lmax, a.mtr, a.gen_fields, a.target_fields = plan.lmax, plan.mtr, Fg, Ft
-        a.gen_v_offset, a.target_v_offset = half_g, half_t
-        a.gen_var_stride, a.gen_time_stride, a.target_var_stride, a.target_time_stride = T * Rp, Rp, T * Sp, Sp
-        a.nvars, a.n0, a.n1, a.T, a.t_start, a.n_timesteps = nv, n0, n1, T, t_start, self._n_timesteps
-        for stat in self._acc:
-            setattr(a, stat, self._at(stat, first))
-        check(lib.sdy_vector_degree_power(C.byref(a), current_stream()), "sdy_vector_degree_power")
-
-    def _pairs_per_chunk(self, l, device) -> int:
-        n0, n1, T, H, W = self._extents(l)
-        plan = _plan(H, W, self._lmax, None, self._grid, device)
-        per_x, per_cs = _floats_per_field(plan)
-        fg, ft = 2 * T * _round_up(n0 * n1, 4), 2 * T * _round_up(n1, 4)
-        if fg > _MAX_FIELDS or fg * H * W > (1 << 31) - 1:
-            raise ValueError(f"KineticEnergySpectrumAggregator: one pair of a window is {fg} fields of {H} x {W}; one "
-                             f"transform call takes at most {_MAX_FIELDS} fields and 2^31 - 1 grid values")
-        per_pair = 4 * (fg * per_x + 2 * (fg + ft) * per_cs + fg)
-        n = min(max(self._limit - _SLACK, 0) // per_pair, _MAX_FIELDS // fg, ((1 << 31) - 1) // (fg * H * W))
-        if n < 1:
-            raise ValueError(f"KineticEnergySpectrumAggregator: one pair of a window ({fg} + {ft} fields of {H} x {W}) needs "
-                             f"{per_pair} bytes of workspace, more than max_workspace_bytes = {self._limit} allows")
-        return n
-
     @torch.no_grad()
     def record_batch(self, loss, target_data, gen_data, target_data_norm=None, gen_data_norm=None, i_time_start: int = 0):
         del loss, target_data_norm, gen_data_norm
@@ -532,18 +517,6 @@ class KineticEnergySpectrumAggregator(FieldAccumulator):
         device = self._prepare(list(self._pairs), lay_u)
         with torch.cuda.device(device):
             for first, last in runs(lay_u, self._extents):
-                step = self._pairs_per_chunk(lay_u[first], device)
-                for c0 in range(first, last, step):
-                    self._chunk(lay_u, lay_v, c0, min(c0 + step, last), i_time_start, device)
+                self._run((lay_u, lay_v), first, last, i_time_start)
         for t in range(i_time_start, i_time_start + T):
             self._n_batches[t] += 1
-
-    @torch.no_grad()
-    def get_data(self) -> Dict[str, Dict[str, torch.Tensor]]:
-        n = self._counts()[:, None]
-        red = self._dist.reduce_mean
-        data = {}
-        for i, name in enumerate(self._names):
-            shape = (self._n_timesteps, self._degrees(self._grids[i]))
-            data[name] = {label: red(self._view(stat, i, *shape) / n) for label, stat in self._STATS}
-        return data

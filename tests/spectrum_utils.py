@@ -240,12 +240,19 @@ def fill_args(lay, gen, target, gen_scale, target_scale, t_start, n_timesteps, a
     from sdy_amd._lib import SdySpectrumArgs
 
     a = SdySpectrumArgs()
-    a.gen, a.target, a.gen_scale, a.target_scale = gen, target, gen_scale, target_scale
-    a.lmax, a.mtr, a.gen_fields, a.target_fields = lay.lmax, lay.mtr, lay.Fg, lay.Ft
-    a.gen_var_stride, a.gen_time_stride, a.target_var_stride, a.target_time_stride = lay.g_var, lay.g_time, lay.t_var, lay.t_time
-    a.nvars, a.n0, a.n1, a.T, a.t_start, a.n_timesteps = lay.nvars, lay.n0, lay.n1, lay.T, t_start, n_timesteps
+    a.gen, a.target = gen, target
+    fill_rows(a.rows, lay, gen_scale, target_scale, t_start, n_timesteps)
     a.gen_power, a.target_power, a.err_power = acc
     return a
+
+
+def fill_rows(rows, lay, gen_scale, target_scale, t_start, n_timesteps, components=1):
+    """The sdy_coef_rows of a Layout, by the package's own `_fill_rows`; a buffer holds `components` runs of the layout's
+    fields (2: the u run and the v run of tests/vector_spectrum_utils.py)."""
+    from sdy_amd.spectrum import _fill_rows
+
+    _fill_rows(rows, lay, gen_scale, target_scale, (components * lay.Fg, lay.g_var, lay.g_time),
+               (components * lay.Ft, lay.t_var, lay.t_time), lay.nvars, lay.n0, lay.n1, lay.T, t_start, n_timesteps)
 
 
 def host_accumulate(lay, cg, ct, sg, st, t_start, acc, with_error=True):

@@ -295,11 +295,9 @@ def fill_args(lay, gd, gm, td, tm, gen_scale, target_scale, t_start, n_timesteps
     from sdy_amd._lib import SdyVectorSpectrumArgs
 
     a = SdyVectorSpectrumArgs()
-    a.gen_d, a.gen_m, a.target_d, a.target_m, a.gen_scale, a.target_scale = gd, gm, td, tm, gen_scale, target_scale
-    a.lmax, a.mtr, a.gen_fields, a.target_fields = lay.lmax, lay.mtr, 2 * lay.Fg, 2 * lay.Ft
+    a.gen_d, a.gen_m, a.target_d, a.target_m = gd, gm, td, tm
+    su.fill_rows(a.rows, lay, gen_scale, target_scale, t_start, n_timesteps, components=2)
     a.gen_v_offset, a.target_v_offset = lay.g_voff, lay.t_voff
-    a.gen_var_stride, a.gen_time_stride, a.target_var_stride, a.target_time_stride = lay.g_var, lay.g_time, lay.t_var, lay.t_time
-    a.nvars, a.n0, a.n1, a.T, a.t_start, a.n_timesteps = lay.nvars, lay.n0, lay.n1, lay.T, t_start, n_timesteps
     a.gen_rot, a.gen_div, a.target_rot, a.target_div, a.err_rot, a.err_div = acc
     return a
 

@@ -90,12 +90,8 @@ def main():
     a = SdyVectorSpectrumArgs()
     a.gen_d = a.target_d = ptr(Cd)
     a.gen_m = a.target_m = ptr(Cm)
-    a.gen_scale = a.target_scale = ptr(scale)
-    a.lmax, a.mtr, a.gen_fields, a.target_fields = plan.lmax, plan.mtr, F, F
+    spectrum._fill_rows(a.rows, plan, ptr(scale), ptr(scale), (F, T * Rp, Rp), (F, T * Rp, Rp), cp, M, 1, T, 0, T)
     a.gen_v_offset = a.target_v_offset = half
-    a.gen_var_stride = a.target_var_stride = T * Rp
-    a.gen_time_stride = a.target_time_stride = Rp
-    a.nvars, a.n0, a.n1, a.T, a.t_start, a.n_timesteps = cp, M, 1, T, 0, T
     a.gen_rot, a.gen_div, a.target_rot, a.target_div, a.err_rot, a.err_div = (acc[i].data_ptr() for i in range(6))
 
     def fft():
