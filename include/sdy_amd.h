@@ -1424,6 +1424,95 @@ int sdy_spacetime_segment_power(const sdy_spacetime_segment_power_args* args, vo
 int sdy_spacetime_segment_power_host(const sdy_spacetime_segment_power_args* args);
 size_t sdy_spacetime_workspace_bytes(int nvars, int M, int B, int N, int R, int K);   /* 0 for an argument out of range */
 
+/* Transient-eddy covariances of groups of variables at every grid point, on the device (no counterpart in the reference): the
+ * second moments along time of two variables together -- the momentum flux u'v', the heat flux v'T', the moisture flux v'q',
+ * the eddy kinetic energy, the correlation of any two variables at a point.  One definition for the kernels and the _host
+ * twins: csrc/time_covariance.h.  The three structures carry struct_size (sizeof of the structure; a call with another value is
+ * refused with SDY_ERR_ARG) and are not part of the sdy_abi_check list.
+ *   A group is an ordered set of K variables, 2 <= K <= SDY_TC_MAX_K, on one grid; NP = K (K + 1) / 2 pairs i <= j in the order
+ *     (0,0), (0,1), .., (0,K-1), (1,1), ..
+ *   One trajectory at one grid point, counted times x_k,1 .. x_k,n (fp32) in run order: c_k = x_k,1, d_k,t = (double)x_k,t -
+ *     (double)c_k, S_k = sum_t d_k,t, P_ij = sum_t d_i,t d_j,t.  float64, every product rounded once, every time's term added to
+ *     the running value in ascending time: the bits do not depend on how a run is cut into windows.
+ *   Trajectories: rows as for the time variability above -- the n0*n1 generated ones (member r / n1, sample r % n1), then the n1
+ *     targets: rows = n0*n1 + n1.
+ *   sums: dev double (n_groups, K, rows, HW); products: dev double (n_groups, NP, rows, HW); origins: dev float (n_groups, K,
+ *     rows, HW), the c_k.  K + NP float64 and K fp32 per group, trajectory and point: 128 bytes at K = 4.
+ * accumulate: ONE launch for all groups of one K.  window: see sdy_window, plane = HW, over the unique variables of the call;
+ *   members[g][k] is the window variable that is variable k of group g.  Adds the window times t0 .. T - 1; first != 0: the run's
+ *   first counted time is t0, the state is written without being read.  Every input value of a group is read once per window,
+ *   the state is read and written once, exactly one thread owns a state element: no atomics, no LDS.  16-byte loads and 32-byte
+ *   state accesses when HW, every stride and every pointer allow them, scalar ones otherwise (same bits).
+ *   SDY_ERR_ARG, before anything is launched: what sdy_window refuses; NULL args, another struct_size, K outside
+ *   2..SDY_TC_MAX_K, n_groups outside 1..SDY_TC_MAX_GROUPS, a member index outside 0..nvars-1 or repeated within a group, NULL
+ *   sums / products / origins, sums or products not 8-byte aligned, origins not 4-byte aligned, t0 outside 0..T-1.
+ *   SDY_ERR_UNSUPPORTED: n_groups*NP*rows*HW >= 2^50.
+ * maps: ONE group and one pair i <= j < K: sums and products are the group's blocks (K, n_elems) and (NP, n_elems), n_elems =
+ *   rows*HW.  With n = n_times, m_k = S_k / n, C_ij = P_ij - S_i m_j (the lower index as S), V_k = C_kk clamped at 0 (a NaN stays
+ *   one): cov[e] = C_ij / n (i == j: V_i / n), corr[e] = C_ij / sqrt(V_i V_j) clamped to [-1, 1], NaN unless n >= 2, V_i > 0 and
+ *   V_j > 0.  cov, corr: dev double (n_elems).  One thread per element.
+ *   SDY_ERR_ARG: NULL args, another struct_size, a NULL or misaligned pointer, K outside 2..SDY_TC_MAX_K, i or j outside 0..K-1,
+ *   i > j, n_elems < 1, n_times below 1 or not finite.  SDY_ERR_UNSUPPORTED: NP*n_elems >= 2^50 or more than 2^31 - 1 blocks.
+ * stats: all pairs of the n_groups groups of one K -> out (n_groups, NP, SDY_TC_SLOTS), per pair the sums over the n1 samples
+ *   and the HW grid points, with w = weights[p], g_m the M members and y the target of the sample:
+ *     slot 0: w mean_m cov(g_m)   1: w cov(y)   2: w (mean_m cov(g_m) - cov(y))^2
+ *     and over the points where n >= 2 and corr(y) and every corr(g_m) are not NaN:
+ *     slot 3: w mean_m corr(g_m)  4: w corr(y)  5: w
+ *   Chunks of 256 points: a wave's lanes by a butterfly, the waves in order, then the chunks in order (csrc/ordered_sum.h).
+ *   weights: dev float (HW); ws: dev, 8-byte aligned, at least sdy_time_covariance_workspace_bytes of (K, n_groups, n1, HW).
+ *   SDY_ERR_ARG: NULL args, another struct_size, a NULL or misaligned pointer, K outside 2..SDY_TC_MAX_K, n_groups outside
+ *   1..SDY_TC_MAX_GROUPS, a non-positive M / n1 / HW, n_times below 1 or not finite, ws_bytes too small.  SDY_ERR_UNSUPPORTED:
+ *   n1*HW > 2^30, n_groups*NP*(M + 1)*n1*HW >= 2^50.
+ * State and maps are bit-identical to their _host twins (the same structures with HOST pointers and the same checks; ws may be
+ * NULL); the stats _host twin uses the same chunks and adds a chunk's points in order. */
+#define SDY_TC_MAX_K 4
+#define SDY_TC_MAX_GROUPS 32
+#define SDY_TC_SLOTS 6
+typedef struct sdy_time_covariance_args sdy_time_covariance_args;
+struct sdy_time_covariance_args {
+  size_t struct_size;
+  sdy_window win;
+  int HW;
+  int t0;
+  int first;
+  int K, n_groups;
+  int members[SDY_TC_MAX_GROUPS][SDY_TC_MAX_K];
+  double* sums;
+  double* products;
+  float* origins;
+};
+int sdy_time_covariance_accumulate(const sdy_time_covariance_args* args, void* stream);
+int sdy_time_covariance_accumulate_host(const sdy_time_covariance_args* args);
+typedef struct sdy_time_covariance_maps_args sdy_time_covariance_maps_args;
+struct sdy_time_covariance_maps_args {
+  size_t struct_size;
+  const double* sums;
+  const double* products;
+  int K, i, j;
+  long n_elems;
+  double n_times;
+  double* cov;
+  double* corr;
+};
+int sdy_time_covariance_maps(const sdy_time_covariance_maps_args* args, void* stream);
+int sdy_time_covariance_maps_host(const sdy_time_covariance_maps_args* args);
+typedef struct sdy_time_covariance_stats_args sdy_time_covariance_stats_args;
+struct sdy_time_covariance_stats_args {
+  size_t struct_size;
+  int K, n_groups;
+  int M, n1, HW;
+  const double* sums;
+  const double* products;
+  const float* weights;
+  double n_times;
+  double* out;
+  void* ws;
+  size_t ws_bytes;
+};
+int sdy_time_covariance_stats(const sdy_time_covariance_stats_args* args, void* stream);
+int sdy_time_covariance_stats_host(const sdy_time_covariance_stats_args* args);
+size_t sdy_time_covariance_workspace_bytes(int K, int n_groups, int n1, int HW);   /* 0 for an argument out of range */
+
 /* The area-weighted Gram matrix of the member errors and the truth anomaly (no counterpart in the reference): what the energy
  * score, the member-to-member and member-to-truth distances of whole fields and the anomaly correlation are read from.  ONE
  * launch for all variables of one window.  window: see sdy_window, plane = HW: n0 = M members (1 for a deterministic run), n1

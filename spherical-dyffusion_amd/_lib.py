@@ -492,6 +492,50 @@ class SdySpacetimeSegmentPowerArgs(_SizedStructure):
     ]
 
 
+SDY_TC_MAX_K = 4
+SDY_TC_MAX_GROUPS = 32
+SDY_TC_SLOTS = 6
+
+
+class SdyTimeCovarianceArgs(_SizedStructure):
+    """`sdy_time_covariance_args`: one window into the state of the groups of one K."""
+    _anonymous_ = ("win",)
+    _fields_ = [
+        ("struct_size", C.c_size_t),
+        ("win", SdyWindow), ("HW", C.c_int),
+        ("t0", C.c_int),
+        ("first", C.c_int),
+        ("K", C.c_int), ("n_groups", C.c_int),
+        ("members", (C.c_int * SDY_TC_MAX_K) * SDY_TC_MAX_GROUPS),
+        ("sums", C.c_void_p), ("products", C.c_void_p), ("origins", C.c_void_p),
+    ]
+
+
+class SdyTimeCovarianceMapsArgs(_SizedStructure):
+    """`sdy_time_covariance_maps_args`: covariance and correlation of one pair of one group."""
+    _fields_ = [
+        ("struct_size", C.c_size_t),
+        ("sums", C.c_void_p), ("products", C.c_void_p),
+        ("K", C.c_int), ("i", C.c_int), ("j", C.c_int),
+        ("n_elems", C.c_long),
+        ("n_times", C.c_double),
+        ("cov", C.c_void_p), ("corr", C.c_void_p),
+    ]
+
+
+class SdyTimeCovarianceStatsArgs(_SizedStructure):
+    """`sdy_time_covariance_stats_args`: the weighted sums of every pair of the groups of one K."""
+    _fields_ = [
+        ("struct_size", C.c_size_t),
+        ("K", C.c_int), ("n_groups", C.c_int),
+        ("M", C.c_int), ("n1", C.c_int), ("HW", C.c_int),
+        ("sums", C.c_void_p), ("products", C.c_void_p), ("weights", C.c_void_p),
+        ("n_times", C.c_double),
+        ("out", C.c_void_p),
+        ("ws", C.c_void_p), ("ws_bytes", C.c_size_t),
+    ]
+
+
 SDY_GRAM_MAX_MEMBERS = 64
 
 
@@ -678,6 +722,13 @@ SIGNATURES = {
     "sdy_spacetime_segment_power": (C.c_int, [C.POINTER(SdySpacetimeSegmentPowerArgs), C.c_void_p]),
     "sdy_spacetime_segment_power_host": (C.c_int, [C.POINTER(SdySpacetimeSegmentPowerArgs)]),
     "sdy_spacetime_workspace_bytes": (C.c_size_t, [C.c_int] * 6),
+    "sdy_time_covariance_accumulate": (C.c_int, [C.POINTER(SdyTimeCovarianceArgs), C.c_void_p]),
+    "sdy_time_covariance_accumulate_host": (C.c_int, [C.POINTER(SdyTimeCovarianceArgs)]),
+    "sdy_time_covariance_maps": (C.c_int, [C.POINTER(SdyTimeCovarianceMapsArgs), C.c_void_p]),
+    "sdy_time_covariance_maps_host": (C.c_int, [C.POINTER(SdyTimeCovarianceMapsArgs)]),
+    "sdy_time_covariance_stats": (C.c_int, [C.POINTER(SdyTimeCovarianceStatsArgs), C.c_void_p]),
+    "sdy_time_covariance_stats_host": (C.c_int, [C.POINTER(SdyTimeCovarianceStatsArgs)]),
+    "sdy_time_covariance_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "sdy_fss_accumulate": (C.c_int, [C.POINTER(SdyFssArgs), C.c_void_p]),
     "sdy_fss_accumulate_host": (C.c_int, [C.POINTER(SdyFssArgs)]),
     "sdy_fss_encode": (C.c_int, [C.POINTER(SdyFssArgs), C.c_void_p]),

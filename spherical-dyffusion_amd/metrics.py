@@ -27,6 +27,7 @@ from .field_scores import FieldScoreAggregator
 from .regions import RegionalMeanAggregator, Regions
 from .spectrum import KineticEnergySpectrumAggregator, PowerSpectrumAggregator
 from .variability import TimeVariabilityAggregator
+from .eddies import CovarianceGroups, EddyCovarianceAggregator
 from .windows import FieldAccumulator, TorchDistributed, fill_window, whole_ics_message, window_layouts  # noqa: F401
 
 
@@ -634,7 +635,15 @@ class InferenceAggregator:
     target in an equatorial band, symmetric and antisymmetric about the equator, read with `get_space_time_spectrum_data()`,
     and `power_gen`, `power_target` and `power_ratio` per band (and `east_west_ratio_gen` / `east_west_ratio_target`) under
     `<label>/space_time_spectra/...`.  Its windows must arrive in run order.  The default `None` adds nothing: the default key
-    set of the logs does not change."""
+    set of the logs does not change.
+
+    `eddy_covariances=<sdy_amd.CovarianceGroups>` adds `eddy_covariance` (`sdy_amd.EddyCovarianceAggregator` on the
+    denormalised data of the groups' variables): per member and for the target the covariance and the correlation along time
+    of every pair of a group's variables at every grid point -- u'v', v'T', v'q', the eddy kinetic energy -- read with
+    `get_eddy_covariance_data(label, a, b)`, and `cov_gen`, `cov_target`, `cov_bias`, `cov_rmse`, `corr_gen`, `corr_target`,
+    `corr_bias` and `corr_defined_fraction` per group and pair, `time_variance_gen` / `time_variance_target` per group and
+    variable and `eke_gen`, `eke_target`, `eke_ratio` per group with winds under `<label>/eddy_covariance/...`.  Its windows
+    must arrive in run order.  The default `None` adds nothing: the default key set of the logs does not change."""
 
     accepts_sample_weights = True
 
@@ -649,7 +658,8 @@ class InferenceAggregator:
                  regions: Optional[Regions] = None, events: Optional[Events] = None, event_pool_times: bool = False,
                  event_frequency_maps: bool = False, field_scores: bool = False, climatology=None,
                  event_neighbourhoods: Optional[Sequence[int]] = None, wind_pairs=None,
-                 space_time_spectra: Optional[SpaceTimeSpectra] = None, event_spells: bool = False,
+                 space_time_spectra: Optional[SpaceTimeSpectra] = None,
+                 eddy_covariances: Optional[CovarianceGroups] = None, event_spells: bool = False,
                  time_quantiles: Optional[Sequence[float]] = None,
                  time_quantile_variables: Optional[Sequence[str]] = None):
         if log_video or enable_extended_videos or log_zonal_mean_images:
@@ -716,6 +726,9 @@ class InferenceAggregator:
         if space_time_spectra is not None:
             self._aggregators["space_time_spectra"] = SpaceTimeSpectrumAggregator(space_time_spectra, dist=dist,
                                                                                   target="denorm", metadata=metadata)
+        if eddy_covariances is not None:
+            self._aggregators["eddy_covariance"] = EddyCovarianceAggregator(eddy_covariances, area_weights, dist=dist,
+                                                                            target="denorm", metadata=metadata)
 
     @torch.no_grad()
     def record_batch(self, loss, target_data, gen_data, target_data_norm, gen_data_norm, i_time_start: int = 0,
@@ -783,6 +796,10 @@ class InferenceAggregator:
     def get_space_time_spectrum_data(self):
         """`SpaceTimeSpectrumAggregator.get_data()` of the run (`space_time_spectra=...`)."""
         return self._aggregators["space_time_spectra"].get_data()
+
+    def get_eddy_covariance_data(self, label: str, a: str, b: str):
+        """`EddyCovarianceAggregator.get_pair_data(label, a, b)` of the run (`eddy_covariances=...`)."""
+        return self._aggregators["eddy_covariance"].get_pair_data(label, a, b)
 
     def get_field_scores(self):
         """`FieldScoreAggregator.get_series()` of the run (`field_scores=True`)."""

@@ -3,7 +3,7 @@ the layouts of a window's variables (`WindowLayout`, the Python side of `sdy_win
 variables one launch takes, and `FieldAccumulator`, the float64 accumulators that stay on the device.
 
 This module sits below `metrics`, `histogram`, `data_writer`, `spectrum`, `member_mean`, `rank_hist`, `events`, `fss`, `spells`,
-`variability`, `regions`, `field_scores`, `quantiles` and `spacetime` and imports none of them.
+`variability`, `eddies`, `regions`, `field_scores`, `quantiles` and `spacetime` and imports none of them.
 """
 from __future__ import annotations
 
@@ -179,8 +179,9 @@ def check_same_job(names: Sequence[str], jobs: Sequence[tuple], first_names: Seq
 
 class FieldAccumulator:
     """What `VideoAggregator`, `ZonalMeanAggregator`, `PowerSpectrumAggregator`, `EnsembleTimeMeanAggregator`,
-    `RankHistogramAggregator`, `EventVerificationAggregator`, `FractionsSkillAggregator`, `EventSpellAggregator` and
-    `TimeVariabilityAggregator` share: the float64 accumulators (`self._acc[stat]`: one flat device buffer per statistic, the variables' blocks in dict order at
+    `RankHistogramAggregator`, `EventVerificationAggregator`, `FractionsSkillAggregator`, `EventSpellAggregator`,
+    `TimeVariabilityAggregator` and (the memory limit, the ranks and the same-job rule; its state is per group)
+    `EddyCovarianceAggregator` share: the float64 accumulators (`self._acc[stat]`: one flat device buffer per statistic, the variables' blocks in dict order at
     `self._offsets[stat]`, so a run of same-shaped variables is one contiguous `(nvars, ...)` block: what one launch takes),
     the memory limit, the device check and the same-job check.  Everything is checked before anything changes: a refused
     window leaves the aggregator as it was.
