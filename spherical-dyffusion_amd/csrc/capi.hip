@@ -114,14 +114,15 @@ struct sdy_sht_plan {
 // SDY_NO_PAIR, SDY_NO_CONV_FRAG -- the paths they selected are still what other shapes take, and are tested there.)
 namespace {
 struct SdySwitches {
-  bool gemm_f32, no_fft360, no_leg_par, no_leg_frag, no_dh_frag, no_fused_mlp, no_drop_skip, no_skip_fold;
+  bool gemm_f32, no_fft360, no_leg_par, no_leg_frag, no_dh_frag, no_fused_mlp, no_drop_skip, no_skip_fold, no_conv_ws;
 };
 const SdySwitches& sw() {
   static const SdySwitches v = [] {
     auto on = [](const char* n) { return std::getenv(n) != nullptr; };
     const char* g = std::getenv("SDY_GEMM_MODE");
     return SdySwitches{g && std::string(g) == "f32", on("SDY_NO_FFT360"), on("SDY_NO_LEG_PAR"), on("SDY_NO_LEG_FRAG"),
-                       on("SDY_NO_DH_FRAG"), on("SDY_NO_FUSED_MLP"), on("SDY_NO_DROP_SKIP"), on("SDY_NO_SKIP_FOLD")};
+                       on("SDY_NO_DH_FRAG"), on("SDY_NO_FUSED_MLP"), on("SDY_NO_DROP_SKIP"), on("SDY_NO_SKIP_FOLD"),
+                       on("SDY_NO_CONV_WS")};
   }();
   return v;
 }
@@ -621,7 +622,8 @@ extern "C" int sdy_h3_pack_weight(const float* w, int Cout, int Cin, void* packe
   return SDY_OK;
 }
 
-extern "C" int sdy_conv1x1(const sdy_conv_args* a, void* stream) {
+// conv_ws: the inner-skip form of the persistent kernel runs weight-stationary (BlockPath::conv_ws; SDY_NO_CONV_WS=1: the ring)
+static int conv1x1(const sdy_conv_args* a, void* stream, bool conv_ws) {
   if (!a || !a->x || (!a->wt && !a->w_h3 && !a->w_frag) || !a->out) return SDY_ERR_ARG;
   if (a->B <= 0 || a->Cin <= 0 || a->Cout <= 0 || a->HW <= 0) return SDY_ERR_ARG;
   if (!a->w_h3 && a->ldw < a->Cout) return SDY_ERR_ARG;
@@ -630,7 +632,7 @@ extern "C" int sdy_conv1x1(const sdy_conv_args* a, void* stream) {
   if ((!a->w_h3 && (a->ldw & 3)) || (a->HW & 3) || (a->x_bstride & 3) || (a->out_bstride & 3)) return SDY_ERR_ALIGN;
   if (a->drop_p < 0.0f || a->drop_p >= 1.0f) return SDY_ERR_ARG;
   if (a->w_frag && sdy_conv256_h3_supported(a->Cin, a->Cout) && a->drop_p == 0.0f && !a->keep_mask && !a->batch_scale)
-    return sdy_conv256_h3_launch(a, (hipStream_t)stream);
+    return sdy_conv256_h3_launch(a, (hipStream_t)stream, conv_ws ? 1 : 0);
   // statistics, the tile-major output and the image map exist in the persistent kernel only
   if (a->stats || a->out_tiled || a->x_rows) return SDY_ERR_UNSUPPORTED;
   GemmParams g{};
@@ -661,6 +663,7 @@ extern "C" int sdy_conv1x1(const sdy_conv_args* a, void* stream) {
   }
   return sdy_gemm_launch(g, (hipStream_t)stream);
 }
+extern "C" int sdy_conv1x1(const sdy_conv_args* a, void* stream) { return conv1x1(a, stream, !sw().no_conv_ws); }
 
 extern "C" int sdy_cold_update(const float* x_s, const float* x_ip_next, const float* x_ip_s, float* out, size_t n,
                                void* stream) {
@@ -767,6 +770,7 @@ struct BlockPath {
   // x = GELU(y + inner_skip(residual)): a convolution, or with the skip folded into the dhconv a GELU pass over y, or nothing
   enum Skip { SKIP_CONV, SKIP_GELU, SKIP_IN_FFT } skip;
   bool stats1;             // norm1 statistics from the inner-skip convolution's epilogue (conv_h3)
+  bool conv_ws;            // the inner-skip convolution holds its weight in registers (conv_h3, WS form); SDY_NO_CONV_WS=1: the ring
   // The tensor between the inner skip and the fused MLP has exactly one producer and one consumer, both walking 64-pixel
   // tiles: it is stored TILE-MAJOR (a tile = one contiguous 64 KB block for the stores of one and the loads of the other).
   bool z_tiled;
@@ -1101,6 +1105,7 @@ static BlockPath resolve_path(const sdy_sfno* n, int i) {
   const bool dh_frag = b.dh == DH_FOLDED || b.dh == DH_FRAG;
   b.cs_tiled = b.in.tiled && b.out.tiled && dh_frag && b.in.plan->lmax == b.out.plan->lmax && b.in.plan->mtr == b.out.plan->mtr;
   b.stats1 = c.gemm_mode == 1 && w.skw.frag && sdy_conv256_h3_supported(E, E);
+  b.conv_ws = b.stats1 && !sw().no_conv_ws;
   b.z_tiled = b.stats1 && b.fused_mlp;
   b.skip = b.dh != DH_FOLDED ? BlockPath::SKIP_CONV : (b.out.tiled && b.z_tiled) ? BlockPath::SKIP_IN_FFT : BlockPath::SKIP_GELU;
   // the drop-path skip needs the row map of fft360, dh_h3, conv_h3 and mlp_h3; SDY_NO_DROP_SKIP=1 computes every row
@@ -1600,7 +1605,7 @@ struct SfnoCall {
       cv.ldw = E; cv.out = k.z; cv.out_bstride = k.z_bs; cv.out_tiled = P.z_tiled ? 1 : 0;
       cv.Cin = E; cv.Cout = E; cv.bias = bw.skb.p; cv.add = y; cv.add_bstride = xbs; cv.add_mode = 1; cv.act = 1; cv.kernel_tag = 3;
       if (P.stats1) cv.stats = st1;
-      SDY_STAGE_N(ST_SKIP_CONV, k.Bp, sdy_conv1x1(&cv, stream));
+      SDY_STAGE_N(ST_SKIP_CONV, k.Bp, conv1x1(&cv, stream, P.conv_ws));
     }
     // norm1 (sfnonet.py:313-320) folded into the fc1 prologue; its statistics come from the pass that produced x
     if (P.skip == BlockPath::SKIP_GELU || P.stats1)

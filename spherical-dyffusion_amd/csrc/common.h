@@ -421,7 +421,8 @@ int sdy_gemm_h3_launch(const GemmParams& p, const void* packed, int rows_pad, in
                        float w_scale, int rows_mode, hipStream_t stream);
 
 // ---- persistent 256 -> 256 convolution (conv_h3.hip)
-int sdy_conv256_h3_launch(const sdy_conv_args* a, hipStream_t stream);
+int sdy_conv256_h3_launch(const sdy_conv_args* a, hipStream_t stream, int ws);   // ws: weight-stationary kernel where the form fits
+int sdy_conv256_h3_ws_form(const sdy_conv_args* a);
 extern "C" int sdy_conv256_h3_pack_cin(const float* w_host, int Cin, void* dev, float* scale);   // (256, Cin) weight, Cin <= 384
 extern "C" size_t sdy_conv256_h3_pack_bytes_cin(int Cin);
 // dh_h3.hip: fragment-stream pack of the dhconv weight; ilv = channel order of the 2C axis (fft.h)

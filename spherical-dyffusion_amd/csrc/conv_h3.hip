@@ -12,6 +12,10 @@
 // Cin <= 256: 4 waves, <= 256 registers, 69 KB of LDS -> TWO workgroups per CU.  They are independent (no barrier couples
 // them), drift apart, and one's MFMA phase / barriers / LDS passes run under the other's HBM traffic (+2..7 % over one
 // 8-wave workgroup per CU).  256 < Cin <= 384 (decoder: [block output | inputs]): 8 waves, one workgroup per CU, 96 KB tile.
+// WEIGHT-STATIONARY form (WS, the block's inner skip: Cin = 256, addend before the GELU): 8 waves, one workgroup per CU, and
+// wave v keeps the fragments of its 32 output rows for all 16 k-steps in 128 registers, loaded once per launch (the whole
+// 256 x 256 x (hi, lo) weight is half of a CU's register file).  No weight load is left in the tile loop, so vmcnt counts
+// HBM traffic only and the tile's addend rows are requested BEFORE the MFMA loop and travel under it.
 #include <cmath>
 #include <cstdlib>
 #include <type_traits>
@@ -80,9 +84,11 @@ __device__ __forceinline__ int cv_off(int px, int c) { return px * KROW + (((c &
 
 // KBLK = ceil(Cin / 64): k-blocks of 4 k-steps actually streamed (4 for the block's 256 -> 256 convs, 2 / 3 for the
 // encoders, 6 for the decoder)
-template <int KBLK, int NW>
+template <int KBLK, int NW, bool WS = false>
 __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void conv_h3_kernel(const ConvParams p) {
   using G = ConvCfg<KBLK, NW>;
+  static_assert(!WS || (KBLK == 4 && NW == 8), "weight-stationary: 256 input channels on 8 waves");
+  constexpr int RING = WS ? G::KSW : CRING;   // WS: the wave's whole stream (16 groups), never refilled
   constexpr int CMT = G::MT, CRS = G::RS, COC = G::OC, CRPT = G::RPT, KROW = G::KROW, CGPK = G::GPK, CGPW = G::GPW;
   __shared__ __attribute__((aligned(16))) unsigned char smem[G::LDS_BYTES];   // x tile (64 / 96 KB) + 4 KB + 1 KB
   _Float16* Xs_hi = reinterpret_cast<_Float16*>(smem);
@@ -90,6 +96,12 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void conv_h3_kernel(const
   float* Os = reinterpret_cast<float*>(smem);   // epilogue: [256 rows][64 px] fp32 (aliases the x tile)
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  // WS: all 256 input channels, addend before the table GELU -- known at compile time.  A conditional pixel load would keep
+  // the previous tile's pixels live across the MFMA loop (32 registers), and hipcc counts vmcnt past a conditional access as
+  // if it had not been issued: the waits of the last store-loop steps would drain the queue.
+  auto Cin = [&] { return WS ? CE : p.Cin; };
+  auto add_mode = [&] { return WS ? 1 : p.add_mode; };
+  auto act = [&] { return WS ? 1 : p.act; };
   int h = lane >> 5, l31 = lane & 31;
   int q0 = tid & 15, o0 = tid >> 4;
   const int tpi = (p.HW + CTN - 1) / CTN;
@@ -100,20 +112,24 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void conv_h3_kernel(const
   const int t_begin = (int)blockIdx.x * t_per;
   const int t_end = (t_begin + t_per < ntiles) ? t_begin + t_per : ntiles;
 
-  sdy_f16x8 r_hi[CRING], r_lo[CRING];
+  sdy_f16x8 r_hi[RING], r_lo[RING];
   // ring loads: (wave-uniform stream base in SGPRs) + (the lane's running offset), sdy_ring_ld in common.h; the stream of a
   // tile (NWIN windows of CRING groups) is fetched front to back, one window ahead of its use, and wraps
   constexpr int CGROUP_BYTES = SDY_GROUP * (int)sizeof(sdy_f16x8);
-  const char* const wbase = reinterpret_cast<const char*>(p.w) + (size_t)__builtin_amdgcn_readfirstlane(wave) * CGPW * CGROUP_BYTES;
+  // WS reads the 4-wave stream of the 256 -> 256 weight ([w][ks][mi], rows 32 (2 w + mi) ..): wave v = 2 w + mi owns groups
+  // 32 w + 2 ks + mi, ks = 0 .. 15
+  const int uwave = __builtin_amdgcn_readfirstlane(wave);
+  const char* const wbase = reinterpret_cast<const char*>(p.w) +
+                            (WS ? (size_t)((uwave >> 1) * 2 * G::KSW + (uwave & 1)) * CGROUP_BYTES : (size_t)uwave * CGPW * CGROUP_BYTES);
   unsigned woff = (unsigned)lane * 16u;
 #pragma unroll
-  for (int s = 0; s < CRING; ++s) {
+  for (int s = 0; s < RING; ++s) {
     r_hi[s] = sdy_ring_ld(wbase, woff, 0);
     r_lo[s] = sdy_ring_ld(wbase, woff, CGROUP_BYTES / 2);
-    woff += CGROUP_BYTES;
+    woff += (WS ? 2 : 1) * CGROUP_BYTES;
   }
   constexpr int NWIN = KBLK * CMT;                     // windows of CRING groups per tile
-  if (NWIN == 1) woff -= CRING * CGROUP_BYTES;         // (the ring holds the whole stream: its refills fetch it again)
+  if (!WS && NWIN == 1) woff -= CRING * CGROUP_BYTES;         // (the ring holds the whole stream: its refills fetch it again)
 
   // bias: pre-divided by out_scale and parked in LDS once; the accumulators START from it (no registers across tiles, no
   // add in the store loop).  Statistics: [256 rows][sum, sum of squares] fp64.
@@ -126,16 +142,19 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void conv_h3_kernel(const
   // GELU table (plain gelu: coefficients / 16); the store loop then works on w = 8 v, the accumulator pass scales by 8
   float* Gt = reinterpret_cast<float*>(smem + G::TILE_BYTES + CSTAT_BYTES + CE * 4);
   const unsigned gt_base = (unsigned)(uintptr_t)Gt;
-  const bool tab_gelu = SDY_CONV_GELU_TAB && p.act == 1;
+  const bool tab_gelu = SDY_CONV_GELU_TAB && act() == 1;
   if (tab_gelu) gelu_tab_to_lds(Gt, p.gelu_tab, tid, G::NT, 1.0f / SDY_GELU_SX);
   const float os_scale = tab_gelu ? p.out_scale * SDY_GELU_WS : p.out_scale;
   // (ordered before their first use by the barrier that ends the first tile's phase 0)
 
-  // Software pipeline over tiles.  Loads are issued ONE per step where they ride on other work, never as a burst inside
+  // Software pipeline over tiles, ring form.  Loads are issued ONE per step where they ride on other work, never as a burst inside
   // the MFMA phase: tile t+1's pixels (xr) ride on tile t's store loop; tile t's addend rows are requested when its MFMA
   // loop has ended (their registers are the accumulators' until then) and travel during the accumulator pass through LDS;
   // the MFMA phase only streams the L2-resident weight ring (vmcnt retires in order: an HBM load issued there makes the
   // ring wait, measured 7.6k -> 12k cycles).
+  // WS has no weight load in the tile loop, so vmcnt counts HBM traffic only and both streams are requested as bursts: tile
+  // t's addend rows ahead of its MFMA loop (they travel under it), tile t+1's pixels when the loop has ended (the B fragments'
+  // registers are free; they travel under the barrier, the accumulator pass and the store loop).  The store loop only stores.
   f32x4 xr[COC][8], addv[CRPT];
   // Addressing: every global access is (wave-uniform base of the image and row: SGPR arithmetic) + (ONE 32-bit byte offset per
   // lane and tile), the SADDR form of global_load / global_store -- per-row 64-bit lane addresses (16 rows x 3 streams) would
@@ -157,7 +176,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void conv_h3_kernel(const
       for (int e = 0; e < 8; ++e) {
         const int ch = 8 * (o0 + CRS * oc) + e;
         xr[oc][e] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (ch < p.Cin) xr[oc][e] = sdy_ld16s(xz + (long)(8 * CRS * oc + e) * p.HW, xo);   // channels past Cin: no load
+        if (WS || ch < Cin()) xr[oc][e] = sdy_ld16s(xz + (long)(8 * CRS * oc + e) * p.HW, xo);   // channels past Cin: no load
       }
   }
 
@@ -203,7 +222,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void conv_h3_kernel(const
           sdy_f16x8 vh, vl;
           float v[8];
 #pragma unroll
-          for (int e = 0; e < 8; ++e) v[e] = (ok && c0 + e < p.Cin) ? fmaf(xr[oc][e][pp], av[e], dv[e]) : 0.0f;
+          for (int e = 0; e < 8; ++e) v[e] = (ok && (WS || c0 + e < Cin())) ? fmaf(xr[oc][e][pp], av[e], dv[e]) : 0.0f;
           sdy_split8(v, vh, vl, amax);
           const int off = cv_off<KROW>(4 * q0 + pp, o0 + CRS * oc);
           *reinterpret_cast<sdy_f16x8*>(Xs_hi + off) = vh;
@@ -223,6 +242,12 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void conv_h3_kernel(const
     const int tnext = (tile + 1 < t_end) ? tile + 1 : tile;   // past the end: a harmless re-read
     const float* xz_next = ximg(tnext);
     const unsigned xo_next = (unsigned)(8 * o0 * p.HW + lane_col(tnext)) * 4u;
+    if constexpr (WS) {   // no load shares vmcnt with these in the MFMA loop: they travel under it
+      const float* az = img(p.add, p.add_bs, tile);   // (the WS form has an addend)
+#pragma unroll
+      for (int i = 0; i < CRPT; ++i) addv[i] = sdy_ld16s(az + (long)(CRS * i) * p.HW, ro);
+      __builtin_amdgcn_sched_barrier(0);
+    }
     stamp(2);
     // ---- MFMA phase: rows 32 CMT wave .. + 32 CMT, all 64 px, K = 64 KBLK
     f32x16 acc[CMT][2];
@@ -236,6 +261,30 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void conv_h3_kernel(const
 #pragma unroll
           for (int r = 0; r < 4; ++r) acc[mi][j][4 * r4 + r] = b4[r];
       }
+    auto ld_b = [&](int ks, sdy_f16x8* bh, sdy_f16x8* bl) {   // B fragments of k-step ks, both pixel tiles
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int off = cv_off<KROW>(32 * j + l31, 2 * ks + h);
+        bh[j] = *reinterpret_cast<const sdy_f16x8*>(Xs_hi + off);
+        bl[j] = *reinterpret_cast<const sdy_f16x8*>(Xs_lo + off);
+      }
+    };
+    if constexpr (WS) {
+      // the weight is in registers: the only loads of the loop are the B fragments, one k-step ahead of their use
+      sdy_f16x8 bh[2][2], bl[2][2];
+      ld_b(0, bh[0], bl[0]);
+      sdy_static_for<0, G::KSW>([&](auto ks_c) {
+        constexpr int ks = decltype(ks_c)::value, c = ks & 1;
+        if constexpr (ks + 1 < G::KSW) ld_b(ks + 1, bh[c ^ 1], bl[c ^ 1]);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) SDY_CROSS_TERM(acc[0][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(r_lo[ks], bh[c][j], acc[0][j], 0, 0, 0));
+#pragma unroll
+        for (int j = 0; j < 2; ++j) SDY_CROSS_TERM(acc[0][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(r_hi[ks], bl[c][j], acc[0][j], 0, 0, 0));
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc[0][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(r_hi[ks], bh[c][j], acc[0][j], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);   // one k-step of fragments in flight, no more (registers)
+      });
+    } else {
     // The stream is consumed in windows of CRING groups; while window c is consumed its slots are refilled with window
     // c + 1, and the last window's refills fetch window 0 again, so the ring is ready for the next tile.
 #pragma unroll
@@ -244,12 +293,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void conv_h3_kernel(const
       for (int i = 0; i < 4; ++i) {
         const int ks = 4 * kb + i;
         sdy_f16x8 bh[2], bl[2];
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          const int off = cv_off<KROW>(32 * j + l31, 2 * ks + h);
-          bh[j] = *reinterpret_cast<const sdy_f16x8*>(Xs_hi + off);
-          bl[j] = *reinterpret_cast<const sdy_f16x8*>(Xs_lo + off);
-        }
+        ld_b(ks, bh, bl);
 #pragma unroll
         for (int mi = 0; mi < CMT; ++mi) {
           const int g = kb * CGPK + CMT * i + mi;   // group of the tile's stream
@@ -268,9 +312,15 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void conv_h3_kernel(const
         }
       }
     }
+    }
 
     stamp(3);
-    {   // this tile's addend rows (defined on both paths: not live across the MFMA loop)
+    if constexpr (WS) {   // the next tile's pixels (COC = 1: channels 8 o0 + e)
+      static_assert(!WS || COC == 1, "one channel octet per thread");
+#pragma unroll
+      for (int e = 0; e < 8; ++e) xr[0][e] = sdy_ld16s(xz_next + (long)e * p.HW, xo_next);
+      __builtin_amdgcn_sched_barrier(0);
+    } else {   // this tile's addend rows (defined on both paths: not live across the MFMA loop)
       const float* az = img(addsrc, addsrc_bs, tile);
 #pragma unroll
       for (int i = 0; i < CRPT; ++i) addv[i] = p.add ? sdy_ld16s(az + (long)(CRS * i) * p.HW, ro) : f32x4{0.f, 0.f, 0.f, 0.f};
@@ -295,16 +345,16 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void conv_h3_kernel(const
       for (int i = 0; i < CRPT; ++i) {
         f32x4 v = *reinterpret_cast<const f32x4*>(Os + (o0 + CRS * i) * CTN + 4 * q0);
         if (tab_gelu) {   // (workgroup-uniform) v holds 8 x the pre-activation: 10 plain VALU instructions per value, no v_rcp / v_exp
-          if (p.add_mode == 1) v = addv[i] * SDY_GELU_WS + v;
+          if (add_mode() == 1) v = addv[i] * SDY_GELU_WS + v;
           v = f32x4{gelu_tab16(v.x, gt_base), gelu_tab16(v.y, gt_base), gelu_tab16(v.z, gt_base), gelu_tab16(v.w, gt_base)};
         } else {
-        if (p.add_mode == 1) v += addv[i];
-        if (p.act == 1) {
+        if (add_mode() == 1) v += addv[i];
+        if (act() == 1) {
           const sdy_gf2 g0 = gelu_erf2(sdy_gf2{v.x, v.y}), g1 = gelu_erf2(sdy_gf2{v.z, v.w});
           v = f32x4{g0.x, g0.y, g1.x, g1.y};
         }
         }
-        if (p.add_mode == 2) v += addv[i];
+        if (add_mode() == 2) v += addv[i];
         if (c_ok) sdy_st16s(oz + (long)(CRS * i) * out_rs, ro_out, v);
         // next tile's pixels, a piece (or two) per step (every lane: a lane beyond a ragged tile's edge still owns pixels of
         // the next tile)
@@ -313,12 +363,15 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void conv_h3_kernel(const
           const int piece = G::PPI * i + k, oc = piece >> 3, e = piece & 7;
           if (oc < COC) {
             const int ch = 8 * (o0 + CRS * oc) + e;
-            if (ch < p.Cin) xr[oc][e] = sdy_ld16s(xz_next + (long)(8 * CRS * oc + e) * p.HW, xo_next);
+            if constexpr (!WS)
+              if (ch < Cin()) xr[oc][e] = sdy_ld16s(xz_next + (long)(8 * CRS * oc + e) * p.HW, xo_next);
           }
         }
         if (p.stats) {   // (workgroup-uniform)
-          const float s1 = row16_sum(c_ok ? (v.x + v.y) + (v.z + v.w) : 0.0f);
-          const float s2 = row16_sum(c_ok ? (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w) : 0.0f);
+          // (explicit FMAs, common.h: left to -ffp-contract the ring form came out as fma(x, x, y * y), the weight-stationary
+          //  form as x * x + y * y, and the two kernels' statistics differed in the last fp32 bit of every quad)
+          const float s1 = row16_sum(c_ok ? sdy_quad_sum(v) : 0.0f);
+          const float s2 = row16_sum(c_ok ? sdy_quad_sumsq(v) : 0.0f);
           if (q0 == 0) {   // the one owner of this row in the workgroup
             double* st = Ss + 2 * (o0 + CRS * i);
             __hip_atomic_fetch_add(st, (double)s1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -399,15 +452,20 @@ extern "C" int sdy_conv256_h3_pack(const float* w_host, void* dev, float* scale)
   return sdy_conv256_h3_pack_cin(w_host, CE, dev, scale);
 }
 
-template <int KBLK, int NW>
+template <int KBLK, int NW, bool WS = false>
 static void conv_launch(const ConvParams& p, long ntiles, int n_cu, hipStream_t stream) {
   using G = ConvCfg<KBLK, NW>;
   const long want = (long)n_cu * G::WGS;   // persistent: WGS workgroups per CU
   dim3 grid((unsigned)(ntiles < want ? ntiles : want));
-  hipLaunchKernelGGL((conv_h3_kernel<KBLK, NW>), grid, dim3(G::NT), 0, stream, p);
+  hipLaunchKernelGGL((conv_h3_kernel<KBLK, NW, WS>), grid, dim3(G::NT), 0, stream, p);
 }
 
-int sdy_conv256_h3_launch(const sdy_conv_args* a, hipStream_t stream) {
+// the block's inner skip, the one form the weight-stationary kernel is built for: 256 -> 256, addend before the table GELU
+int sdy_conv256_h3_ws_form(const sdy_conv_args* a) {
+  return a && SDY_CONV_GELU_TAB && a->Cin == CE && a->Cout == CE && a->add_mode == 1 && a->add && a->act == 1;
+}
+
+int sdy_conv256_h3_launch(const sdy_conv_args* a, hipStream_t stream, int ws) {
   if (!a || !a->x || !a->w_frag || !a->out || a->B <= 0 || a->HW <= 0) return SDY_ERR_ARG;
   if (!sdy_conv256_h3_supported(a->Cin, a->Cout)) return SDY_ERR_UNSUPPORTED;
   if (a->drop_p > 0.f || a->keep_mask || a->batch_scale) return SDY_ERR_UNSUPPORTED;
@@ -443,7 +501,10 @@ int sdy_conv256_h3_launch(const sdy_conv_args* a, hipStream_t stream) {
     case 1: conv_launch<1, 4>(p, ntiles, n_cu, stream); break;
     case 2: conv_launch<2, 4>(p, ntiles, n_cu, stream); break;
     case 3: conv_launch<3, 4>(p, ntiles, n_cu, stream); break;
-    case 4: conv_launch<4, 4>(p, ntiles, n_cu, stream); break;
+    case 4:
+      if (ws && sdy_conv256_h3_ws_form(a)) conv_launch<4, 8, true>(p, ntiles, n_cu, stream);
+      else conv_launch<4, 4>(p, ntiles, n_cu, stream);
+      break;
     case 5: conv_launch<5, 8>(p, ntiles, n_cu, stream); break;
     default: conv_launch<6, 8>(p, ntiles, n_cu, stream); break;
   }

@@ -90,11 +90,19 @@ def conv1x1(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] 
             drop_p: float = 0.0, keep_mask: Optional[torch.Tensor] = None, seed: int = 0, call: int = 0,
             stream_id: int = 0, batch_offset: int = 0, batch_scale: Optional[torch.Tensor] = None,
             kernel_tag: int = 0, out: Optional[torch.Tensor] = None, wt_prepared=None, h3: bool = False,
-            h3_prepared=None, frag_prepared=None, stats: Optional[torch.Tensor] = None) -> torch.Tensor:
+            h3_prepared=None, frag_prepared=None, stats: Optional[torch.Tensor] = None,
+            x_rows=None, out_tiled: bool = False) -> torch.Tensor:
     """nn.Conv2d(kernel_size=1) with the block's fused prologue/epilogue (see include/sdy_amd.h, sdy_conv1x1).
-    x (B,Cin,H,W), weight (Cout,Cin[,1,1])."""
+    x (B,Cin,H,W), weight (Cout,Cin[,1,1]).  frag_prepared only: `x_rows` (a sequence of batch rows of x / pre_affine) makes
+    the launch len(x_rows) images long, image z reading row x_rows[z] (add, out and stats stay indexed by z); `out_tiled`
+    returns the tile-major tensor (B, ceil(H W / 64), Cout, 64), the padding of an image's last tile left unwritten."""
     x = _f32c(x)
     B, Cin, H, W = x.shape
+    rows_host = None
+    if x_rows is not None:
+        assert all(0 <= int(r) < B for r in x_rows)
+        rows_host = (C.c_ubyte * len(x_rows))(*[int(r) for r in x_rows])
+        B = len(x_rows)
     w2 = weight.detach().to(torch.float32).reshape(weight.shape[0], -1)
     Cout = w2.shape[0]
     assert w2.shape[1] == Cin
@@ -105,11 +113,15 @@ def conv1x1(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] 
         wt = torch.zeros(Cin, ldw, dtype=torch.float32, device=x.device)
         wt[:, :Cout] = w2.t().to(x.device)
     if out is None:
-        out = torch.empty(B, Cout, H, W, dtype=torch.float32, device=x.device)
+        shape = (B, (H * W + 63) // 64, Cout, 64) if out_tiled else (B, Cout, H, W)
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
     a = SdyConvArgs()
     a.x, a.x_bstride = ptr(x), Cin * H * W
     a.wt, a.ldw = ptr(wt), ldw
-    a.out, a.out_bstride = ptr(out), Cout * H * W
+    a.out, a.out_bstride = ptr(out), out.numel() // B if out_tiled else Cout * H * W
+    a.out_tiled = 1 if out_tiled else 0
+    if rows_host is not None:
+        a.x_rows = C.addressof(rows_host)
     a.B, a.Cin, a.Cout, a.HW = B, Cin, Cout, H * W
     keep = [x, wt, out]
     if h3 or h3_prepared is not None:     # split-fp16 3-pass MFMA path (include/sdy_amd.h, sdy_h3_pack_weight)

@@ -1,7 +1,19 @@
-"""Times the persistent 256->256 conv kernel against the tile GEMM (run on the GPU box)."""
-import sys, os
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+"""Times the persistent 256->256 conv kernels -- weight-stationary and ring -- against the tile GEMM (run on the GPU box).
+
+The kernel-selection switch SDY_NO_CONV_WS is read once per process, so each kernel is timed in a child process of its own
+(`--one` is that child; the parent never touches the GPU).  SDY_CONV_STAMPS=1 with a -DSDY_STAMPS build prints the phase stamps
+of whichever kernel the process runs."""
+import sys, os, subprocess
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if "--one" not in sys.argv:
+    for tag, extra in (("weight-stationary", {}), ("ring", {"SDY_NO_CONV_WS": "1"})):
+        env = dict(os.environ); env.pop("SDY_NO_CONV_WS", None); env.update(extra)
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--one", tag] + sys.argv[1:], env=env)
+        if r.returncode: sys.exit(r.returncode)
+    sys.exit(0)
+sys.path.insert(0, ROOT)
 import torch, sdy_amd as sdy
+tag = sys.argv[sys.argv.index("--one") + 1]
 def timeit(fn, n=10):
     for _ in range(2): fn()
     torch.cuda.synchronize()
@@ -21,8 +33,10 @@ out = torch.empty_like(x)
 f = lambda: sdy.ops.conv1x1(x, w, bias, pre_affine=(pa, pd), add=y, add_mode=1, gelu=True, frag_prepared=frag, stats=st, out=out, wt_prepared=out)
 u = lambda: sdy.ops.conv1x1(x, w, bias, pre_affine=(pa, pd), add=y, add_mode=1, gelu=True, h3_prepared=h3, out=out, wt_prepared=out, kernel_tag=3)
 s = lambda: sdy.ops.instnorm_coeffs(out, bias, bias)
-tf, tu, ts = timeit(f), timeit(u), timeit(s)
-print(f"conv_h3 (with stats) {tf:.3f} ms ({3*B*E*H*W*4/tf/1e6:.0f} GB/s) | tile GEMM {tu:.3f} ms + stats pass {ts:.3f} ms")
+tf = [timeit(f) for _ in range(3)]
+tu, ts = timeit(u), timeit(s)
+print(f"conv_h3 {tag} (with stats) " + " ".join(f"{t:.4f}" for t in tf) + f" ms ({3*B*E*H*W*4/min(tf)/1e6:.0f} GB/s at best) | "
+      f"tile GEMM {tu:.3f} ms + stats pass {ts:.3f} ms", flush=True)
 if os.environ.get("SDY_CONV_STAMPS"):
     import ctypes as C
     from importlib import import_module
@@ -33,4 +47,4 @@ if os.environ.get("SDY_CONV_STAMPS"):
     for t in range(3):
         s_ = v[t * 8:(t + 1) * 8]; nxt = v[(t + 1) * 8]
         d = [s_[i + 1] - s_[i] for i in range(7)] + [nxt - s_[7]]
-        print(f"tile {t}: total {sum(d)}: " + ", ".join(f"{n} {x}" for n, x in zip(names, d)))
+        print(f"{tag} tile {t}: total {sum(d)}: " + ", ".join(f"{n} {x}" for n, x in zip(names, d)), flush=True)
