@@ -1026,6 +1026,55 @@ struct sdy_vector_spectrum_args {
 int sdy_vector_degree_power(const sdy_vector_spectrum_args* args, void* stream);
 int sdy_vector_degree_power_host(const sdy_vector_spectrum_args* args);
 
+/* Relative vorticity, divergence, streamfunction and velocity potential of winds (no counterpart in the reference; the
+ * definition is the library's own): the coefficients of up to four scalar fields per wind from the
+ * products of the vector Legendre analysis, ready for the scalar synthesis.  With s and t as above (V = sum s Psi + t Phi) and
+ * the wind on a sphere of radius a written V = grad chi + r x grad psi (u = -d psi/dy + d chi/dx, v = d psi/dx + d chi/dy, so
+ * that zeta = laplace psi and delta = laplace chi), in the convention of sdy_sht_inverse:
+ *   psi(l,m) = a t(l,m) / sqrt(l (l + 1))      chi(l,m)   = a s(l,m) / sqrt(l (l + 1))
+ *   zeta(l,m) = -sqrt(l (l + 1)) t(l,m) / a    delta(l,m) = -sqrt(l (l + 1)) s(l,m) / a          all four zero at l = 0
+ * Solid-body rotation u = U cos(lat), v = 0 gives zeta = 2 U sin(lat) / a and psi = -a U sin(lat).
+ *
+ * sdy_helmholtz_factors_host: host-only, one row out[lmax] of the factor table: kind 0 is -sqrt(l (l + 1)) / radius (zeta,
+ * delta), kind 1 is radius / sqrt(l (l + 1)) (psi, chi); out[0] = 0, and out[l] = 0 for l > truncate when truncate >= 0 (a
+ * triangular truncation is a property of the table).  SDY_ERR_ARG for a NULL out, lmax < 1, a radius that is not finite and
+ * positive, or another kind.
+ *
+ * sdy_helmholtz_coefficients: one launch.
+ *   struct_size: sizeof of this structure (it is not part of the sdy_abi_check list; another value is refused).
+ *   Cs_d, Cs_m: dev float, what sdy_vector_legendre_fwd writes for ONE image (B = 1): [lmax][mtr][ri][fields].  The u fields are
+ *              the n_winds fields from u_offset, the v fields the n_winds fields from v_offset.  Entries with m > l and fields
+ *              outside the two runs are never read, except the fields that complete a run's last quad.
+ *   scale:     dev float [fields] or NULL for 1: what a field's stored coefficients are multiplied with, as in sdy_coef_rows.
+ *   factor:    dev double [n_out][lmax].
+ *   out:       dev float [lmax][mtr][ri][out_fields], for sdy_legendre_inv with B = 1, C = out_fields.  Output q < n_out of wind
+ *              i is field q * out_stride + i; it is part[q] (0: s, 1: t) with both components multiplied by factor[q][l] in
+ *              float64 and rounded once to fp32.  Exact zeros: row l = 0, entries with m > l, and every field no output names.
+ *              out must not overlap Cs_d or Cs_m.
+ * The arithmetic is csrc/helmholtz.h and csrc/vector_spectrum.h; a wind's values depend on its own eight coefficients only;
+ * device and host twin give the same bits.
+ * SDY_ERR_ARG, before anything is launched: NULL args / Cs_d / Cs_m / factor / out, another struct_size, n_out outside 1..4, a
+ * part outside {0, 1}, a non-positive lmax, mtr, fields, out_fields or n_winds, a negative offset or stride, a run or an output
+ * plane that leaves its tensor, planes closer than n_winds rounded up to four, out overlapping an input.
+ * SDY_ERR_ALIGN: fields, out_fields, u_offset, v_offset or out_stride not a multiple of 4; Cs_d, Cs_m, scale or out not
+ * 16-byte aligned, factor not 8-byte aligned.  SDY_ERR_UNSUPPORTED: 2^31 or more quads of fields in one call.
+ * The _host twin takes HOST pointers. */
+typedef struct sdy_helmholtz_args sdy_helmholtz_args;
+struct sdy_helmholtz_args {
+  size_t struct_size;
+  const float *Cs_d, *Cs_m;
+  const float* scale;
+  const double* factor;
+  float* out;
+  int lmax, mtr;
+  int fields, u_offset, v_offset, n_winds;
+  int out_fields, out_stride, n_out;
+  int part[4];
+};
+int sdy_helmholtz_factors_host(int lmax, double radius, int kind, int truncate, double* out);
+int sdy_helmholtz_coefficients(const sdy_helmholtz_args* args, void* stream);
+int sdy_helmholtz_coefficients_host(const sdy_helmholtz_args* args);
+
 /* Per-trajectory time variance and lag-1 autocorrelation at every grid point (no counterpart in the reference): the second
  * moments along time of a rollout, kept on the device.  A trajectory is a member of a sample, or a sample's target.  For its
  * counted times x_1 .. x_n (fp32) at one grid point, in run order (csrc/variability.h):

@@ -15,7 +15,7 @@ from .sfno import SphericalFourierNeuralOperatorNet  # noqa: F401
 from .sht import InverseRealSHT, RealSHT  # noqa: F401
 from .stepper import MultiStepStepper, Prescriber, SteppedData  # noqa: F401
 from .loop import NullAggregator, NullDataWriter, WindowStitcher, run_inference  # noqa: F401
-from . import checkpoint, conservation, corrector, data_writer, derived, eddies, ensemble, events, field_scores, fss, histogram, interface, member_mean, metrics, normalizer, ops, quantiles, rank_hist, regions, spacetime, spectrum, spells, synthetic, variability  # noqa: F401
+from . import checkpoint, conservation, corrector, data_writer, derived, eddies, ensemble, events, field_scores, fss, helmholtz, histogram, interface, member_mean, metrics, normalizer, ops, quantiles, rank_hist, regions, spacetime, spectrum, spells, synthetic, variability  # noqa: F401
 from .corrector import Corrector, CorrectorConfig  # noqa: F401
 from .conservation import (ConservationLoss, ConservationLossConfig, DerivedMetricsAggregator,  # noqa: F401
                            compute_dry_air_absolute_differences, get_dry_air_nonconservation)

@@ -323,6 +323,21 @@ class SdyVectorSpectrumArgs(_SizedStructure):
     ]
 
 
+class SdyHelmholtzArgs(_SizedStructure):
+    """`sdy_helmholtz_args`."""
+    _fields_ = [
+        ("struct_size", C.c_size_t),
+        ("Cs_d", C.c_void_p), ("Cs_m", C.c_void_p),
+        ("scale", C.c_void_p),
+        ("factor", C.c_void_p),
+        ("out", C.c_void_p),
+        ("lmax", C.c_int), ("mtr", C.c_int),
+        ("fields", C.c_int), ("u_offset", C.c_int), ("v_offset", C.c_int), ("n_winds", C.c_int),
+        ("out_fields", C.c_int), ("out_stride", C.c_int), ("n_out", C.c_int),
+        ("part", C.c_int * 4),
+    ]
+
+
 class SdyVariabilityArgs(C.Structure):
     _anonymous_ = ("win",)
     _fields_ = [
@@ -697,6 +712,9 @@ SIGNATURES = {
     "sdy_vector_legendre_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "sdy_vector_degree_power": (C.c_int, [C.POINTER(SdyVectorSpectrumArgs), C.c_void_p]),
     "sdy_vector_degree_power_host": (C.c_int, [C.POINTER(SdyVectorSpectrumArgs)]),
+    "sdy_helmholtz_factors_host": (C.c_int, [C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p]),
+    "sdy_helmholtz_coefficients": (C.c_int, [C.POINTER(SdyHelmholtzArgs), C.c_void_p]),
+    "sdy_helmholtz_coefficients_host": (C.c_int, [C.POINTER(SdyHelmholtzArgs)]),
     "sdy_time_variability_accumulate": (C.c_int, [C.POINTER(SdyVariabilityArgs), C.c_void_p]),
     "sdy_time_variability_accumulate_host": (C.c_int, [C.POINTER(SdyVariabilityArgs)]),
     "sdy_time_variability_maps": (C.c_int, [C.POINTER(SdyVariabilityMapsArgs), C.c_void_p]),

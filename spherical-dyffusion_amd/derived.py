@@ -175,3 +175,14 @@ def deriver(sigma_coordinates):
     host ONCE, here, so that applying it per window never waits for the device."""
     ak, bk = _host_levels(sigma_coordinates)
     return lambda data: _apply(data, ak, bk)
+
+
+def chain(*derivers):
+    """One callable for `run_inference(derive=...)` out of several, applied left to right: each takes the dict the one before it
+    returned (`chain(deriver(sigma_coordinates), helmholtz.deriver(names))`: the water budget, then the winds' fields)."""
+    def derive(data):
+        for d in derivers:
+            data = d(data)
+        return data
+
+    return derive
