@@ -12,8 +12,11 @@ Follows `src/diffusion/dyffusion.py`:
 and `InterpolationExperiment.get_dynamical_condition` (`src/experiment_types/interpolation.py:133-141`).
 
 `forecaster(x, time, **cond)` and `interpolator(x, time, **cond)` are callables (e.g. OracleSFNO.forward
-wrapped with a mask provider).  Only what the shipped configs exercise is restated
-(`schedule="before_t1_only"`, `forward_conditioning="none"`, `time_encoding="dynamics"`).
+wrapped with a mask provider).  Restated: `schedule="before_t1_only"`, `forward_conditioning="none"`,
+`time_encoding` "dynamics" and "discrete" (:286-297; "continuous" is not), `prediction_timesteps` of the refining sweep
+(:550-564).  `dynamic_cond_from_t="t"` is restated as `dyn[:, int(t)]`, the condition at the forecaster's input step: the
+reference itself raises there (`slice_time` indexes with a float tensor, :343,357-361), so for that switch this file is the
+only statement of the behaviour.
 """
 from __future__ import annotations
 
@@ -39,7 +42,12 @@ class OracleDYffusion:
         dynamic_cond_from_t: str = "h",
         sampling_schedule=None,
         enable_interpolator_dropout=True,
+        time_encoding: str = "dynamics",
+        prediction_timesteps=None,
     ):
+        assert time_encoding in ("dynamics", "discrete"), time_encoding
+        self.time_encoding = time_encoding
+        self.prediction_timesteps = prediction_timesteps
         self.forecaster, self.interpolator = forecaster, interpolator
         self.horizon = timesteps
         self.k = additional_interpolation_steps
@@ -111,12 +119,12 @@ class OracleDYffusion:
     # -- network calls ----------------------------------------------------------------------
     def predict_x_last(self, x0, x_t, t, **kwargs):
         B = x0.shape[0]
-        time = torch.full((B,), float(self.d2i(t)), dtype=torch.float32)
+        time = torch.full((B,), float(t if self.time_encoding == "discrete" else self.d2i(t)), dtype=torch.float32)
         dyn = kwargs.pop("dynamical_condition", None)
         cond = None
         if dyn is not None:
             assert dyn.shape[1] == self.num_timesteps + 1
-            cond = {"0": dyn[:, 0], "h": dyn[:, -1]}[self.dynamic_cond_from_t]
+            cond = {"0": dyn[:, 0], "h": dyn[:, -1], "t": dyn[:, int(t)]}[self.dynamic_cond_from_t]
         return self.forecaster(x_t, time=time, condition=cond, **kwargs)
 
     def q_sample(self, x0, x_end, t, interpolation_time=None, is_artificial_step=True, **kwargs):
@@ -139,6 +147,12 @@ class OracleDYffusion:
     # -- sampler ----------------------------------------------------------------------------
     @torch.no_grad()
     def sample(self, initial_condition, **kwargs) -> Dict[str, torch.Tensor]:
+        return self.sample_loop(initial_condition, **kwargs)[1]
+
+    @torch.no_grad()
+    def sample_loop(self, initial_condition, **kwargs):
+        """-> (final state, predictions): the state x_s when the schedule ends before the last diffusion step, else the
+        last forecast (:565-567)."""
         sched = self.sampling_schedule
         N = self.num_timesteps
         last_p1 = sched[-1] + 1
@@ -176,8 +190,10 @@ class OracleDYffusion:
                 preds = x_s if (self.cold_intermediate or is_last) else x_ip_next
                 out[f"t{dyn_step}_preds"] = preds[:, 1:] if self.hack else preds
         if self.refine:
-            for i_n in [i for i in self.dynamical_steps.values() if i < N]:
-                r = self.q_sample(xhat, initial_condition, None, interpolation_time=int(i_n), is_artificial_step=False,
+            for i_n in [i for i in (self.prediction_timesteps or self.dynamical_steps.values()) if i < N]:
+                label = int(i_n) if float(i_n).is_integer() else i_n
+                assert not float(i_n).is_integer() or f"t{label}_preds" in out
+                r = self.q_sample(xhat, initial_condition, None, interpolation_time=label, is_artificial_step=False,
                                   **dict(kwargs))
-                out[f"t{int(i_n)}_preds"] = r[:, 1:] if self.hack else r
-        return out
+                out[f"t{label}_preds"] = r[:, 1:] if self.hack else r
+        return (x_s if last_p1 < N else xhat), out

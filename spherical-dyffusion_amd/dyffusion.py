@@ -354,6 +354,13 @@ class DYffusion(torch.nn.Module):
         if hp.sampling_type not in ("cold", "naive"):
             raise ValueError(f"unknown sampling type {hp.sampling_type}")
         assert len(initial_condition.shape) == 4, f"condition.shape: {initial_condition.shape} (should be 4D)"
+        if hp.hack_for_imprecise_interpolation and not hp.use_cold_sampling_for_last_step \
+                and self.use_cold_sampling_for_init_of_ar_step:
+            # the state carries the input-only channel, the forecast does not: x_s + x_hat - I(x_0, x_hat, s) has no meaning
+            # (the reference fails on the same sum at dyffusion.py:508, after a whole pass of network calls)
+            raise RuntimeError("hack_for_imprecise_interpolation=True cannot be combined with use_cold_sampling_for_last_step="
+                               "False and use_cold_sampling_for_init_of_ar_step=True: the cold state that would seed the next "
+                               "window has one channel more than the forecast")
         sched, last = self.sampling_schedule, self.num_timesteps - 1
         cold = hp.sampling_type == "cold"
         preds: Dict[str, Tensor] = {}

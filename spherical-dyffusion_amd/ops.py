@@ -404,7 +404,16 @@ def irfft_lon_act(plan, Yf: torch.Tensor, bias: Optional[torch.Tensor], B: int, 
 
 
 def cold_update(x_s: torch.Tensor, x_ip_next: torch.Tensor, x_ip_s: Optional[torch.Tensor]) -> torch.Tensor:
-    """x_s + (x_ip_next - x_ip_s)  (`src/diffusion/dyffusion.py:517-519`); x_ip_s None means x_ip_s == x_s."""
+    """x_s + (x_ip_next - x_ip_s)  (`src/diffusion/dyffusion.py:517-519`); x_ip_s None means x_ip_s == x_s.
+    The kernel walks all operands with x_s's element count: operands of another shape, type or device are refused here
+    (ValueError), before anything is launched."""
+    for name, t in (("x_ip_next", x_ip_next), ("x_ip_s", x_ip_s)):
+        if t is not None and (t.shape != x_s.shape or t.device != x_s.device):
+            raise ValueError(f"cold_update: {name} is {tuple(t.shape)} on {t.device}, x_s is {tuple(x_s.shape)} on "
+                             f"{x_s.device}: all operands must have one shape on one device")
+    for name, t in (("x_s", x_s), ("x_ip_next", x_ip_next), ("x_ip_s", x_ip_s)):
+        if t is not None and t.dtype != torch.float32:
+            raise ValueError(f"cold_update: {name} is {t.dtype}, all operands must be float32")
     a, b = _f32c(x_s), _f32c(x_ip_next)
     c = _f32c(x_ip_s) if x_ip_s is not None else None
     out = torch.empty_like(a)
@@ -414,7 +423,18 @@ def cold_update(x_s: torch.Tensor, x_ip_next: torch.Tensor, x_ip_s: Optional[tor
 
 
 def concat_channels(tensors) -> torch.Tensor:
-    """torch.cat(tensors, dim=1) for up to 4 NCHW float32 tensors (`src/diffusion/dyffusion.py:655-661`)."""
+    """torch.cat(tensors, dim=1) for up to 4 NCHW float32 tensors (`src/diffusion/dyffusion.py:655-661`).  The kernel takes
+    B, H and W from the first tensor: inputs that are not all 4-D with one B, H and W on one device are refused here
+    (ValueError), before anything is launched."""
+    tensors = list(tensors)
+    if not 1 <= len(tensors) <= 4:
+        raise ValueError(f"concat_channels: 1 to 4 tensors, got {len(tensors)}")
+    first = tensors[0]
+    for i, t in enumerate(tensors):
+        if t.dim() != 4 or first.dim() != 4 or (t.shape[0], *t.shape[2:]) != (first.shape[0], *first.shape[2:]) \
+                or t.device != first.device:
+            raise ValueError(f"concat_channels: input {i} is {tuple(t.shape)} on {t.device}, input 0 is {tuple(first.shape)} on "
+                             f"{first.device}: all inputs must be (B, C_i, H, W) with one B, H and W on one device")
     ts = [_f32c(t) for t in tensors]
     if len(ts) == 1:
         return ts[0]

@@ -87,3 +87,33 @@ def seeded_case(z):
     idig = np.array([float(x.double().abs().sum()), float(cond.double().abs().sum())])
     assert np.allclose(idig, z["inputs_digest"], rtol=1e-9), "the seeded inputs no longer reproduce the fixture's"
     return cfg, n_in, n_cond, sd, x, cond, torch.from_numpy(z["time"])
+
+
+SWITCH_FIXTURES = ["fx_sample_sw_mid", "fx_sample_sw_discrete_k2", "fx_sample_sw_cond0", "fx_sample_sw_plus3",
+                   "fx_sample_sw_short", "fx_sample_sw_refine_pt", "fx_sample_sw_last_ar"]
+
+
+def _sums(tensors):
+    return [float(t.double().abs().sum()) for t in tensors], [float((t.double() ** 2).sum()) for t in tensors]
+
+
+def switch_case(name):
+    """A sampler fixture that stores outputs only (tools/gen_golden.py, gen_sample_switches) joined with the base fixture that
+    holds its networks and inputs: -> dict(base=<base npz>, hack, extra, ipol_min_time, x0, kw, ref, trace, final_state).
+    Refuses to return unless the base fixture's weights and inputs reproduce the checksums the generating run stored."""
+    import numpy as np
+
+    z = load(name)
+    zb = load(str(z["base"]))
+    kw = {k: torch.from_numpy(zb[k]) for k in ("dynamical_condition", "static_condition") if k in zb.files}
+    x0 = torch.from_numpy(zb["x0"])
+    for prefix, key in (("f::", "f_digest"), ("i::", "i_digest")):
+        a, s = _sums(state_dict(zb, prefix).values())
+        assert np.array_equal(np.array([sum(a), sum(s)]), z[key]), f"{name}: {key} is not that of {z['base']}"
+    a, s = _sums([x0] + list(kw.values()))
+    assert np.array_equal(np.array(a + s), z["inputs_digest"]), f"{name}: the inputs are not those of {z['base']}"
+    assert int(z["hack"]) == int(zb["hack"]) and int(z["dropout"]) == 0
+    return dict(base=zb, hack=bool(int(z["hack"])), extra=json.loads(str(z["diffusion_extra"])),
+                ipol_min_time=float(z["ipol_min_time"]), x0=x0, kw=kw, trace=json.loads(str(z["trace"])),
+                ref={k[5:]: torch.from_numpy(z[k]) for k in z.files if k.startswith("out::")},
+                final_state=torch.from_numpy(z["final_state"]) if "final_state" in z.files else None)

@@ -221,6 +221,86 @@ def test_cold_update_and_concat(sdy):
     assert torch.equal(cat, torch.cat([a, b[:, :1], c], 1))
 
 
+COLD_N = [1, 3, 4, 5, 1023, 2048 * 256 * 4 + 7]
+# (which pointer is off the 16-byte grid, x_ip_s given): without x_ip_s there is no third pointer to shift
+COLD_CASES = [(off, w) for off in ("none", "x_s", "x_ip_next", "x_ip_s", "out") for w in (True, False) if w or off != "x_ip_s"]
+
+
+def _same_with_nan(got, want):
+    """torch.equal, with NaN equal to NaN (the payload of a generated NaN is the hardware's)."""
+    nan = want.isnan()
+    zero = torch.zeros((), dtype=want.dtype)
+    return got.shape == want.shape and torch.equal(got.isnan(), nan) and \
+        torch.equal(torch.where(nan, zero, got), torch.where(nan, zero, want))
+
+
+@pytest.mark.parametrize("offset,with_ip_s", COLD_CASES)
+@pytest.mark.parametrize("n", COLD_N)
+def test_cold_update_edges(sdy, n, offset, with_ip_s):
+    """`sdy_cold_update` at the edges of its two loops, against fp32 a + (b - c) on the CPU, value for value:
+    n = 1, 3 (scalar tail only), 4 (one float4, no tail), 5, 1023 (tails of 1 and 3), 2048 * 256 * 4 + 7 (every thread of the
+    capped grid of 2048 workgroups takes one float4, seven threads a second one in the grid-stride loop, then a tail of 3).
+    `offset`: that operand (or the output) is a view 4 bytes off the 16-byte grid, all others aligned, so `vec == 0` and the
+    scalar loop takes the whole range -- through the C entry point, because ops.cold_update copies such a view before the
+    launch (that wrapper is checked on the aligned and on the offset operands as well: same values).  x_ip_s = None (c = a) on
+    both paths.  A NaN in x_s[0], +Inf in x_ip_next[n - 1], +Inf in x_ip_s[n // 2] and in x_s[n // 3] propagate as IEEE
+    arithmetic says (NaN, +Inf, -Inf or NaN, NaN from Inf - Inf when c = a).  Guard bands around every buffer stay untouched."""
+    from sdy_amd._lib import current_stream
+    from test_gpu_window_kernels import Buf
+
+    g = _gen(n)
+    a, b, c = (torch.randn(n, generator=g) for _ in range(3))
+    a[0], b[n - 1], c[n // 2] = float("nan"), float("inf"), float("inf")
+    if n > 3:
+        a[n // 3] = float("inf")
+    want = a + (b - (c if with_ip_s else a))
+    assert want.isnan().any() and (n < 4 or want.isinf().any())
+    ba, bb, bc = (Buf((n,), t, offset=int(offset == name)) for t, name in ((a, "x_s"), (b, "x_ip_next"), (c, "x_ip_s")))
+    out = Buf((n,), offset=int(offset == "out"))
+    assert sum(t.ptr % 16 != 0 for t in (ba, bb, bc, out)) == int(offset != "none")
+    assert sdy.lib.sdy_cold_update(ba.ptr, bb.ptr, bc.ptr if with_ip_s else None, out.ptr, n, current_stream()) == 0
+    assert _same_with_nan(out.t.cpu(), want)
+    assert out.guards_intact() and ba.unchanged() and bb.unchanged() and bc.unchanged()
+    if offset != "out":
+        got = sdy.ops.cold_update(ba.t, bb.t, bc.t if with_ip_s else None)
+        assert got.data_ptr() % 16 == 0 and _same_with_nan(got.cpu(), want)
+
+
+CONCAT_CHANS = [(1,), (3,), (1, 3), (3, 1), (2, 1, 3), (1, 2, 3, 2), (2, 3, 2, 1), (2, 1, 1, 3)]
+
+
+@pytest.mark.parametrize("H,W", [(1, 4), (4, 257)])
+@pytest.mark.parametrize("B", [1, 3])
+@pytest.mark.parametrize("chans", CONCAT_CHANS, ids=lambda c: "+".join(map(str, c)))
+def test_concat_channels_edges(sdy, chans, B, H, W):
+    """`sdy_concat_channels` == torch.cat(dim=1): one to four groups, a one-channel group first, in the middle and last,
+    B = 1 and 3, H * W = 4 (a single float4 per plane) and 4 * 257 (two workgroups, the second with one float4)."""
+    g = _gen(17)
+    srcs = [torch.randn(B, c, H, W, generator=g) for c in chans]
+    got = sdy.ops.concat_channels([s.cuda() for s in srcs])
+    assert got.shape == (B, sum(chans), H, W)
+    assert torch.equal(got.cpu(), torch.cat(srcs, dim=1))
+
+
+def test_pointwise_ops_refuse_mismatched_operands_on_the_device(sdy):
+    """The host checks of ops.cold_update / ops.concat_channels with device tensors (tests/test_sampler_guards_host.py holds the
+    same with CPU tensors): ValueError, nothing launched."""
+    a = torch.zeros(2, 7, 4, 8).cuda()
+    with pytest.raises(ValueError):
+        sdy.ops.cold_update(a, a[:, :6], a)           # the sampler's former 7 + 6 + 7 channels
+    with pytest.raises(ValueError):
+        sdy.ops.cold_update(a, a, a.double())
+    with pytest.raises(ValueError):
+        sdy.ops.cold_update(a, a, a.cpu())
+    for other in (torch.zeros(3, 7, 4, 8), torch.zeros(2, 7, 5, 8), torch.zeros(2, 7, 4, 12)):
+        with pytest.raises(ValueError):
+            sdy.ops.concat_channels([a, other.cuda()])
+        with pytest.raises(ValueError):
+            sdy.ops.concat_channels([other.cuda(), a[:, :1], a])
+    with pytest.raises(ValueError):
+        sdy.ops.concat_channels([a, a.cpu()])
+
+
 def test_errors_are_reported(sdy):
     with pytest.raises(sdy.SdyError):
         sdy.RealSHT(30, 62, grid="equiangular")(torch.zeros(1, 4, 30, 62).cuda())  # nlon % 4 != 0

@@ -142,6 +142,45 @@ def test_sampler_outside_k0_matches_reference(name, n_dropout_calls):
     assert len(gu.masks_per_forward(masks, SFNOConfig(**json.loads(str(z["icfg"]))))) == n_dropout_calls
 
 
+@pytest.mark.parametrize("name", gu.SWITCH_FIXTURES)
+def test_sampler_switches_match_reference(name):
+    """The oracle's restatement of the sampler's switches against the reference's own DYffusion.sample (fixtures of
+    tools/gen_golden.py, gen_sample_switches: intermediate steps not cold, discrete time encoding with two artificial steps,
+    dynamic_cond_from_t="0", fractional schedule steps, a schedule that ends early with the state it returns, the refining sweep
+    at prediction_timesteps with a fractional time, last step not cold with the cold state kept for the next window):
+    outputs, keys and the network call trace."""
+    case = gu.switch_case(name)
+    zb = case["base"]
+    fcfg = SFNOConfig(**json.loads(str(zb["fcfg"])))
+    icfg = SFNOConfig(**json.loads(str(zb["icfg"])))
+    # the valid time ranges the reference's experiments set: the interpolator's opened for artificial steps by the generator,
+    # the forecaster's is the diffusion steps under the discrete encoding (forecasting_multi_horizon.py:52-57)
+    icfg.min_time = case["ipol_min_time"]
+    if case["extra"].get("time_encoding") == "discrete":
+        fcfg.max_time = 5.0 + case["extra"].get("additional_interpolation_steps", 0)
+    fnet, inet = OracleSFNO(fcfg, gu.state_dict(zb, "f::")), OracleSFNO(icfg, gu.state_dict(zb, "i::"))
+    trace = []
+
+    def f(x, time, condition=None, static_condition=None):
+        trace.append(["F", float(time[0])])
+        return fnet(x, time=time, condition=condition, static_condition=static_condition)
+
+    def i(x, time, condition=None, static_condition=None):
+        trace.append(["I", float(time[0])])
+        return inet(x, time=time, condition=condition, static_condition=static_condition)
+
+    smp = OracleDYffusion(f, i, timesteps=6, hack_for_imprecise_interpolation=case["hack"], enable_interpolator_dropout=False,
+                          **case["extra"])
+    final, out = smp.sample_loop(case["x0"], **case["kw"])
+    assert sorted(out) == sorted(case["ref"])
+    assert trace == case["trace"]
+    for k, want in case["ref"].items():
+        err = rel_l2(out[k], want)
+        assert err < 5e-6, f"{name}/{k}: rel L2 {err:.3e}"
+    if case["final_state"] is not None:
+        assert final.shape == case["final_state"].shape and rel_l2(final, case["final_state"]) < 5e-6
+
+
 def test_call_trace_fixture():
     with open(os.path.join(gu.GOLDEN, "fx_trace.json")) as f:
         tr = json.load(f)

@@ -243,7 +243,30 @@ def build_experiments(C, n_forc, H, W, E, L, hack, dropout, seed_f, seed_i, extr
     return fc, ipol, fcfg, icfg, fsd, isd, cs
 
 
-def gen_sample(tag, hack, dropout, extra=None, ipol_min_time=1.0):
+def save_npz_fixed(path, arrays):
+    """np.savez_compressed, but every archive member carries one fixed timestamp (np.savez stamps the time of writing): the
+    same arrays give the same bytes, so a regenerated fixture can be compared with the committed one by checksum."""
+    import zipfile
+
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as zf:
+        for k, v in arrays.items():
+            info = zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            with zf.open(info, "w", force_zip64=True) as f:
+                np.lib.format.write_array(f, np.asanyarray(v), allow_pickle=False)
+
+
+def sample_case_digest(fsd, isd, inputs):
+    """Checksums of a sampler case's weights and inputs (x0, then the condition): what a fixture that stores only outputs keeps
+    of them, asserted against the base fixture that stores them whole."""
+    return dict(f_digest=_weights_digest(fsd), i_digest=_weights_digest(isd), inputs_digest=_digest(*inputs))
+
+
+def gen_sample(tag, hack, dropout, extra=None, ipol_min_time=1.0, base=None, keep_final=False):
+    """One DYffusion.sample of the reference on the tiny networks.  `base`: the name of a fixture with the same networks and
+    inputs -- the new fixture then stores the outputs, the trace and the configuration only, with checksums of weights and
+    inputs that are asserted against `base` here, and is written with fixed timestamps.  `keep_final`: also store what
+    `sample_loop` returns first (the final state)."""
     C, n_forc, H, W, E, L = 6, 2, 32, 64, 16, 2
     fc, ipol, fcfg, icfg, fsd, isd, cs = build_experiments(C, n_forc, H, W, E, L, hack, dropout, 11, 22, extra,
                                                            ipol_min_time=ipol_min_time)
@@ -263,10 +286,38 @@ def gen_sample(tag, hack, dropout, extra=None, ipol_min_time=1.0):
         lambda m, a, k: trace.append(["I", float(k["time"][0])] + ([bool(m.blocks[0].mlp.fwd[2].training)] if per_call_dropout else [])),
         with_kwargs=True)
     rec = MaskRecorder(i_net) if dropout else None
+    final = {}
+    if keep_final:      # `sample` drops sample_loop's first return value (dyffusion.py:565-572): record it on the way
+        loop = fc.model.sample_loop
+
+        def recording_loop(*a, **k):
+            final["state"], intermediates = loop(*a, **k)
+            return final["state"], intermediates
+        fc.model.sample_loop = recording_loop
     torch.manual_seed(4242)
     res = fc.model.sample(x0, **kw)     # DYffusion.sample (dyffusion.py:569-572)
     hf.remove()
     hi.remove()
+    if base is not None:
+        assert not dropout, "a fixture that leans on a base fixture stores no masks"
+        zb = np.load(os.path.join(OUT, f"{base}.npz"), allow_pickle=False)
+        dig = sample_case_digest(fsd, isd, [x0] + list(kw.values()))
+        want = sample_case_digest({k[3:]: torch.from_numpy(zb[k]) for k in zb.files if k.startswith("f::")},
+                                  {k[3:]: torch.from_numpy(zb[k]) for k in zb.files if k.startswith("i::")},
+                                  [torch.from_numpy(zb["x0"])] + [torch.from_numpy(zb[k]) for k in kw])
+        for k in dig:
+            assert np.array_equal(dig[k], want[k]), f"{tag}: {k} differs from {base}'s"
+        assert int(zb["hack"]) == int(hack)
+        out = dict(base=base, hack=np.array(int(hack)), dropout=np.array(0), trace=json.dumps(trace),
+                   diffusion_extra=json.dumps(extra or {}), ipol_min_time=np.array(float(ipol_min_time)), **dig)
+        for k, v in res.items():
+            out["out::" + k] = v.numpy()
+        if keep_final:
+            out["final_state"] = final["state"].numpy()
+        save_npz_fixed(os.path.join(OUT, f"{tag}.npz"), out)
+        print(f"{tag}: keys {sorted(res.keys())}, {len(trace)} network calls, "
+              f"{os.path.getsize(os.path.join(OUT, f'{tag}.npz'))} bytes, saved")
+        return trace
     out = dict(x0=x0.numpy(), hack=np.array(int(hack)), dropout=np.array(int(dropout)),
                fcfg=json.dumps(fcfg.__dict__), icfg=json.dumps(icfg.__dict__), trace=json.dumps(trace))
     if extra:
@@ -418,6 +469,50 @@ def gen_sample_artificial():
     t3 = gen_sample("fx_sample_tiny_naive", hack=True, dropout=True,
                     extra=dict(additional_interpolation_steps=1, sampling_type="naive"), ipol_min_time=0.0)
     return t1, t2, t3
+
+
+SWITCH_CASES = {
+    # tag: (hack, extra diffusion options, interpolator's minimal time, keep sample_loop's final state)
+    "fx_sample_sw_mid": (True, dict(use_cold_sampling_for_intermediate_steps=False), 1.0, False),
+    "fx_sample_sw_discrete_k2": (True, dict(time_encoding="discrete", additional_interpolation_steps=2), 0.0, False),
+    "fx_sample_sw_cond0": (False, dict(dynamic_cond_from_t="0"), 1.0, False),
+    "fx_sample_sw_plus3": (True, dict(additional_interpolation_steps=2, sampling_schedule="only_dynamics_plus3"), 0.0, False),
+    "fx_sample_sw_short": (True, dict(sampling_schedule=[0, 1, 2, 3]), 1.0, True),
+    "fx_sample_sw_refine_pt": (True, dict(refine_intermediate_predictions=True, prediction_timesteps=[1, 2.5, 4]), 1.0, False),
+    "fx_sample_sw_last_ar": (False, dict(use_cold_sampling_for_last_step=False, use_cold_sampling_for_init_of_ar_step=True),
+                             1.0, False),
+}
+
+
+def gen_sample_switches():
+    """The sampler's switches outside the shipped configuration, one reference pass each (src/diffusion/dyffusion.py:286-297
+    time encoding, :333-345 dynamic_cond_from_t, :367-455 schedules, :495-534 cold-sampling switches, :546-567 refining sweep
+    with prediction_timesteps and the final state of a schedule that ends early).  Networks and inputs are those of
+    fx_sample_tiny (no carried channel: dynamical condition) / fx_sample_tiny_hack (carried channel: static condition), so
+    only outputs, trace and configuration are stored (gen_sample, `base`).  Dropout off everywhere.
+    Two configurations the reference cannot run are asserted to fail as recorded in NOTEBOOK.md:
+      dynamic_cond_from_t="t"                                    IndexError (slice_time indexes with a float tensor, :343,360)
+      carried channel + last step not cold + cold AR init        RuntimeError (7-channel state + 6-channel forecast, :508)"""
+    traces = {}
+    for tag, (hack, extra, ipol_min_time, keep_final) in SWITCH_CASES.items():
+        traces[tag] = gen_sample(tag, hack=hack, dropout=False, extra=extra, ipol_min_time=ipol_min_time,
+                                 base="fx_sample_tiny_hack" if hack else "fx_sample_tiny", keep_final=keep_final)
+    for hack, extra, error in ((False, dict(dynamic_cond_from_t="t"), IndexError),
+                               (True, dict(use_cold_sampling_for_last_step=False, use_cold_sampling_for_init_of_ar_step=True),
+                                RuntimeError)):
+        C, n_forc, H, W = 6, 2, 32, 64
+        fc, _, _, _, _, _, cs = build_experiments(C, n_forc, H, W, 16, 2, hack, False, 11, 22, extra)
+        g = torch.Generator(device="cpu").manual_seed(1234)
+        x0 = torch.randn(2, cs, H, W, generator=g)
+        kw = {"static_condition": torch.randn(2, n_forc, H, W, generator=g)} if hack else \
+            {"dynamical_condition": torch.randn(2, 7, n_forc, H, W, generator=g)}
+        try:
+            fc.model.sample(x0, **kw)
+        except error as e:
+            print(f"reference with {extra}: {type(e).__name__}: {str(e)[:100]}")
+        else:
+            raise AssertionError(f"the reference no longer raises {error.__name__} with {extra}")
+    return traces
 
 
 def gen_stepper(tag="fx_stepper_tiny"):
@@ -1343,6 +1438,7 @@ if __name__ == "__main__":
     gen_sample("fx_sample_tiny_masks", hack=True, dropout=True)
     gen_sample_refine()
     gen_sample_artificial()
+    gen_sample_switches()
     gen_sample_fcond()
     with open(os.path.join(OUT, "fx_trace.json"), "w") as f:
         json.dump(t1, f)
