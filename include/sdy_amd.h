@@ -1562,6 +1562,61 @@ int sdy_time_covariance_stats(const sdy_time_covariance_stats_args* args, void* 
 int sdy_time_covariance_stats_host(const sdy_time_covariance_stats_args* args);
 size_t sdy_time_covariance_workspace_bytes(int K, int n_groups, int n1, int HW);   /* 0 for an argument out of range */
 
+/* Time sums and extremes per time bin (no counterpart in the reference): a window's times belong to different bins -- the
+ * months, seasons or years of a calendar, the hours of the day -- and every bin keeps its own float64 sum and, optionally,
+ * its fp32 maximum and minimum, per variable, trajectory and grid point, on the device.  One launch adds ONE window of a run of
+ * same-shaped variables.  One definition for the kernel and the _host twin: csrc/time_bins.h.  The structure carries
+ * struct_size (sizeof of the structure; a call with another value is refused with SDY_ERR_ARG) and is not part of the
+ * sdy_abi_check list.
+ *   window:     see sdy_window, plane = HW: n0 members, n1 samples
+ *   groups:     the counted times of the call, grouped by bin: group g is the bin group_bin[g] and the window times
+ *               times[group_end[g - 1]] .. times[group_end[g] - 1] (group_end[-1] = 0), ascending; every bin at most once,
+ *               every time at most once, at most SDY_BIN_MAX_TIMES times per call (the caller cuts a longer window into
+ *               calls, in time order).  n_groups == 0: nothing is counted, SDY_OK, nothing is launched.
+ *   Accumulators: a bin's block holds bin_vars >= nvars variables, of which this call's are the first nvars (the caller offsets
+ *               the pointers to the call's first variable): the element of (bin b, variable v, row r, point p) is at
+ *               ((b * bin_vars + v) * rows + r) * HW + p, so that one bin of a run of variables is the contiguous (bin_vars,
+ *               members, samples, HW) block that sdy_member_map_stats takes.
+ *   gen_sum:    dev double (n_bins, bin_vars, n0, n1, HW), row r = member * n1 + sample; pool_members != 0: (n_bins, bin_vars, 1,
+ *               n1, HW), the members of a sample added into one element.  Zeroed by the caller before the first call
+ *   target_sum: dev double (n_bins, bin_vars, n1, HW), likewise
+ *   gen_max, gen_min, target_max, target_min: dev float of the same shapes, all four or none; filled with -inf (max) and +inf
+ *               (min) by the caller before the first call: what an empty bin keeps
+ * CHAIN ORDER.  The sum of one (bin, element) is ONE sequential float64 chain acc = acc + (double)x over its counted times in
+ * the order given (run order, when the caller lists them so); pooled: the members in member order inside each time.  The
+ * accumulator is loaded, the group's values are added to it one by one, and it is stored: there is no per-window partial sum
+ * (sdy_member_time_sum folds one and is therefore not invariant).  Every bit is the same however a run is cut into windows and
+ * calls, in any layout (16-byte or scalar loads) and batch, in any order of the groups (bins are independent chains), and
+ * equal to the _host twin's.
+ * EXTREMES.  max: kept = x when x > kept or x is NaN, min likewise with <: a NaN makes the extreme of that bin and element NaN
+ * from then on (no later value compares above or below it).
+ * Exactly one thread owns an accumulator element (no atomics, no LDS): calls on the same accumulators must be ordered on a
+ * stream.  An accumulator element is read and written once per group of the call, every input value is read once.
+ * SDY_ERR_ARG, before anything is launched: what sdy_window refuses; NULL args, another struct_size, HW < 1, n_bins < 1,
+ * bin_vars < nvars, n_groups outside 0..SDY_BIN_MAX_TIMES, a bin outside 0..n_bins-1 or listed twice, a group_end that does
+ * not exceed the one before (an empty group) or exceeds SDY_BIN_MAX_TIMES, a time outside 0..T-1 or listed twice, the times of
+ * a group not ascending, NULL gen_sum / target_sum, a sum not 8-byte aligned, one extreme pointer without the others, an
+ * extreme not 4-byte aligned.
+ * SDY_ERR_UNSUPPORTED: n_bins*bin_vars*(n0 + 1)*n1*HW >= 2^50 (flat accumulator indices are 64-bit).
+ * The _host twin: the same structure with HOST pointers and the same checks. */
+#define SDY_BIN_MAX_TIMES 64
+typedef struct sdy_binned_sum_args sdy_binned_sum_args;
+struct sdy_binned_sum_args {
+  size_t struct_size;
+  sdy_window win;
+  int HW;
+  int n_bins, bin_vars;
+  int pool_members;
+  int n_groups;
+  int group_bin[SDY_BIN_MAX_TIMES];
+  unsigned short group_end[SDY_BIN_MAX_TIMES];
+  unsigned short times[SDY_BIN_MAX_TIMES];
+  double *gen_sum, *target_sum;
+  float *gen_max, *gen_min, *target_max, *target_min;
+};
+int sdy_binned_time_accumulate(const sdy_binned_sum_args* args, void* stream);
+int sdy_binned_time_accumulate_host(const sdy_binned_sum_args* args);
+
 /* The area-weighted Gram matrix of the member errors and the truth anomaly (no counterpart in the reference): what the energy
  * score, the member-to-member and member-to-truth distances of whole fields and the anomaly correlation are read from.  ONE
  * launch for all variables of one window.  window: see sdy_window, plane = HW: n0 = M members (1 for a deterministic run), n1

@@ -15,7 +15,7 @@ from .sfno import SphericalFourierNeuralOperatorNet  # noqa: F401
 from .sht import InverseRealSHT, RealSHT  # noqa: F401
 from .stepper import MultiStepStepper, Prescriber, SteppedData  # noqa: F401
 from .loop import NullAggregator, NullDataWriter, WindowStitcher, run_inference  # noqa: F401
-from . import checkpoint, conservation, corrector, data_writer, derived, eddies, ensemble, events, field_scores, fss, helmholtz, histogram, interface, member_mean, metrics, normalizer, ops, quantiles, rank_hist, regions, spacetime, spectrum, spells, synthetic, variability  # noqa: F401
+from . import checkpoint, conservation, corrector, data_writer, derived, eddies, ensemble, events, field_scores, fss, helmholtz, histogram, interface, member_mean, metrics, normalizer, ops, quantiles, rank_hist, regions, spacetime, spectrum, spells, synthetic, time_bins, variability  # noqa: F401
 from .corrector import Corrector, CorrectorConfig  # noqa: F401
 from .conservation import (ConservationLoss, ConservationLossConfig, DerivedMetricsAggregator,  # noqa: F401
                            compute_dry_air_absolute_differences, get_dry_air_nonconservation)
@@ -31,6 +31,7 @@ from .quantiles import TimeQuantileAggregator  # noqa: F401
 from .spacetime import SpaceTimeSpectra, SpaceTimeSpectrumAggregator  # noqa: F401
 from .variability import TimeVariabilityAggregator  # noqa: F401
 from .eddies import CovarianceGroups, EddyCovarianceAggregator  # noqa: F401
+from .time_bins import BinnedTimeMeanAggregator, TimeBins  # noqa: F401
 from .regions import RegionalMeanAggregator, Regions  # noqa: F401
 from .field_scores import FieldScoreAggregator, member_gram  # noqa: F401
 from .spectrum import KineticEnergySpectrumAggregator, PowerSpectrumAggregator, kinetic_energy_spectrum, power_spectrum  # noqa: F401

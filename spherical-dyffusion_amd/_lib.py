@@ -551,6 +551,26 @@ class SdyTimeCovarianceStatsArgs(_SizedStructure):
     ]
 
 
+SDY_BIN_MAX_TIMES = 64
+
+
+class SdyBinnedSumArgs(_SizedStructure):
+    """`sdy_binned_sum_args`: the counted times of one window, grouped by bin, into the bins' sums and extremes."""
+    _anonymous_ = ("win",)
+    _fields_ = [
+        ("struct_size", C.c_size_t),
+        ("win", SdyWindow), ("HW", C.c_int),
+        ("n_bins", C.c_int), ("bin_vars", C.c_int),
+        ("pool_members", C.c_int),
+        ("n_groups", C.c_int),
+        ("group_bin", C.c_int * SDY_BIN_MAX_TIMES),
+        ("group_end", C.c_ushort * SDY_BIN_MAX_TIMES),
+        ("times", C.c_ushort * SDY_BIN_MAX_TIMES),
+        ("gen_sum", C.c_void_p), ("target_sum", C.c_void_p),
+        ("gen_max", C.c_void_p), ("gen_min", C.c_void_p), ("target_max", C.c_void_p), ("target_min", C.c_void_p),
+    ]
+
+
 SDY_GRAM_MAX_MEMBERS = 64
 
 
@@ -747,6 +767,8 @@ SIGNATURES = {
     "sdy_time_covariance_stats": (C.c_int, [C.POINTER(SdyTimeCovarianceStatsArgs), C.c_void_p]),
     "sdy_time_covariance_stats_host": (C.c_int, [C.POINTER(SdyTimeCovarianceStatsArgs)]),
     "sdy_time_covariance_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "sdy_binned_time_accumulate": (C.c_int, [C.POINTER(SdyBinnedSumArgs), C.c_void_p]),
+    "sdy_binned_time_accumulate_host": (C.c_int, [C.POINTER(SdyBinnedSumArgs)]),
     "sdy_fss_accumulate": (C.c_int, [C.POINTER(SdyFssArgs), C.c_void_p]),
     "sdy_fss_accumulate_host": (C.c_int, [C.POINTER(SdyFssArgs)]),
     "sdy_fss_encode": (C.c_int, [C.POINTER(SdyFssArgs), C.c_void_p]),

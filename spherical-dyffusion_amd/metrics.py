@@ -28,6 +28,7 @@ from .regions import RegionalMeanAggregator, Regions
 from .spectrum import KineticEnergySpectrumAggregator, PowerSpectrumAggregator
 from .variability import TimeVariabilityAggregator
 from .eddies import CovarianceGroups, EddyCovarianceAggregator
+from .time_bins import BinnedTimeMeanAggregator, TimeBins
 from .windows import FieldAccumulator, TorchDistributed, fill_window, whole_ics_message, window_layouts  # noqa: F401
 
 
@@ -643,7 +644,16 @@ class InferenceAggregator:
     `get_eddy_covariance_data(label, a, b)`, and `cov_gen`, `cov_target`, `cov_bias`, `cov_rmse`, `corr_gen`, `corr_target`,
     `corr_bias` and `corr_defined_fraction` per group and pair, `time_variance_gen` / `time_variance_target` per group and
     variable and `eke_gen`, `eke_target`, `eke_ratio` per group with winds under `<label>/eddy_covariance/...`.  Its windows
-    must arrive in run order.  The default `None` adds nothing: the default key set of the logs does not change."""
+    must arrive in run order.  The default `None` adds nothing: the default key set of the logs does not change.
+
+    `time_bins=<sdy_amd.TimeBins>` adds `time_bins` (`sdy_amd.BinnedTimeMeanAggregator` on the denormalised data of
+    `time_bin_variables`, `None`: every generated variable): per bin of the run's times -- months, seasons, years, hours of the
+    day -- one time-mean map per member (`time_bin_per_member=False`: one for the pooled members) and the target's, with
+    `time_bin_extremes=True` the bin's maximum and minimum too, read with `get_time_bin_data()`, and `rmse`, `bias`,
+    `rmse_member_avg`, `bias_member_avg` and `crps` per bin and variable, `bin_range_gen` / `_target` / `_ratio`, `bin_std_gen` /
+    `_target` / `_ratio` and `centred_rmse` per variable under `<label>/time_bins/...`.  Per-member maps of every bin are large
+    (one bin of 25 members x 63 variables x 180 x 360: 0.85 GB): name the variables.  Its windows must not go back in time.  The
+    default `None` adds nothing: the default key set of the logs does not change."""
 
     accepts_sample_weights = True
 
@@ -659,7 +669,9 @@ class InferenceAggregator:
                  event_frequency_maps: bool = False, field_scores: bool = False, climatology=None,
                  event_neighbourhoods: Optional[Sequence[int]] = None, wind_pairs=None,
                  space_time_spectra: Optional[SpaceTimeSpectra] = None,
-                 eddy_covariances: Optional[CovarianceGroups] = None, event_spells: bool = False,
+                 eddy_covariances: Optional[CovarianceGroups] = None, time_bins: Optional[TimeBins] = None,
+                 time_bin_variables: Optional[Sequence[str]] = None, time_bin_extremes: bool = False,
+                 time_bin_per_member: bool = True, event_spells: bool = False,
                  time_quantiles: Optional[Sequence[float]] = None,
                  time_quantile_variables: Optional[Sequence[str]] = None):
         if log_video or enable_extended_videos or log_zonal_mean_images:
@@ -729,6 +741,10 @@ class InferenceAggregator:
         if eddy_covariances is not None:
             self._aggregators["eddy_covariance"] = EddyCovarianceAggregator(eddy_covariances, area_weights, dist=dist,
                                                                             target="denorm", metadata=metadata)
+        if time_bins is not None:
+            self._aggregators["time_bins"] = BinnedTimeMeanAggregator(
+                time_bins, area_weights, variables=time_bin_variables, per_member=time_bin_per_member,
+                extremes=time_bin_extremes, target="denorm", dist=dist, metadata=metadata)
 
     @torch.no_grad()
     def record_batch(self, loss, target_data, gen_data, target_data_norm, gen_data_norm, i_time_start: int = 0,
@@ -800,6 +816,13 @@ class InferenceAggregator:
     def get_eddy_covariance_data(self, label: str, a: str, b: str):
         """`EddyCovarianceAggregator.get_pair_data(label, a, b)` of the run (`eddy_covariances=...`)."""
         return self._aggregators["eddy_covariance"].get_pair_data(label, a, b)
+
+    def get_time_bin_data(self):
+        """`{"counts", "means", "extremes"}` of the run's `BinnedTimeMeanAggregator` (`time_bins=...`): `counts()`,
+        `get_bin_means()` and, with `time_bin_extremes=True`, `get_extremes()` (else None)."""
+        agg = self._aggregators["time_bins"]
+        return {"counts": agg.counts(), "means": agg.get_bin_means(),
+                "extremes": agg.get_extremes() if agg._extremes else None}
 
     def get_field_scores(self):
         """`FieldScoreAggregator.get_series()` of the run (`field_scores=True`)."""

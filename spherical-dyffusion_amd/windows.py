@@ -3,7 +3,7 @@ the layouts of a window's variables (`WindowLayout`, the Python side of `sdy_win
 variables one launch takes, and `FieldAccumulator`, the float64 accumulators that stay on the device.
 
 This module sits below `metrics`, `histogram`, `data_writer`, `spectrum`, `member_mean`, `rank_hist`, `events`, `fss`, `spells`,
-`variability`, `eddies`, `regions`, `field_scores`, `quantiles` and `spacetime` and imports none of them.
+`variability`, `eddies`, `time_bins`, `regions`, `field_scores`, `quantiles` and `spacetime` and imports none of them.
 """
 from __future__ import annotations
 
